@@ -300,7 +300,14 @@ def parse_args():
     ap.add_argument("--min-seconds", type=float, default=2.0,
                     help="after the K timed steps keep stepping (reported separately as `sustained`) until the GPU "
                          "has been busy this long, so that external samplers see the run")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path handed its caller in its last step to "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all); the inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -427,10 +434,34 @@ def make_inputs(cfg, B, T, rank):
     return id_lists, noise_w
 
 
-def timed_leg(ctx, eng, cfg, preset, B, T, steps, warmup, sync_ranks=True, scales=SCALES, resident_steps=0):
+DUMP_LIMIT = 64 << 20          # --dump-outputs: bytes written by one run, all ranks together
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> float32 / float64 array) as out_dir/<name>.npy, or <name>_rank<r>.npy on every
+    rank when N > 1. The arrays fill this rank's share of DUMP_LIMIT smallest first; one that does not fit whole is
+    replaced by a fixed, seeded sample of its elements in index order, with their flat indices in <name>_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    room = DUMP_LIMIT // world
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes + 128 > room:                  # (128: the .npy header)
+            k = min(a.size, max(0, room - 256) // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, f"{name}_index{suffix}.npy"), idx)
+            room -= idx.nbytes + 128
+            a = a.reshape(-1)[idx.astype(np.int64)]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        room -= a.nbytes + 128
+
+
+def timed_leg(ctx, eng, cfg, preset, B, T, steps, warmup, sync_ranks=True, scales=SCALES, resident_steps=0,
+              keep_last=False):
     """W untimed + exactly K timed steps bracketed by barrier + device synchronisation; max over ranks. A step spans what
     the reference's inferSeconds spans (piper.cpp:385-395): ids from host memory (pe_upload), the device pipeline with
-    both noise sites drawn by the engine (pe_run), int16 PCM in host memory (pe_fetch)."""
+    both noise sites drawn by the engine (pe_run), int16 PCM in host memory (pe_fetch). keep_last: the result also
+    carries `last`, the arrays the last timed step handed its caller (--dump-outputs)."""
     import torch
     id_lists, noise_w = make_inputs(cfg, B, T, ctx.rank)
     eng.set_seed(1234 + ctx.rank)
@@ -438,11 +469,11 @@ def timed_leg(ctx, eng, cfg, preset, B, T, steps, warmup, sync_ranks=True, scale
 
     def step():
         # the result views are used as the C ABI hands them out -- no Python-side copy of the samples inside the timed region.
-        # Returns the samples this step produced: the engine draws fresh duration noise every step (models.py:111), so the
-        # frame counts differ from step to step
+        # The caller reads the samples this step produced from them: the engine draws fresh duration noise every step
+        # (models.py:111), so the frame counts differ from step to step
         eng.upload_host(host_in)
         eng.run()
-        return eng.fetch_views(False, True).sample_offsets[B]
+        return eng.fetch_views(False, True)
 
     for _ in range(max(1, warmup)):          # (at least one untimed step: graph capture, and the frame counts below)
         step()
@@ -457,11 +488,17 @@ def timed_leg(ctx, eng, cfg, preset, B, T, steps, warmup, sync_ranks=True, scale
     t0 = time.perf_counter()
     total_samples = 0
     for _ in range(steps):
-        total_samples += step()
+        res = step()
+        total_samples += res.sample_offsets[B]
     torch.cuda.synchronize()
     if sync_ranks:
         ctx.barrier()
     elapsed_local = time.perf_counter() - t0
+    last = None
+    if keep_last:                  # (the views stay valid until the engine's next call)
+        r = eng._collect(res, want_audio=False, want_pcm=True)
+        last = {"pcm": np.concatenate(r.pcm).astype(np.float32), "frames": r.frames.astype(np.float64),
+                "sample_offsets": np.concatenate([[0], np.cumsum([p.size for p in r.pcm])]).astype(np.float64)}
     total_local = float(total_samples)
     if sync_ranks and ctx.dist is not None:
         elapsed = ctx.reduce(elapsed_local, "MAX")
@@ -483,7 +520,7 @@ def timed_leg(ctx, eng, cfg, preset, B, T, steps, warmup, sync_ranks=True, scale
     return {"value": total / elapsed, "ms_per_step": elapsed / steps * 1e3, "elapsed_local": elapsed_local,
             "frames": frames, "samples_per_step": samples_per_step, "launches": launches, "per_rank": per_rank,
             "id_lists": id_lists, "noise_w": noise_w, "step": step, "steps": steps, "warmup": warmup,
-            "device_resident_ms": resident_ms,
+            "device_resident_ms": resident_ms, "last": last,
             # frames per step averaged over the timed steps (every step draws its own duration noise)
             "avg_frames_per_step": total_local / max(steps, 1) / eng.hop}
 
@@ -575,7 +612,9 @@ def main():
     dbg(f"engine ready (broadcast {bcast_bytes} bytes in {t_bcast:.3f} s)")
 
     if args.stream_latency:
-        out = stream_latency(eng, cfg, preset, T, args.steps, args.warmup, ctx.rank)
+        out = stream_latency(eng, cfg, preset, T, args.steps, args.warmup, ctx.rank, keep_last=bool(args.dump_outputs))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out.pop("last"), ctx.rank, ctx.world)
         if ctx.rank == 0:
             print(json.dumps(out), flush=True)
         finish(ctx)
@@ -591,8 +630,11 @@ def main():
                           "what": "rank 0 alone (other ranks waiting at a barrier), same workload, same build"}
         ctx.barrier()
 
-    leg = timed_leg(ctx, eng, cfg, preset, B, T, args.steps, args.warmup, resident_steps=max(10, args.steps))
+    leg = timed_leg(ctx, eng, cfg, preset, B, T, args.steps, args.warmup, resident_steps=max(10, args.steps),
+                    keep_last=bool(args.dump_outputs))
     dbg(f"timed leg done: {leg['ms_per_step']:.3f} ms/step")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, leg["last"], ctx.rank, ctx.world)
     frames, id_lists, noise_w = leg["frames"], leg["id_lists"], leg["noise_w"]
 
     # ---- sustained: keep the GPU busy for >= --min-seconds in total (same step), reported separately
@@ -1152,34 +1194,39 @@ def pmc_traffic(preset, B, T, kernel):
     return None
 
 
-def stream_latency(eng, cfg, preset, T, steps, warmup, rank):
+def stream_latency(eng, cfg, preset, T, steps, warmup, rank, keep_last=False):
     """Time from the request to the first 45-frame chunk of PCM (encoder + durations + flow + one
     exact-halo vocoder window), like the "Latency" the reference's streaming script logs
-    (infer_onnx_streaming.py:118-121), over >= 100 requests; plus the whole-utterance streaming rate."""
+    (infer_onnx_streaming.py:118-121), over `steps` requests; plus the whole-utterance streaming rate.
+    keep_last: the result also carries `last`, the chunks of the last request (--dump-outputs)."""
     from piper_amd import weights as W
     ids = W.synthetic_phoneme_ids(T, rank, id_max=min(cfg.n_vocab - 1, 129))
     first, total, samples = [], [], 0
-    n = max(100, steps)
-    for i in range(n + warmup):
+    for i in range(steps + warmup):
         t0 = time.perf_counter()
         it = eng.stream(ids, SCALES, chunk_frames=45)
-        a, _ = next(it)
+        a, p = next(it)
         t1 = time.perf_counter()
-        cnt = a.size + sum(c[0].size for c in it)
+        chunks = [(a, p)] + list(it)
         t2 = time.perf_counter()
         if i >= warmup:
             first.append((t1 - t0) * 1e3)
             total.append((t2 - t0) * 1e3)
-            samples = cnt
+            samples = sum(c[0].size for c in chunks)
     first.sort()
     total.sort()
-    return {"metric": "p50 first-chunk latency", "value": first[len(first) // 2], "unit": "ms", "higher_is_better": False,
-            "p95_ms": first[int(len(first) * 0.95)], "n_gpus": 1, "steps": n, "warmup": warmup, "dtype": "f32",
-            "data": "synthetic", "vs_baseline": None,
-            "config": {"workload": f"BASELINE configs[4]: {preset} VITS voice, streaming decode, one {T}-id utterance, "
-                                   f"45-frame chunks, halo {eng.stream_halo} frames, {eng.stream_frames} frames total"},
-            "utterance_ms_p50": total[len(total) // 2],
-            "streaming_samples_per_s": samples / (total[len(total) // 2] * 1e-3)}
+    out = {"metric": "p50 first-chunk latency", "value": first[len(first) // 2], "unit": "ms", "higher_is_better": False,
+           "p95_ms": first[int(len(first) * 0.95)], "n_gpus": 1, "steps": steps, "warmup": warmup, "dtype": "f32",
+           "data": "synthetic", "vs_baseline": None,
+           "config": {"workload": f"BASELINE configs[4]: {preset} VITS voice, streaming decode, one {T}-id utterance, "
+                                  f"45-frame chunks, halo {eng.stream_halo} frames, {eng.stream_frames} frames total"},
+           "utterance_ms_p50": total[len(total) // 2],
+           "streaming_samples_per_s": samples / (total[len(total) // 2] * 1e-3)}
+    if keep_last:
+        out["last"] = {"audio": np.concatenate([c[0] for c in chunks]).astype(np.float32),
+                       "pcm": np.concatenate([c[1] for c in chunks]).astype(np.float32),
+                       "chunk_offsets": np.concatenate([[0], np.cumsum([c[0].size for c in chunks])]).astype(np.float64)}
+    return out
 
 
 def cpu_baseline(cfg, wts, ids, scales, noise_w, budget_s, preset="medium"):

@@ -147,3 +147,25 @@ def test_rocprof_clock_lookup_reads_the_committed_summaries():
     assert k and 5.0 < k["avg_us"] < 20.0 and k["source"].endswith("_b1_kernel_stats.csv")
     assert bench.rocprof_kernel_us("medium", 7, "gate4_kernel") is None
     assert bench.rocprof_kernel_us("medium", 1, "no_such_kernel") is None
+
+
+def test_dump_outputs_writes_float_arrays_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy; one that does not fit the cap is a seeded sample of its elements with
+    their indices beside it -- the same sample on every run, so that two builds can be compared element for element."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 16)
+    pcm = np.arange(40000, dtype=np.float32)
+    arrays = {"pcm": pcm, "frames": np.array([3.0, 5.0]), "sample_offsets": np.array([0.0, 768.0, 2048.0])}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["frames.npy", "pcm.npy", "pcm_index.npy", "sample_offsets.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 1 << 16
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(np.load(tmp_path / "a" / "frames.npy"), arrays["frames"])
+    idx, got = np.load(tmp_path / "a" / "pcm_index.npy"), np.load(tmp_path / "a" / "pcm.npy")
+    assert got.dtype == np.float32 and idx.dtype == np.float64 and got.size == idx.size > 1000
+    assert np.all(np.diff(idx) > 0) and np.array_equal(got, pcm[idx.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "r"), arrays, rank=1, world=2)
+    assert "pcm_rank1.npy" in os.listdir(tmp_path / "r")

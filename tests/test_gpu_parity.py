@@ -260,19 +260,17 @@ def test_cpp_piper_api_on_gpu(tmp_path):
 
 
 @pytest.mark.parametrize("name,preset", [("medium_voice.onnx", "medium"), ("high_voice.onnx", "high"), ("high_stream", "high")])
-def test_full_size_onnx_voices_load_on_gpu(name, preset):
-    """FULL-SIZE voices written by the reference's exporter (voices/, made by __graft_entry__.build() where the reference
-    is available: en_US-lessac-medium / -high shapes and the high voice's streaming pair) through pe_create on the GPU
-    box: the engine built from the .onnx must equal, bit for bit, the engine built from the weight blob of the same
-    file, carry the seeded weights (2e-6: the export folds the flow's weight norm), and match the oracle."""
+def test_full_size_onnx_voices_load_on_gpu(name, preset, tmp_path):
+    """FULL-SIZE voices written by the reference's exporter (en_US-lessac-medium / -high shapes and the high voice's
+    streaming pair; rebuilt byte for byte from tests/golden/full/ by oracle/voice_skeleton.py) through pe_create on the GPU
+    box: the engine built from the .onnx must equal, bit for bit, the engine built from the weight blob of the
+    same file, carry the seeded weights (2e-6: the export folds the flow's weight norm), and match the oracle."""
     import ctypes as C
     from oracle import vits_oracle as O
     from piper_amd import _lib as L
+    from oracle import voice_skeleton as S
     from piper_amd.engine import Engine
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = os.path.join(root, "voices", name)
-    if not os.path.exists(path):
-        pytest.skip("voices/ not present: run __graft_entry__.build() in the build container (needs /root/reference)")
+    path = S.fill(name, str(tmp_path))
     eng = Engine(onnx_path=path, device=0)                 # pe_create: parse the .onnx, pack, upload
     lib = L.get_lib()
     blob, n = C.c_void_p(), C.c_size_t()

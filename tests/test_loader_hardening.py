@@ -1,7 +1,7 @@
 """CPU tests: the structural .onnx loader (onnx_reader.cpp) against files rewritten the way post-export tooling
 rewrites real voices (SURVEY.md section 7 hard part A; TRAINING.md:234 recommends onnx-simplifier):
 numeral initialiser names, stripped node names, weights in Constant nodes, de-duplicated tensors, float_data
-encoding -- and, when the reference is available (build container), a freshly exported FULL-SIZE medium voice."""
+encoding -- and a FULL-SIZE medium voice exported by the reference's export path."""
 import ctypes as C
 import dataclasses
 import os
@@ -111,16 +111,12 @@ def test_resblock1_detected_without_names(lib, tmp_path):
     assert load(lib, out2)[0].resblock == 2
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/python/piper_train"),
-                    reason="needs the reference's exporter (build container only)")
 def test_full_size_medium_export_loads(lib, tmp_path):
-    """A full-size en_US-lessac-medium-shaped voice written by the reference's own export path at test time (63 MB, not
-    committed), also after the rewrites above."""
-    import subprocess
-    import sys
-    prefix = str(tmp_path / "medium_voice")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "oracle", "make_voice.py"), "medium", prefix],
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=1200)
+    """A full-size en_US-lessac-medium-shaped voice written by the reference's own export path (oracle/make_voice.py;
+    63 MB, not committed: rebuilt byte for byte from tests/golden/full/ by oracle/voice_skeleton.py), also after the
+    rewrites above."""
+    from oracle import voice_skeleton as S
+    prefix = S.fill("medium_voice.onnx", str(tmp_path))[:-len(".onnx")]
     size = os.path.getsize(prefix + ".onnx")
     assert abs(size - 63201294) / 63201294 < 0.01          # voices.json: en_US-lessac-medium is 63 201 294 bytes
     cfg = W.preset("medium")
