@@ -93,6 +93,17 @@ int pe_synthesize_batch(pe_engine* e, const int64_t* ids, const int64_t* offsets
  * is written straight into pinned host memory by the last kernel; want_audio adds a copy of the float waveform). */
 int pe_upload(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float scales[3],
               const int64_t* sids, const pe_noise* noise);
+
+/* Per-utterance scales: the same two calls with one triple per utterance -- scales[batch * 3], laid out as
+ * [utterance][noise_scale, length_scale, noise_w] -- so that one batch may mix speaking rates and variability. Utterance b is
+ * computed exactly as a call with scales b alone would compute it (the reference's Run() with its own `scales` tensor,
+ * piper.cpp:347-365; its batch export shares one tensor, so this goes beyond it). A NULL `scales` or a non-finite value is
+ * rejected (the message names the utterance) before anything of the engine changes: the next call works as usual. The
+ * one-triple entry points above are these calls with the triple repeated. */
+int pe_synthesize_batch_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                               const float* scales, const int64_t* sids, const pe_noise* noise, pe_result* result);
+int pe_upload_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                     const int64_t* sids, const pe_noise* noise);
 int pe_run(pe_engine* e);
 int pe_fetch(pe_engine* e, int want_audio, int want_pcm, pe_result* result);
 
@@ -159,7 +170,8 @@ int pe_speculation_stats(pe_engine* e, int64_t* runs, int64_t* misses);
 /* Session warm-up -- what loadModel's session creation does for ORT (piper.cpp:262-306: graph optimisation at load), here
  * for the hipGraphs: the kernel sequence of a call is captured once per shape bucket (ids in steps of 32 up to 512, then
  * 8 steps per octave; frames in steps of 64 up to 1024, then 16 per octave) and replayed afterwards; the cache keeps the
- * 256 most recently used graphs (PIPER_HIP_GRAPHS) and evicts one at a time. pe_warmup
+ * 256 most recently used graphs (PIPER_HIP_GRAPHS) and evicts one at a time. The scales are not part of a graph (the
+ * kernels read each utterance's triple from the call's input block), so one warm-up serves every scale value. pe_warmup
  *   - sizes the workspaces for calls of up to max_batch utterances x max_ids ids and frames_per_id * max_ids frames
  *     (<= 0: 8), so that no later call grows them (growth re-creates every graph), and
  *   - if sample_ids is given (a representative utterance of the voice: its frames-per-id ratio seeds the speculative
@@ -208,6 +220,10 @@ int32_t pe_group_size(pe_group* g);
 pe_engine* pe_group_engine(pe_group* g, int32_t i);           /* e.g. pe_set_seed / pe_get_info / pe_profile_* per device */
 int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
                               const float scales[3], const int64_t* sids, pe_result* result);
+/* ... with one triple per utterance (scales[batch * 3], as pe_synthesize_batch_scaled): each shard takes its utterances'
+ * triples along with their ids */
+int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                     const float* scales, const int64_t* sids, pe_result* result);
 /* which engine (index into the group) ran utterance i of the last call */
 int pe_group_assignment(pe_group* g, int32_t* engine_index, int64_t capacity);
 void pe_group_destroy(pe_group* g);
@@ -225,6 +241,10 @@ void pe_group_destroy(pe_group* g);
  * not be used directly while requests are in flight. */
 typedef struct pe_coalescer pe_coalescer;
 int pe_coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out);
+/* The same, but the leader merges queued requests WHATEVER their scales and uploads one triple per request
+ * (pe_upload_scaled): a server whose clients set their own speaking rate still runs one batched call. Each request still
+ * gets what its own B=1 call with its own scales computes. Requests with a non-finite scale are rejected on entry. */
+int pe_coalescer_create_mixed(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out);
 int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                             int16_t** pcm, int64_t* n_samples, int32_t* frames, double* infer_seconds, int32_t* batch_size);
 int pe_coalescer_stats(pe_coalescer* c, int64_t* engine_calls, int64_t* requests);

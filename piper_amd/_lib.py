@@ -14,13 +14,14 @@ LIB_PATH = os.path.join(_HERE, "libpiper_hip.so")
 SYMBOLS = [
     "pe_create", "pe_create_from_blob", "pe_weights_bound", "pe_create_in_arena", "pe_weights_used", "pe_arena_ready",
     "pe_onnx_to_blob", "pe_free", "pe_synthesize",
-    "pe_synthesize_batch", "pe_upload", "pe_run", "pe_fetch", "pe_stream_begin", "pe_stream_next",
+    "pe_synthesize_batch", "pe_synthesize_batch_scaled", "pe_upload", "pe_upload_scaled", "pe_run", "pe_fetch", "pe_stream_begin", "pe_stream_next",
     "pe_get_durations", "pe_get_info",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
     "pe_stream", "pe_debug_tensor", "pe_debug_randn", "pe_rng_calls", "pe_run_launches", "pe_speculation_stats", "pe_warmup", "pe_graph_stats", "pe_xcc_pattern", "pe_device_pci_bus_id", "pe_policy_describe", "pe_last_error", "pe_destroy",
-    "pe_group_create", "pe_group_broadcast_path", "pe_group_size", "pe_group_engine", "pe_group_synthesize_batch", "pe_group_assignment",
+    "pe_group_create", "pe_group_broadcast_path", "pe_group_size", "pe_group_engine", "pe_group_synthesize_batch", "pe_group_synthesize_batch_scaled",
+    "pe_group_assignment",
     "pe_group_destroy",
-    "pe_coalescer_create", "pe_coalescer_synthesize", "pe_coalescer_stats", "pe_coalescer_destroy",
+    "pe_coalescer_create", "pe_coalescer_create_mixed", "pe_coalescer_synthesize", "pe_coalescer_stats", "pe_coalescer_destroy",
 ]
 
 
@@ -57,7 +58,9 @@ def bind(path: str) -> C.CDLL:
     lib.pe_synthesize.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(PeNoise), C.POINTER(PeResult)]
     lib.pe_synthesize_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise),
                                         C.POINTER(PeResult)]
+    lib.pe_synthesize_batch_scaled.argtypes = lib.pe_synthesize_batch.argtypes
     lib.pe_upload.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise)]
+    lib.pe_upload_scaled.argtypes = lib.pe_upload.argtypes
     lib.pe_run.argtypes = [vp]
     lib.pe_fetch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PeResult)]
     lib.pe_stream_begin.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(PeNoise), i32p, i32p]
@@ -95,10 +98,12 @@ def bind(path: str) -> C.CDLL:
     lib.pe_group_engine.argtypes = [vp, C.c_int32]
     lib.pe_group_engine.restype = vp
     lib.pe_group_synthesize_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeResult)]
+    lib.pe_group_synthesize_batch_scaled.argtypes = lib.pe_group_synthesize_batch.argtypes
     lib.pe_group_assignment.argtypes = [vp, i32p, C.c_int64]
     lib.pe_group_destroy.argtypes = [vp]
     lib.pe_group_destroy.restype = None
     lib.pe_coalescer_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.pe_coalescer_create_mixed.argtypes = lib.pe_coalescer_create.argtypes
     lib.pe_coalescer_synthesize.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(C.POINTER(C.c_int16)), i64p,
                                             i32p, C.POINTER(C.c_double), i32p]
     lib.pe_coalescer_stats.argtypes = [vp, i64p, i64p]

@@ -152,13 +152,16 @@ void Engine::ensure_stage_a(int B, int Tmax) {
   const int Ts = rup(Tmax, 128);    // row strides are multiples of 128 columns (conv epilogue relies on it)
   auto carve = [&](char* base, size_t Bc, size_t T) -> size_t {
     Carver c(base);
-    // input block: [rng 4 x u64 | lengths Bc | speaker ids Bc | ids Bc x T] (contiguous, copied as one piece by upload())
-    d_in_ = c.take<char>(32 + (2 * Bc + Bc * T) * sizeof(int));
+    // input block: [rng 4 x u64 | lengths Bc | speaker ids Bc | scales Bc x 3 (padded to 4) | ids Bc x T] (contiguous,
+    // copied as one piece by upload())
+    const size_t ns = in_scale_slots(Bc);
+    d_in_ = c.take<char>(32 + (2 * Bc + ns + Bc * T) * sizeof(int));
     d_rng_ = reinterpret_cast<unsigned long long*>(d_in_);
     d_tlens_ = reinterpret_cast<int*>(d_in_ + 32);
     d_sids_ = d_tlens_ + Bc;
-    d_ids_ = d_sids_ + Bc;
-    in_bytes_ = 32 + (2 * Bc + Bc * T) * sizeof(int);
+    d_scales_ = reinterpret_cast<float*>(d_sids_ + Bc);
+    d_ids_ = d_sids_ + Bc + ns;
+    in_bytes_ = 32 + (2 * Bc + ns + Bc * T) * sizeof(int);
     d_dur_ = c.take<int>(Bc * T);
     d_cum_ = c.take<int>(Bc * T);
     d_frames_ = c.take<int>(Bc);
@@ -332,10 +335,11 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
 // the synthesis call
 // ------------------------------------------------------------------------------------------------
 
-void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const float scales[3],
-                    const int64_t* sids, const NoiseIn* noise) {
+void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
+                    const int64_t* sids, const NoiseIn* noise, bool per_utt) {
   EntryLock entry_lock;
   if (B <= 0 || B > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!scales) throw std::runtime_error("null scales");
   PE_HIP(hipSetDevice(device_));
   B_ = B;
   id_off_.assign(offsets, offsets + B + 1);
@@ -359,7 +363,8 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   unsigned long long* hr = reinterpret_cast<unsigned long long*>(h_in_);
   int* htl = reinterpret_cast<int*>(h_in_ + 32);
   int* hsid = htl + Bc;
-  int* hid = hsid + Bc;
+  float* hsc = reinterpret_cast<float*>(hsid + Bc);
+  int* hid = hsid + Bc + in_scale_slots(Bc);
   for (int b = 0; b < B; ++b) {
     int* row = hid + (size_t)b * Ts;
     const int64_t* src = ids + offsets[b];
@@ -380,6 +385,19 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
       if (sp < 0 || sp >= nspk_) throw std::runtime_error("speaker id outside [0, num_speakers)");
       hsid[b] = (int)sp;
     }
+  float ls_max = 0.f;
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < 3; ++k) hsc[(size_t)b * 3 + k] = scales[(per_utt ? (size_t)b * 3 : 0) + k];
+    const float ls = hsc[(size_t)b * 3 + 1];
+    if (ls > 0.f && std::isfinite(ls)) ls_max = std::max(ls_max, ls);
+  }
+  // (below half the slowest rate the ceil of every duration keeps the frames from shrinking in proportion: an over-guess
+  // stays a hit, an inflated ratio would oversize later calls)
+  spec_rel_.resize(B);
+  for (int b = 0; b < B; ++b) {
+    const float ls = hsc[(size_t)b * 3 + 1];
+    spec_rel_[b] = (ls > 0.f && std::isfinite(ls)) ? std::max(0.5f, ls / ls_max) : 1.f;
+  }
   // {seed, runs so far, serial of this upload}: the first kernel of every run() advances the counter on the device
   // (embed_kernel). Short calls enqueue no copy at all: embed_kernel reads the pinned block in place and publishes the
   // lengths / speaker ids / generator state to device memory for the kernels behind it (the serial tells it a replay
@@ -387,7 +405,8 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   hr[0] = seed_; hr[1] = call_; hr[2] = ++upload_serial_; hr[3] = 0;
   ids_zc_ = pol_.ids_from_host((long)B * Ts);
   if (!ids_zc_)
-    PE_HIP(hipMemcpyAsync(d_in_, h_in_, 32 + (2 * Bc + (size_t)B * Ts) * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(d_in_, h_in_, 32 + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int), hipMemcpyHostToDevice,
+                          stream_));
   scales_[0] = scales[0]; scales_[1] = scales[1]; scales_[2] = scales[2];
   have_noise_w_ = noise && noise->noise_w;
   have_noise_z_ = noise && noise->noise_z;
@@ -558,7 +577,11 @@ void Engine::run() {
   if (spec && spec_cooldown_ > 0) { --spec_cooldown_; spec = false; }
   int fguess = 0;
   if (spec) {
-    fguess = spec_fg_force_ ? spec_fg_force_ : frame_bucket((int)std::ceil(last_ratio_ * spec_margin_ * (float)Tmax_) + 1);
+    // ids counted at each utterance's rate relative to the call's slowest (engine.h: spec_rel_): a batch that mixes speaking
+    // rates is sized by its slow utterances, not by the longest text at a fast rate; a uniform call counts plain ids
+    float units = 0.f;
+    for (int b = 0; b < B; ++b) units = std::max(units, spec_rel(b) * (float)tlens_h_[b]);
+    fguess = spec_fg_force_ ? spec_fg_force_ : frame_bucket((int)std::ceil(last_ratio_ * spec_margin_ * units) + 1);
     if (fguess > MAX_FRAMES) spec = false;
   }
   if (spec) {
@@ -586,10 +609,9 @@ void Engine::run() {
     // profiles/r04_notes.md). Grids and clamps are sized by Fg_; the real counts arrive in finish_run().
     frames_h_.resize(B);
     for (int b = 0; b < B; ++b)
-      frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (float)tlens_h_[b]))) : Fg_;
+      frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%a|%a|%d|%d|%d|%a", B, Tg_, Ts_, scales_[1], scales_[2], (int)have_noise_w_,
-             Fs_, Fg_, scales_[0]);
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_);
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -604,7 +626,7 @@ void Engine::run() {
     ++spec_runs_;
     return;
   }
-  snprintf(key, sizeof(key), "A|%d|%d|%d|%a|%a|%d|%d", B, Tg_, Ts_, scales_[1], scales_[2], (int)have_noise_w_, Fs_);
+  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
   run_stage('A', key);
   ++call_;                                    // mirrors the device-side counter bump of this run
   PE_HIP(hipStreamSynchronize(stream_));      // the only data-dependent shape: F
@@ -617,7 +639,7 @@ void Engine::run() {
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d|%a", B, Fg_, Fs_, Ts_, scales_[0]);
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
     run_stage('B', key);
   }
 }
@@ -635,7 +657,7 @@ void Engine::finish_stage_b_sizes() {
   float ratio = 0.f;
   for (int b = 0; b < B; ++b) {
     Fmax = std::max(Fmax, frames_h_[b]);
-    ratio = std::max(ratio, (float)frames_h_[b] / (float)tlens_h_[b]);
+    ratio = std::max(ratio, (float)frames_h_[b] / (spec_rel(b) * (float)tlens_h_[b]));
   }
   if (Fmax > MAX_FRAMES)
     throw std::runtime_error("utterance too long: more than " + std::to_string(MAX_FRAMES) + " spectrogram frames "
@@ -667,7 +689,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d|%a", B_, Fg_, Fs_, Ts_, scales_[0]);
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d", B_, Fg_, Fs_, Ts_);
   run_stage('B', key);
   return false;
 }
@@ -729,7 +751,7 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
   spec_pending_ = false;
   Tg_ = std::min(id_bucket(Tmax_), Ts_);
   char key[160];
-  snprintf(key, sizeof(key), "A|%d|%d|%d|%a|%a|%d|%d", 1, Tg_, Ts_, scales_[1], scales_[2], (int)have_noise_w_, Fs_);
+  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", 1, Tg_, Ts_, (int)have_noise_w_, Fs_);
   run_stage('A', key);
   ++call_;
   PE_HIP(hipStreamSynchronize(stream_));
@@ -740,7 +762,7 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
   if (have_noise_z_) {
     issue_flow();
   } else {
-    snprintf(key, sizeof(key), "F|%d|%d|%d|%d|%a", 1, Fg_, Fs_, Ts_, scales_[0]);
+    snprintf(key, sizeof(key), "F|%d|%d|%d|%d", 1, Fg_, Fs_, Ts_);
     run_stage('F', key);
   }
   s_frames_ = Fmax_;

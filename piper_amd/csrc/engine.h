@@ -74,9 +74,11 @@ class Engine {
   size_t arena_used() const { return arena_off_; }
   const void* arena_base() const { return arena_; }
 
-  // Phase 1: copy inputs to HBM. ids: concatenated phoneme ids, offsets[B+1].
-  void upload(const int64_t* ids, const int64_t* offsets, int B, const float scales[3],
-              const int64_t* sids, const NoiseIn* noise);
+  // Phase 1: copy inputs to HBM. ids: concatenated phoneme ids, offsets[B+1]. scales: one {noise_scale, length_scale,
+  // noise_w} triple for every utterance, or (per_utt) [B][3], one triple per utterance. The triples are call inputs in
+  // device memory like the ids: no captured graph depends on their values.
+  void upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
+              const int64_t* sids, const NoiseIn* noise, bool per_utt = false);
   // Phase 2: the whole device pipeline (one host read-back of B frame counts in the middle).
   void run();
   // Phase 3: results to host (pinned buffers owned by the engine, valid until the next upload()).
@@ -172,7 +174,7 @@ class Engine {
   // options of one DDSConv run: ConvFlow.pre folded into the first layer, a 1x1 conv (+ spline) fused after the last
   struct DdsOpt {
     const float* pre_z = nullptr; long pre_z_bs = 0; const float* pre_w = nullptr; const float* pre_b = nullptr;
-    float z_scale = 1.f;
+    const float* z_scale = nullptr;   // per-utterance noise_scale_w, stride 3 (&d_scales_[2]); null: 1
     const float* post_w16 = nullptr; const float* post_bias = nullptr; int post_rows = 0;
     View post_out{nullptr, 0, 0};
     const float* zin = nullptr; long zin_bs = 0; int z_cs = 0, c0 = 0, c1 = 1; float* zout = nullptr; long zout_bs = 0;
@@ -336,7 +338,7 @@ class Engine {
   // per-call state
   int B_ = 0, Tmax_ = 0, Ts_ = 0, Fmax_ = 0, Fs_ = 0, Tg_ = 0, Fg_ = 0;
   bool use_graphs_ = true;
-  // hipGraphExec_t per (stage, shape bucket, scales), least recently used first: a new key beyond graph_cap_ entries
+  // hipGraphExec_t per (stage, shape bucket), least recently used first: a new key beyond graph_cap_ entries
   // evicts ONE graph (the coldest), never the whole cache
   struct GraphEntry { std::string key; void* exec; long launches; };
   std::list<GraphEntry> graphs_;
@@ -356,7 +358,11 @@ class Engine {
  private:
   long run_launches_ = 0;
   unsigned long long* d_rng_ = nullptr;       // {seed, call counter} read by randn_kernel
-  float scales_[3] = {0.667f, 1.0f, 0.8f};
+  float scales_[3] = {0.667f, 1.0f, 0.8f};         // utterance 0's triple of the last upload (pe_warmup's default)
+  // utterance b's length_scale relative to the slowest (largest) one of the call, >= 0.5: the speculative guess counts
+  // ids x this (1 for every utterance of a uniform call -- today's frames-per-id rule)
+  std::vector<float> spec_rel_;
+  float spec_rel(int b) const { return (size_t)b < spec_rel_.size() ? spec_rel_[b] : 1.f; }
   bool have_noise_w_ = false, have_noise_z_ = false;
   bool drew_w_ = false;                       // this call's duration noise is drawn by embed_kernel (small calls), not randn_kernel
   bool fold_dur_ = false;                  // the stage being issued is the one-graph form: regulate_kernel computes the durations
@@ -377,7 +383,9 @@ class Engine {
   char* wsB_ = nullptr; size_t wsB_bytes_ = 0;
   int *d_ids_ = nullptr, *d_tlens_ = nullptr, *d_sids_ = nullptr, *d_dur_ = nullptr, *d_cum_ = nullptr,
       *d_frames_ = nullptr;
-  // The small inputs of a call -- {seed, call}, lengths, speaker ids, phoneme ids -- are one contiguous block in the stage-A
+  float* d_scales_ = nullptr;        // [B][3] per-utterance {noise_scale, length_scale, noise_w}, part of the input block
+  static size_t in_scale_slots(size_t Bc) { return (3 * Bc + 3) & ~(size_t)3; }   // its 4-byte slots (ids stay 16-byte aligned)
+  // The small inputs of a call -- {seed, call}, lengths, speaker ids, scales, phoneme ids -- are one contiguous block in the stage-A
   // workspace (d_in_) mirrored by a pinned host block (h_in_): upload() fills the host block and enqueues ONE copy, no
   // synchronisation (the pinned block outlives the copy; the call's final synchronisation covers it)
   char* d_in_ = nullptr; char* h_in_ = nullptr; size_t in_bytes_ = 0, h_in_cap_ = 0;

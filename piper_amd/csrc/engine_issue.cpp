@@ -58,8 +58,9 @@ void Engine::issue_stage_a() {
       ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in_);
       ep.h_lens = reinterpret_cast<const int*>(h_in_ + 32);
       ep.h_sids = ep.h_lens + Bc;
-      ep.h_ids = ep.h_sids + Bc;
-      ep.d_lens = d_tlens_; ep.d_sids = d_sids_;
+      ep.h_scales = reinterpret_cast<const float*>(ep.h_sids + Bc);
+      ep.h_ids = ep.h_sids + Bc + in_scale_slots(Bc);
+      ep.d_lens = d_tlens_; ep.d_sids = d_sids_; ep.d_scales = d_scales_;
     }
     // small calls: the duration noise is drawn here too (one workgroup, <= 4 Philox blocks per thread), not by a launch of
     // its own in front of the first ConvFlow
@@ -246,7 +247,7 @@ void Engine::issue_stage_a() {
     PE_LAUNCH_KB("randn_kernel", 4.0 * 2.0 * tsum, launch::randn(stream_, noise_w_, (long)B * 2, T, (long)Ts, 0L, d_rng_, 0));
   if (!pol_.fuse_dp) {
     const long n = (long)B * 2 * Ts;
-    PE_LAUNCH_K("scale_kernel", launch::scale(dim3((unsigned)((n + 255) / 256)), stream_, noise_w_, z2_, n, scales_[2]));
+    PE_LAUNCH_K("scale_kernel", launch::scale(dim3((unsigned)((n + 255) / 256)), stream_, noise_w_, z2_, n, d_scales_ + 2, (long)2 * Ts));
   }
   // Flip is folded into which physical channel is x0 (conditioning) and which is x1 (transformed):
   // logical = physical when an even number of flips has been applied.
@@ -263,7 +264,7 @@ void Engine::issue_stage_a() {
       const float* zin = fi == 0 ? noise_w_ : z2_;
       DdsOpt o;
       o.pre_z = zin + (long)c0 * Ts; o.pre_z_bs = (long)2 * Ts; o.pre_w = cf.pre_w; o.pre_b = cf.pre_b;
-      o.z_scale = fi == 0 ? scales_[2] : 1.f;
+      o.z_scale = fi == 0 ? d_scales_ + 2 : nullptr;
       o.post_w16 = cf.proj16; o.post_bias = cf.proj.bias; o.post_rows = cf.proj.rows;
       o.zin = zin; o.zin_bs = (long)2 * Ts; o.z_cs = Ts; o.c0 = c0; o.c1 = c1; o.zout = z2_; o.zout_bs = (long)2 * Ts;
       dds(cf.dds, xg, dh, dy2, &o);
@@ -279,7 +280,7 @@ void Engine::issue_stage_a() {
   {
     const int c0 = (flips & 1) ? 1 : 0;     // physical channel holding logical channel 0 = logw
     DurP dp{};
-    dp.z0 = z2_ + (long)c0 * Ts; dp.z_bs = (long)2 * Ts; dp.m0 = ea_m0_; dp.es0 = ea_es0_; dp.length_scale = scales_[1];
+    dp.z0 = z2_ + (long)c0 * Ts; dp.z_bs = (long)2 * Ts; dp.m0 = ea_m0_; dp.es0 = ea_es0_; dp.scales = d_scales_;
     dp.lens = d_tlens_; dp.dur = d_dur_; dp.cum = d_cum_; dp.d_bs = Ts; dp.frames = d_frames_; dp.logw_out = logw_;
     dp.frames_host = h_frames_; dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
     // the whole utterance as one graph: regulate_kernel, first launch of stage B, computes the durations itself
@@ -318,7 +319,7 @@ void Engine::issue_flow() {
     rp.stats = stats_; rp.s_bs = (long)2 * C_ * Ts; rp.s_cs = Ts;
     rp.cum = d_cum_; rp.d_bs = Ts; rp.tlens = d_tlens_; rp.frames = lens_b_;
     rp.noise = noise_z_; rp.n_bs = (long)C_ * Fs; rp.n_cs = Fs;
-    rp.noise_scale = scales_[0];
+    rp.scales = d_scales_;
     rp.out = zp_; rp.o_bs = (long)C_ * Fs; rp.o_cs = Fs; rp.C = C_;
     rp.absmax = absmax_;
     rp.rng = d_rng_; rp.gen = have_noise_z_ ? 0 : 1;

@@ -455,7 +455,7 @@ void Engine::dds_params(const DdsW& d, View in, View out, View tmp, const DdsOpt
     if (opt && i == 0 && opt->pre_z) {
       p.pre_z = opt->pre_z; p.pre_z_bs = opt->pre_z_bs; p.pre_w = opt->pre_w; p.pre_b = opt->pre_b;
     }
-    p.z_scale = opt ? opt->z_scale : 1.f;
+    p.z_scale = opt ? opt->z_scale : nullptr;
     if (opt && i == n - 1 && opt->post_w16) {
       p.post_w16 = opt->post_w16; p.post_w4 = w4_of(opt->post_w16); p.post_bias = opt->post_bias; p.post_rows = opt->post_rows;
       p.post_out = opt->post_out.p; p.po_bs = opt->post_out.bs; p.po_cs = opt->post_out.cs;

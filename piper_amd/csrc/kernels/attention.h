@@ -12,7 +12,7 @@ namespace pe {
 // Text-encoder embedding: x[b][h][t] = emb[id][h] * sqrt(H)  (models.py:199-200)
 // The first kernel of every pipeline run also advances the RNG call counter (state[1]) that both randn sites of
 // the run read afterwards, so a replayed graph draws fresh noise on every run without a host copy.
-// Zero-copy inputs (p.h_ids != null): the call's ids / lengths / speaker ids / {seed, counter} are read straight from
+// Zero-copy inputs (p.h_ids != null): the call's ids / lengths / speaker ids / scales / {seed, counter} are read straight from
 // the pinned host block upload() filled (the counterpart of pcm16_kernel writing the PCM straight into pinned host
 // memory): no copy is enqueued in front of the graph. state[2] remembers the upload that was ingested last, so a replay
 // without a new upload keeps counting on the device.
@@ -25,7 +25,14 @@ __global__ void embed_kernel(EmbedP p) {
   const int len = (zc ? p.h_lens : p.lens)[b];
   const int id = (zc ? p.h_ids : p.ids)[(long)b * p.ids_bs + (t < p.ids_bs ? t : 0)];
   if (blockIdx.x == 0 && blockIdx.y == 0) {
-    if (threadIdx.x == 0 && zc) { p.d_lens[b] = len; p.d_sids[b] = p.h_sids[b]; }
+    if (threadIdx.x == 0 && zc) {
+      // every host read in flight before the first store (a store ahead of a load it might alias would serialise the
+      // PCIe round trips)
+      const int sid = p.h_sids[b];
+      const float s0 = p.h_scales[3 * b], s1 = p.h_scales[3 * b + 1], s2 = p.h_scales[3 * b + 2];
+      p.d_lens[b] = len; p.d_sids[b] = sid;
+      p.d_scales[3 * b] = s0; p.d_scales[3 * b + 1] = s1; p.d_scales[3 * b + 2] = s2;
+    }
     if (b == 0) {
       // the state of this run, read by every thread of the workgroup BEFORE thread 0 replaces it (no other workgroup reads it)
       const bool fresh = zc && p.h_rng[2] != p.rng[2];

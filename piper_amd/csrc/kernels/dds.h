@@ -144,6 +144,7 @@ __device__ __forceinline__ void dds_layer16_body(const DdsP& p, int ctile, int b
   const bool okb = t < Lb;
   const float* xb = p.x + (long)b * p.x_bs;
   float* ob = p.out + (long)b * p.o_bs;
+  const float zscale = p.z_scale ? p.z_scale[3 * b] : 1.f;     // utterance b's noise_scale_w (first flow), one scalar load
   const int pad = (p.dw_k - 1) / 2 * p.dw_dil;
   const bool fold = p.pre_z != nullptr;
   // this wave's 1x1-conv weight row blocks: in flight under phase 1
@@ -170,7 +171,7 @@ __device__ __forceinline__ void dds_layer16_body(const DdsP& p, int ctile, int b
     for (int kk = 0; kk < MAXK; ++kk) {
       const int tt = t + kk * p.dw_dil - pad;
       const bool tv = okb && kk < p.dw_k && tt >= 0 && tt < Lb;
-      zt[kk] = pe_row_load(zd, tv ? tt : -1) * p.z_scale;
+      zt[kk] = pe_row_load(zd, tv ? tt : -1) * zscale;
     }
 #pragma unroll
     for (int k = 0; k < NVT; ++k) {
@@ -329,8 +330,8 @@ __device__ __forceinline__ void dds_layer16_body(const DdsP& p, int ctile, int b
       for (int i = 0; i <= NB; ++i) dv[i] = S[(scol * 3 + 2) * 16 + i];
       const float* zi = p.zin + (long)b * p.zin_bs;
       float* zo = p.zout + (long)b * p.zout_bs;
-      const float x1 = zi[(long)p.c1 * p.z_cs + st] * p.z_scale;
-      const float x0 = zi[(long)p.c0 * p.z_cs + st] * p.z_scale;
+      const float x1 = zi[(long)p.c1 * p.z_cs + st] * zscale;
+      const float x0 = zi[(long)p.c0 * p.z_cs + st] * zscale;
       zo[(long)p.c1 * p.z_cs + st] = (x1 >= -5.0f && x1 <= 5.0f) ? spline_finish(uw, uh, dv, x1) : x1;
       zo[(long)p.c0 * p.z_cs + st] = x0;
     }

@@ -10,7 +10,7 @@ namespace pe {
 
 // ElementwiseAffine reverse + durations (modules.py:407-409; models.py:702-704):
 //   logw = (z0 - m0) * exp(-logs0); w = exp(logw) * length_scale; d = ceil(w);
-//   cum = inclusive prefix sum; frames = max(sum d, 1).   One block per utterance.
+//   cum = inclusive prefix sum; frames = max(sum d, 1).   One block per utterance, length_scale = that utterance's own.
 // Sums run in 64 bits and are clamped to MAX_FRAMES + 1 (a single duration to 1e6): an absurd length_scale cannot
 // overflow `cum`, and the host rejects frames > MAX_FRAMES before sizing stage B from it.
 __global__ __launch_bounds__(256) void duration_kernel(DurP p) {
@@ -18,6 +18,7 @@ __global__ __launch_bounds__(256) void duration_kernel(DurP p) {
   __shared__ long long part[256];
   const int b = blockIdx.x;
   const int T = p.lens[b], tid = threadIdx.x;
+  const float length_scale = p.scales[3 * b + 1];
   const int per = (T + 255) / 256;
   const int lo = tid * per, hi = (lo + per < T) ? lo + per : T;
   long long s = 0;
@@ -25,7 +26,7 @@ __global__ __launch_bounds__(256) void duration_kernel(DurP p) {
     for (int t = lo; t < hi; ++t) {
       const float zv = p.z0[(long)b * p.z_bs + t];
       const float logw = (zv - p.m0) * p.es0;
-      const float w = expf(logw) * p.length_scale;
+      const float w = expf(logw) * length_scale;
       float c = ceilf(w);
       c = c < 0.f ? 0.f : (c > 1.0e6f ? 1.0e6f : c);
       const int d = (int)c;
@@ -78,7 +79,7 @@ __global__ void randn_kernel(float* out, long rows, int cols, long stride, long 
 // ------------------------------------------------------------------------------------------------
 // Length regulator + prior sample (models.py:705-718, commons.py:116-129). The reference multiplies
 // by a one-hot path matrix; the same result is a gather: frame f takes id i with cum[i-1] <= f < cum[i].
-//   z_p[c][f] = m_p[c][i] + noise[c][f] * exp(logs_p[c][i]) * noise_scale
+//   z_p[c][f] = m_p[c][i] + noise[c][f] * exp(logs_p[c][i]) * noise_scale     (noise_scale: utterance b's own)
 // One thread = four consecutive frames of one channel = one Philox block of the prior-noise stream (site 1): with
 // p.gen the N(0,1) draws are made here -- exactly the values randn_kernel would have written, which are stored to
 // `noise` as well (pe_debug_tensor, tests) -- instead of by a launch of their own in front of this one. With p.fold
@@ -106,13 +107,14 @@ __global__ __launch_bounds__(256) void regulate_kernel(RegP p) {
   if (p.fold) {
     // ---- duration_kernel's arithmetic (modules.py:407-409; models.py:702-704), ids [lo, hi) per thread
     const DurP& d = p.dur;
+    const float length_scale = d.scales[3 * b + 1];
     const int per = (T + 255) / 256;
     const int lo = tid * per < T ? tid * per : T, hi = (lo + per < T) ? lo + per : T;
     long long s = 0;
     for (int t = lo; t < hi; ++t) {
       const float zv = d.z0[(long)b * d.z_bs + t];
       const float logw = (zv - d.m0) * d.es0;
-      const float w = expf(logw) * d.length_scale;
+      const float w = expf(logw) * length_scale;
       float c = ceilf(w);
       c = c < 0.f ? 0.f : (c > 1.0e6f ? 1.0e6f : c);
       const int dv = (int)c;
@@ -190,10 +192,11 @@ __global__ __launch_bounds__(256) void regulate_kernel(RegP p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) nz[k] = (nrow && f0 + k < F) ? nrow[k] : 0.f;
   }
+  const float noise_scale = p.scales[3 * b];
   float* ob = p.out + (long)b * p.o_bs + (long)c * p.o_cs + f0;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    if (f0 + k < F) ob[k] = m[k] + nz[k] * expf(lg[k]) * p.noise_scale;
+    if (f0 + k < F) ob[k] = m[k] + nz[k] * expf(lg[k]) * noise_scale;
 }
 
 }  // namespace pe

@@ -8,9 +8,10 @@
 
 namespace pe {
 
-__global__ void scale_kernel(const float* in, float* out, long n, float s) {
+// out[i] = in[i] * s[3 b] with b = i / per_utt: every utterance's elements scaled by its own noise_scale_w
+__global__ void scale_kernel(const float* in, float* out, long n, const float* s, long per_utt) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[i] * s;
+  if (i < n) out[i] = in[i] * s[3 * (i / per_utt)];
 }
 
 // Speaker conditioning (models.py:692-696 emb_g; :66-68 dp.cond; modules.py:188-199 WN.cond_layer;

@@ -54,7 +54,7 @@ void cf_pre(dim3 grid, hipStream_t stream, const float* z0, long z_bs, const flo
             long g_bs, int g_cs, float* out, long o_bs, int o_cs, const int* lens, int H);
 void spline_inverse(dim3 grid, hipStream_t stream, const float* hproj, long h_bs, int h_cs, float* z1, long z_bs,
                     const int* lens, float inv_sqrt_h);
-void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, float s);
+void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, const float* s, long per_utt);
 void duration(dim3 grid, hipStream_t stream, const DurP& p);
 void randn(hipStream_t stream, float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
            int site);

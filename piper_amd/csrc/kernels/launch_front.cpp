@@ -95,8 +95,8 @@ void spline_inverse(dim3 grid, hipStream_t stream, const float* hproj, long h_bs
   PE_LAUNCH(spline_inverse_kernel, grid, dim3(64), 0, stream, hproj, h_bs, h_cs, z1, z_bs, lens, inv_sqrt_h);
 }
 
-void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, float s) {
-  PE_LAUNCH(scale_kernel, grid, dim3(256), 0, stream, in, out, n, s);
+void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, const float* s, long per_utt) {
+  PE_LAUNCH(scale_kernel, grid, dim3(256), 0, stream, in, out, n, s, per_utt);
 }
 
 void duration(dim3 grid, hipStream_t stream, const DurP& p) { PE_LAUNCH(duration_kernel, grid, dim3(256), 0, stream, p); }

@@ -114,7 +114,9 @@ struct DdsP {
   // layer of a ConvFlow: the input is  pre_w[c] * (z0[t] * z_scale) + pre_b[c] + x[c][t]  with x = the conditioning g.
   const float* pre_z; long pre_z_bs;        // z0 row of utterance b (null: no fold)
   const float* pre_w; const float* pre_b;
-  float z_scale;                            // noise_scale_w on the first flow (z is still the raw N(0,1) draw), else 1
+  // noise_scale_w of utterance b at z_scale[3 b] on the first flow (z is still the raw N(0,1) draw: &scales[0][2] of the
+  // per-utterance [B][3] array); null: 1
+  const float* z_scale;
   // Optional second 1x1 conv on the layer's output columns (last layer of a DDSConv: dp.proj / ConvFlow.proj,
   // models.py:65, modules.py:507), weights in the 16x16x4 fragment order; the layer output itself is then not stored.
   const float* post_w16; const float* post_w4; const float* post_bias; int post_rows;
@@ -189,8 +191,8 @@ struct EmbedP {
   // Zero-copy inputs (null: upload() copied the input block to the device). The pinned host mirror of the block is read
   // in place: ids and lengths by every workgroup that needs them, lengths / speaker ids / {seed, counter} published to
   // device memory for the kernels behind this one.
-  const unsigned long long* h_rng; const int* h_lens; const int* h_sids; const int* h_ids;
-  int* d_lens; int* d_sids;
+  const unsigned long long* h_rng; const int* h_lens; const int* h_sids; const float* h_scales; const int* h_ids;
+  int* d_lens; int* d_sids; float* d_scales;   // (scales: [B][3] per utterance {noise_scale, length_scale, noise_w})
   // Optional (small calls): the duration noise of models.py:111 -- rows 2 b, 2 b + 1 of the site-0 stream, draw_cols columns,
   // exactly the values randn_kernel writes -- drawn by workgroup (0, 0, 0), the one that advances the generator state, with
   // the state it publishes; null: randn_kernel draws it in a launch of its own.
@@ -200,7 +202,8 @@ struct EmbedP {
 // ---- durations, N(0,1) generator, length regulator (duration.h)
 static constexpr int MAX_FRAMES = 60000;      // per-utterance activations stay below the 2 GiB descriptor range
 struct DurP {
-  const float* z0; long z_bs; float m0, es0, length_scale;
+  const float* z0; long z_bs; float m0, es0;
+  const float* scales;                         // [B][3] per utterance {noise_scale, length_scale, noise_w} (device)
   const int* lens; int* dur; int* cum; int d_bs; int* frames; float* logw_out;
   int* frames_host; int* frames_clamped; int frame_cap;
 };
@@ -211,7 +214,7 @@ struct RegP {
   const int* cum; int d_bs;
   const int* tlens; const int* frames;
   float* noise; long n_bs; int n_cs;           // [B][C][>=F]: read (injected noise), or written by the kernel's own draws (gen)
-  float noise_scale;
+  const float* scales;                         // [B][3] per utterance {noise_scale, length_scale, noise_w} (device)
   float* out; long o_bs; int o_cs;
   int C;
   unsigned* absmax;                            // per-utterance peak accumulator of conv_post_kernel: zeroed here

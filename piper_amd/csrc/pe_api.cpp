@@ -2,6 +2,7 @@
 #include "../../include/piper_hip.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -41,6 +42,24 @@ static void fill_result(pe_engine* e, pe_result* r, double secs) {
   r->pcm = e->eng->pcm_host();
   r->frames = e->eng->frames_host().data();
   r->infer_seconds = secs;
+}
+
+// Per-utterance scales of the *_scaled entry points: [batch][3], every value finite. Checked before the engine is
+// touched, so that a rejected call leaves the inputs of the previous one in place.
+static void check_scales(const float* scales, int64_t batch, int64_t max_batch) {
+  if (!scales) throw std::runtime_error("null scales");
+  if (batch < 1 || batch > max_batch) throw std::runtime_error("batch size must be in [1, " + std::to_string(max_batch) + "]");
+  static const char* const what[3] = {"noise_scale", "length_scale", "noise_w"};
+  for (int64_t u = 0; u < batch; ++u)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(scales[u * 3 + k]))
+        throw std::runtime_error("utterance " + std::to_string(u) + ": " + what[k] + " is not finite");
+}
+
+static void to_noise(const pe_noise* noise, pe::NoiseIn& n) {
+  if (!noise) return;
+  n.noise_w = noise->noise_w; n.w_stride = noise->w_stride;
+  n.noise_z = noise->noise_z; n.z_stride = noise->z_stride;
 }
 
 extern "C" {
@@ -149,6 +168,17 @@ int pe_upload(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t 
   });
 }
 
+int pe_upload_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                     const int64_t* sids, const pe_noise* noise) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true);
+  });
+}
+
 int pe_run(pe_engine* e) {
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
@@ -175,6 +205,22 @@ int pe_synthesize_batch(pe_engine* e, const int64_t* ids, const int64_t* offsets
     }
     const auto t0 = std::chrono::steady_clock::now();
     e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr);
+    e->eng->run();
+    e->eng->download(true, true);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fill_result(e, result, secs);
+  });
+}
+
+int pe_synthesize_batch_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                               const float* scales, const int64_t* sids, const pe_noise* noise, pe_result* result) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    const auto t0 = std::chrono::steady_clock::now();
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true);
     e->eng->run();
     e->eng->download(true, true);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -600,11 +646,15 @@ pe_engine* pe_group_engine(pe_group* g, int32_t i) {
   return (g && i >= 0 && i < (int32_t)g->eng.size()) ? g->eng[i] : nullptr;
 }
 
-int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
-                              const float scales[3], const int64_t* sids, pe_result* result) {
+}  // extern "C"
+
+// pe_group_synthesize_batch(_scaled): scales = one triple for the whole call, or (per_utt) [batch][3]
+static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                            bool per_utt, const int64_t* sids, pe_result* result) {
   return guard([&] {
-    if (!g || !ids || !offsets || !scales) throw std::runtime_error("null argument");
+    if (!g || !ids || !offsets || (!per_utt && !scales)) throw std::runtime_error("null argument");
     const int n = (int)g->eng.size();
+    if (per_utt) check_scales(scales, batch, (int64_t)4096 * n);
     // the offsets are the caller's: check them BEFORE they size a copy (the same rules and messages as Engine::upload,
     // which would only see them after the deal)
     if (batch < 1 || (int64_t)batch > (int64_t)4096 * n)
@@ -646,6 +696,7 @@ int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* of
     g->assign.assign(batch, 0);
     struct Work {
       std::vector<int64_t> ids, off, sids;
+      std::vector<float> scales;                // [shard][3] (per-utterance calls)
       pe_result res{};
       int rc = 0;
       std::string err;
@@ -659,6 +710,7 @@ int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* of
         w.ids.insert(w.ids.end(), ids + offsets[u], ids + offsets[u + 1]);
         w.off.push_back((int64_t)w.ids.size());
         if (sids) w.sids.push_back(sids[u]);
+        if (per_utt) w.scales.insert(w.scales.end(), scales + (size_t)u * 3, scales + (size_t)u * 3 + 3);
       }
     }
     // a shard = upload + device pipeline + int16 PCM to the host; the float waveform stays on the device (the group
@@ -668,7 +720,8 @@ int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* of
       if (shard[i].empty()) return;
       try {
         pe::Engine* e = g->eng[i]->eng;
-        e->upload(w.ids.data(), w.off.data(), (int)shard[i].size(), scales, sids ? w.sids.data() : nullptr, nullptr);
+        e->upload(w.ids.data(), w.off.data(), (int)shard[i].size(), per_utt ? w.scales.data() : scales,
+                  sids ? w.sids.data() : nullptr, nullptr, per_utt);
         e->run();
         e->download(false, true);
         fill_result(g->eng[i], &w.res, 0.0);
@@ -727,6 +780,18 @@ int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* of
   });
 }
 
+extern "C" {
+
+int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                              const float scales[3], const int64_t* sids, pe_result* result) {
+  return group_synthesize(g, ids, offsets, batch, scales, false, sids, result);
+}
+
+int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                     const float* scales, const int64_t* sids, pe_result* result) {
+  return group_synthesize(g, ids, offsets, batch, scales, true, sids, result);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // pe_coalescer_*: concurrent single-utterance requests of many caller threads as batched engine calls (include/piper_hip.h)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -745,6 +810,7 @@ struct pe_coalescer {
   };
   pe_engine* eng;
   int max_batch, max_wait_us;
+  bool mixed = false;         // merge requests whatever their scales (pe_coalescer_create_mixed)
   std::mutex m;
   std::condition_variable cv;
   std::deque<Req*> q;
@@ -755,7 +821,7 @@ struct pe_coalescer {
 
 extern "C" {
 
-int pe_coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out) {
+static int coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, bool mixed, pe_coalescer** out) {
   return guard([&] {
     if (!e || !out) throw std::runtime_error("null argument");
     if (max_batch < 1 || max_batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
@@ -763,8 +829,17 @@ int pe_coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe
     c->eng = e;
     c->max_batch = max_batch;
     c->max_wait_us = max_wait_us < 0 ? 0 : max_wait_us;
+    c->mixed = mixed;
     *out = c;
   });
+}
+
+int pe_coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out) {
+  return coalescer_create(e, max_batch, max_wait_us, false, out);
+}
+
+int pe_coalescer_create_mixed(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out) {
+  return coalescer_create(e, max_batch, max_wait_us, true, out);
 }
 
 void pe_coalescer_destroy(pe_coalescer* c) {
@@ -792,6 +867,7 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
     if (!c || !ids || !scales || !pcm || !n_samples) throw std::runtime_error("null argument");
     if (n_ids <= 0) throw std::runtime_error("empty phoneme id sequence");
     if (n_ids > 8192) throw std::runtime_error("phoneme id sequence longer than 8192");
+    if (c->mixed) check_scales(scales, 1, 1);       // (one bad request must not fail the batch it would join)
     pe_coalescer::Req me;
     me.ids = ids; me.n = n_ids; me.sid = sid;
     memcpy(me.scales, scales, sizeof(me.scales));
@@ -827,7 +903,7 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
     while (me.state < 2) {
       if (me.state == 0 && !c->busy) {
         // ---- leader: optionally give concurrent callers max_wait_us to arrive, then take what is queued (requests with
-        // the leader's scales, up to max_batch) and run it as ONE engine call
+        // the leader's scales -- any scales on a mixed coalescer --, up to max_batch) and run it as ONE engine call
         c->busy = true;
         leading = true;
         take.clear();
@@ -837,7 +913,7 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
         }
         for (auto it = c->q.begin(); it != c->q.end() && (int)take.size() < c->max_batch;) {
           pe_coalescer::Req* r = *it;
-          if (r == &me || !memcmp(r->scales, me.scales, sizeof(me.scales))) {
+          if (r == &me || c->mixed || !memcmp(r->scales, me.scales, sizeof(me.scales))) {
             r->state = 1;
             take.push_back(r);
             it = c->q.erase(it);
@@ -850,14 +926,16 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
         std::string err;
         try {
           std::vector<int64_t> cat, off{0}, sids;
+          std::vector<float> sc;
           for (auto* r : take) {
             cat.insert(cat.end(), r->ids, r->ids + r->n);
             off.push_back((int64_t)cat.size());
             sids.push_back(r->sid < 0 ? 0 : r->sid);
+            sc.insert(sc.end(), r->scales, r->scales + 3);
           }
           const auto t0 = std::chrono::steady_clock::now();
           pe::Engine* e = c->eng->eng;
-          e->upload(cat.data(), off.data(), (int)take.size(), me.scales, sids.data(), nullptr);
+          e->upload(cat.data(), off.data(), (int)take.size(), sc.data(), sids.data(), nullptr, true);   // one triple per request
           e->run();
           e->download(false, true);
           const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

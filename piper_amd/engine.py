@@ -29,6 +29,17 @@ class Synthesis:
         self.infer_seconds = infer_seconds
 
 
+def per_utterance_scales(scales, batch: int):
+    """None for one (noise_scale, length_scale, noise_w) triple (the call's scales); a C-contiguous float32 [batch][3] array
+    for one triple per utterance (the *_scaled entry points of include/piper_hip.h)."""
+    a = np.asarray(scales, dtype=np.float32)
+    if a.shape == (3,):
+        return None
+    if a.shape != (batch, 3):
+        raise ValueError(f"scales must be one triple or a ({batch}, 3) array, got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
 class Engine:
     def __init__(self, *, onnx_path: Optional[str] = None, blob: Optional[bytes] = None, device: int = 0,
                  lib: Optional[C.CDLL] = None, arena=None, skeleton: bool = False):
@@ -135,9 +146,13 @@ class Engine:
 
     # ---- API
     def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None) -> Synthesis:
+        """``scales``: one (noise_scale, length_scale, noise_w) triple for every utterance, or a (B, 3) array with one
+        triple per utterance (pe_synthesize_batch_scaled)."""
         ids, offs = self._pack(id_lists)
-        sc = (C.c_float * 3)(*[float(s) for s in scales])
-        keep: list = []
+        per = per_utterance_scales(scales, len(id_lists))
+        sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
+        entry = self._lib.pe_synthesize_batch if per is None else self._lib.pe_synthesize_batch_scaled
+        keep: list = [per]
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -145,7 +160,7 @@ class Engine:
             keep.append(sid_np)
             sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
         res = L.PeResult()
-        self._check(self._lib.pe_synthesize_batch(
+        self._check(entry(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)),
             len(id_lists), sc, sid_arr, nz, C.byref(res)))
         return self._collect(res)
@@ -156,9 +171,12 @@ class Engine:
         return self.synthesize_batch([ids], scales, None if sid is None else [sid], nw, nz)
 
     def upload(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None):
+        """``scales``: one triple, or a (B, 3) array of per-utterance triples (pe_upload_scaled)."""
         ids, offs = self._pack(id_lists)
-        sc = (C.c_float * 3)(*[float(s) for s in scales])
-        keep: list = []
+        per = per_utterance_scales(scales, len(id_lists))
+        sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
+        entry = self._lib.pe_upload if per is None else self._lib.pe_upload_scaled
+        keep: list = [per]
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -166,8 +184,8 @@ class Engine:
             keep.append(sid_np)
             sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
         self._keep = keep          # noise_z is read during run()
-        self._check(self._lib.pe_upload(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                        offs.ctypes.data_as(C.POINTER(C.c_int64)), len(id_lists), sc, sid_arr, nz))
+        self._check(entry(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                          offs.ctypes.data_as(C.POINTER(C.c_int64)), len(id_lists), sc, sid_arr, nz))
 
     def pack_host(self, id_lists, scales=(0.667, 1.0, 0.8)):
         """The host-side inputs of a call as the C ABI takes them -- int64 ids, prefix offsets, float scales in host

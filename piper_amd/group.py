@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
-from .engine import EngineError, Synthesis
+from .engine import EngineError, Synthesis, per_utterance_scales
 
 
 class EngineGroup:
@@ -50,16 +50,19 @@ class EngineGroup:
 
     def synthesize_batch(self, id_lists: Sequence[Sequence[int]], scales=(0.667, 1.0, 0.8),
                          sids: Optional[Sequence[int]] = None) -> Synthesis:
+        """``scales``: one triple for every utterance, or a (B, 3) array with one triple per utterance."""
         if len(id_lists) == 0:
             raise EngineError("empty batch")
+        per = per_utterance_scales(scales, len(id_lists))
         ids = np.concatenate([np.asarray(x, dtype=np.int64) for x in id_lists])
         off = np.zeros(len(id_lists) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(x) for x in id_lists])
-        sc = np.asarray(scales, dtype=np.float32)
+        sc = np.asarray(scales, dtype=np.float32) if per is None else per
+        entry = self._lib.pe_group_synthesize_batch if per is None else self._lib.pe_group_synthesize_batch_scaled
         sid = None if sids is None else np.ascontiguousarray(sids, dtype=np.int64)
         i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
         res = L.PeResult()
-        self._check(self._lib.pe_group_synthesize_batch(
+        self._check(entry(
             self._h, ids.ctypes.data_as(i64p), off.ctypes.data_as(i64p), len(id_lists), sc.ctypes.data_as(f32p),
             None if sid is None else sid.ctypes.data_as(i64p), C.byref(res)))
         B = res.batch
@@ -91,13 +94,16 @@ class Coalescer:
     """Dynamic batching of concurrent single-utterance requests on ONE engine (``pe_coalescer_*`` of include/piper_hip.h):
     ``synthesize`` is thread-safe and blocking; requests that are pending at the same moment run as one batched engine
     call. Every request gets what its own B=1 call computes (own noise draws, int16 peak-normalised over its own
-    waveform). The engine must stay alive and must not be used directly while requests are in flight."""
+    waveform). The engine must stay alive and must not be used directly while requests are in flight.
+    ``mix_scales``: requests are merged whatever their scales, one triple per request (pe_coalescer_create_mixed); by
+    default only requests with the same scales share a call."""
 
-    def __init__(self, engine, max_batch: int = 8, max_wait_us: int = 0):
+    def __init__(self, engine, max_batch: int = 8, max_wait_us: int = 0, mix_scales: bool = False):
         self._lib = engine._lib
         self._engine = engine                     # keeps the engine alive
         self._h = C.c_void_p()
-        if self._lib.pe_coalescer_create(engine._h, int(max_batch), int(max_wait_us), C.byref(self._h)):
+        create = self._lib.pe_coalescer_create_mixed if mix_scales else self._lib.pe_coalescer_create
+        if create(engine._h, int(max_batch), int(max_wait_us), C.byref(self._h)):
             raise EngineError(self._lib.pe_last_error().decode(errors="replace"))
 
     def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid: Optional[int] = None):

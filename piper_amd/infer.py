@@ -2,7 +2,9 @@
 ``python -m piper_train.infer_onnx`` (reference src/python/piper_train/infer_onnx.py:19-102): one JSON object
 per stdin line with ``phoneme_ids`` (and optionally ``speaker_id``), one ``<line index>.wav`` per utterance in
 ``--output-dir``, same scale options and defaults. The ONNX Runtime session is replaced by the HIP engine;
-``--batch N`` (new) groups N consecutive lines into one batched GPU call.
+``--batch N`` (new) groups N consecutive lines into one batched GPU call. A line may carry its own ``length_scale``,
+``noise_scale`` and / or ``noise_w`` (new): they override the command-line values for that utterance alone, and the group
+it belongs to still runs as one call (one scale triple per utterance).
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -35,6 +37,25 @@ def read_utterances(lines: Iterable[str]) -> List[Tuple[int, List[int], Optional
     return utts
 
 
+SCALE_KEYS = ("noise_scale", "length_scale", "noise_w")      # the order of an engine scale triple
+
+
+def read_scales(lines: Iterable[str], default: Tuple[float, float, float]) -> List[Optional[Tuple[float, float, float]]]:
+    """Per non-empty line (the order of read_utterances): its (noise_scale, length_scale, noise_w) with the line's own
+    keys over ``default``, or None when the line sets none of them."""
+    out: List[Optional[Tuple[float, float, float]]] = []
+    for line in lines:
+        line = line.strip()
+        if not line:
+            continue
+        obj = json.loads(line)
+        if not any(k in obj for k in SCALE_KEYS):
+            out.append(None)
+            continue
+        out.append(tuple(float(obj[k]) if k in obj else float(d) for k, d in zip(SCALE_KEYS, default)))
+    return out
+
+
 def write_wav(path: Path, sample_rate: int, pcm) -> None:
     with wave.open(str(path), "wb") as w:
         w.setnchannels(1)
@@ -64,13 +85,18 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     if args.seed is not None:
         engine.set_seed(args.seed)
     scales = (args.noise_scale, args.length_scale, args.noise_scale_w)
-    utts = read_utterances(stdin if stdin is not None else sys.stdin)
+    lines = list(stdin if stdin is not None else sys.stdin)
+    utts = read_utterances(lines)
+    line_scales = read_scales(lines, scales)
     step = max(1, args.batch)
     for k in range(0, len(utts), step):
         group = utts[k:k + step]
         sids = [u[2] for u in group]
+        own = line_scales[k:k + step]
+        # lines without scale keys: the command-line triple; any line with its own: one triple per utterance
+        call_scales = scales if all(s is None for s in own) else [scales if s is None else s for s in own]
         t0 = time.perf_counter()
-        res = engine.synthesize_batch([u[1] for u in group], scales,
+        res = engine.synthesize_batch([u[1] for u in group], call_scales,
                                       sids=None if all(s is None for s in sids) else [s or 0 for s in sids])
         infer_sec = time.perf_counter() - t0
         audio_sec = sum(p.shape[-1] for p in res.pcm) / args.sample_rate

@@ -145,9 +145,22 @@ class PiperVoice:
                                     length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                                     noise_w: Optional[float] = None) -> List[bytes]:
         """Batched extension: several utterances in one GPU call, each identical to its own
-        synthesize_ids_to_raw() (same noise stream aside)."""
+        synthesize_ids_to_raw() (same noise stream aside). ``length_scale`` / ``noise_scale`` / ``noise_w`` may each be
+        one value for every utterance or a list with one value per utterance (None entries: the voice's default)."""
         sids = None
+        n = len(phoneme_id_lists)
         if self.config.num_speakers > 1:
-            sids = [0 if s is None else s for s in (speaker_ids or [None] * len(phoneme_id_lists))]
-        r = self.session.synthesize_batch(phoneme_id_lists, self._scales(length_scale, noise_scale, noise_w), sids=sids)
+            sids = [0 if s is None else s for s in (speaker_ids or [None] * n)]
+        knobs = (length_scale, noise_scale, noise_w)
+        if any(isinstance(v, (list, tuple)) for v in knobs):
+            def at(v, i):
+                if not isinstance(v, (list, tuple)):
+                    return v
+                if len(v) != n:
+                    raise ValueError(f"{len(v)} per-utterance scale values for {n} utterances")
+                return v[i]
+            scales = [self._scales(*(at(v, i) for v in knobs)) for i in range(n)]
+        else:
+            scales = self._scales(length_scale, noise_scale, noise_w)
+        r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
         return [p.tobytes() for p in r.pcm]
