@@ -440,6 +440,57 @@ def infer_one(w, cfg, ids, scales, noise_w=None, noise_z=None, sid: Optional[int
     return res
 
 
+@torch.no_grad()
+def decode(w, cfg, z_p, sid: Optional[int] = None, dtype=torch.float64) -> np.ndarray:
+    """flow_reverse + generator of ``infer_one`` on a GIVEN prior sample z_p [inter, F] (every frame inside the mask, as
+    for one utterance of F frames): the arithmetic that the split matrix modes change, and nothing in front of it. A
+    test feeds it the engine's own z_p, so the durations' ceil can never make the two runs incomparable. Weights are
+    converted to `dtype` (f32 -> f64 exactly); returns the float audio [F * hop] in that precision."""
+    if not isinstance(next(iter(w.values())), torch.Tensor) or next(iter(w.values())).dtype != dtype:
+        w = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in w.items()}
+    zt = torch.as_tensor(np.asarray(z_p)).to(dtype)[None]
+    g = None
+    if cfg.n_speakers > 1:
+        g = F.embedding(torch.tensor([int(sid or 0)]), w["emb_g.weight"]).unsqueeze(-1)
+    y_mask = torch.ones(1, 1, zt.shape[2], dtype=dtype)
+    z = flow_reverse(w, cfg, zt, y_mask, g=g)
+    return generator(w, cfg, z * y_mask, g=g)[0, 0].numpy()
+
+
+_WEIGHT_DIGESTS: Dict[int, tuple] = {}
+
+
+def content_key(w, *parts) -> str:
+    """sha256 of a weight dict and of the arrays / scalars / None in `parts`: a cache key that two different inputs
+    cannot share (a free-form name can). The digest of a weight dict is kept per dict object (which it holds on to, so
+    its id is not reused)."""
+    import hashlib
+    ent = _WEIGHT_DIGESTS.get(id(w))
+    if ent is None or ent[0] is not w:
+        h = hashlib.sha256()
+        for k in sorted(w):
+            a = w[k].numpy() if isinstance(w[k], torch.Tensor) else np.asarray(w[k])
+            h.update(k.encode() + str(a.dtype).encode() + str(a.shape).encode())
+            h.update(np.ascontiguousarray(a).tobytes())
+        ent = (w, h.hexdigest())
+        _WEIGHT_DIGESTS[id(w)] = ent
+    h = hashlib.sha256(ent[1].encode())
+
+    def feed(p):
+        if p is None:
+            h.update(b"<none>")
+        elif isinstance(p, (list, tuple)) and not all(np.isscalar(x) for x in p):
+            h.update(b"<seq %d>" % len(p))
+            for x in p:
+                feed(x)
+        else:
+            a = np.ascontiguousarray(p.numpy() if isinstance(p, torch.Tensor) else np.asarray(p))
+            h.update(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes())
+    for p in parts:
+        feed(p)
+    return h.hexdigest()
+
+
 def audio_float_to_int16(audio: np.ndarray) -> np.ndarray:
     """piper.cpp:410-431 == util.py:5-12: peak-normalise with floor 0.01, clamp, truncating cast."""
     audio = np.asarray(audio, dtype=np.float32)

@@ -13,10 +13,14 @@ namespace pe {
 //   SM 0 "bf16x3": v = h + l, h = bf16(v), l = bf16(v - h); products hh + hl + lh (ll, 2^-16 relative, dropped):
 //                  16 significand bits per operand, 3 x v_mfma_f32_32x32x16_bf16.
 //   SM 1 "f16x3":  v = h + l, h = f16(v), l = f16(v - h); the same three products on v_mfma_f32_32x32x16_f16:
-//                  22 significand bits per operand (the f32 significand has 24). f16's narrow exponent is handled by
-//                  scaling: weights are packed times a power of two per conv (largest magnitude near 2^13, undone
-//                  exactly on the accumulators), activations clamp at +-65504 (never reached by a voice; a term
-//                  below f16's subnormal step 2^-24 is dropped, an ABSOLUTE error of 6e-8 per element).
+//                  22 significand bits per operand (the f32 significand has 24). f16's narrow exponent is handled for
+//                  the weights only: they are packed times a power of two per conv (largest magnitude near 2^13, undone
+//                  exactly on the accumulators). Activations are not scaled. Above 65504 the high term saturates and the
+//                  low term carries the rest up to |v| = 131008, where the split saturates (the clamp in front of it;
+//                  never reached by a voice, tests/test_matrix_truth_emu.py forces it). Below f16's normal range (2^-14)
+//                  the terms are subnormal and keep fewer bits: an ABSOLUTE error of up to 2^-25 (3e-8) per element for
+//                  the low term, so small activation channels or small weight columns (relative to the conv's largest
+//                  weight) lose relative accuracy -- profiles/matrix_truth.md measures it on a rescaled voice.
 //   SM 2 "bf16x6": v = h + m + l (three bf16 terms = the whole 24-bit significand, operands exact); products
 //                  hh + hm + mh + hl + lh + mm (the dropped ml, lm, ll are 2^-24 relative: f32 rounding level),
 //                  6 x v_mfma_f32_32x32x16_bf16.
@@ -72,8 +76,21 @@ __device__ __forceinline__ float pe_lrelu2(float v, float slope) {
 #endif
 
 // f32 pair -> f16 pair, round toward zero (v_cvt_pkrtz_f16_f32: ONE instruction per two elements; a magnitude beyond
-// f16's range lands on +-65504, the largest finite value, so no clamp is needed in front of it)
+// f16's range lands on +-65504, the largest finite value)
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// Clamp in front of the f16 split: the high term saturates at +-65504 by itself, but the low term f16(v - hi) of a
+// |v| >= 131024 would round to inf. Clamped to +-2 * 65504, hi + lo saturates monotonically at +-131008 and both terms
+// stay finite for every finite v (one v_med3_f32 per element; inline asm: the builtin adds a canonicalising max in front).
+static constexpr float F16_SPLIT_MAX = 2.f * F16_MAX;
+#ifdef PE_EMU
+inline float pe_clamp_f16_split(float v) { return std::fmin(std::fmax(v, -F16_SPLIT_MAX), F16_SPLIT_MAX); }
+#else
+__device__ __forceinline__ float pe_clamp_f16_split(float v) {
+  float r;
+  asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(-F16_SPLIT_MAX), "v"(F16_SPLIT_MAX));
+  return r;
+}
+#endif
 #ifdef PE_EMU
 inline _Float16 pe_f2h_rtz(float v) {
   _Float16 h = (_Float16)v;                               // round to nearest even, then step back towards zero where that rounded away
@@ -93,16 +110,18 @@ __device__ __forceinline__ f16x2 pe_cvt_pkrtz(float a, float b) { return __built
 template <int SM>
 __device__ __forceinline__ void split8(const float (&v)[8], frag16 (&t)[split_terms(SM)]) {
   if constexpr (SM == 1) {
-    // hi = v rounded TOWARD ZERO to f16 (packed conversion, saturating: no clamp), lo = f16(v - hi): hi + lo carries 21-22
-    // significand bits either way, and the staging costs 2.5 VALU instructions per element instead of 6
+    // hi = v rounded TOWARD ZERO to f16 (packed conversion, saturating), lo = f16(v - hi): hi + lo carries 21-22
+    // significand bits either way, and the staging costs 2.5 VALU instructions per element instead of 6 (plus the clamp
+    // at 2 * 65504 in front, pe_clamp_f16_split, which keeps both terms finite for any finite v)
     f16x8 hi, lo;
 #pragma unroll
     for (int i = 0; i < 8; i += 2) {
-      const f16x2 h = pe_cvt_pkrtz(v[i], v[i + 1]);
+      const float a = pe_clamp_f16_split(v[i]), b = pe_clamp_f16_split(v[i + 1]);
+      const f16x2 h = pe_cvt_pkrtz(a, b);
       hi[i] = h[0];
       hi[i + 1] = h[1];
-      lo[i] = (_Float16)(v[i] - (float)h[0]);
-      lo[i + 1] = (_Float16)(v[i + 1] - (float)h[1]);
+      lo[i] = (_Float16)(a - (float)h[0]);
+      lo[i + 1] = (_Float16)(b - (float)h[1]);
     }
     t[0] = __builtin_bit_cast(frag16, hi);
     t[1] = __builtin_bit_cast(frag16, lo);

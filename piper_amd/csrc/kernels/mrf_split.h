@@ -48,12 +48,13 @@ __device__ __forceinline__ void split4(const float (&v)[4], frag8& hi, frag8& lo
   if constexpr (SM == 1) {
     f16x4 h, l;
 #pragma unroll
-    for (int i = 0; i < 4; i += 2) {          // hi rounded toward zero (packed, saturating), lo = f16(v - hi): conv_bf3.h split8
-      const f16x2 t = pe_cvt_pkrtz(v[i], v[i + 1]);
+    for (int i = 0; i < 4; i += 2) {          // clamp, hi rounded toward zero (packed, saturating), lo = f16(v - hi): conv_bf3.h split8
+      const float a = pe_clamp_f16_split(v[i]), b = pe_clamp_f16_split(v[i + 1]);
+      const f16x2 t = pe_cvt_pkrtz(a, b);
       h[i] = t[0];
       h[i + 1] = t[1];
-      l[i] = (_Float16)(v[i] - (float)t[0]);
-      l[i + 1] = (_Float16)(v[i + 1] - (float)t[1]);
+      l[i] = (_Float16)(a - (float)t[0]);
+      l[i + 1] = (_Float16)(b - (float)t[1]);
     }
     hi = __builtin_bit_cast(frag8, h);
     lo = __builtin_bit_cast(frag8, l);

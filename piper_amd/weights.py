@@ -335,6 +335,97 @@ def synthetic_weights(cfg: ArchConfig, seed: int = 1234, family: str = "gauss") 
     return w
 
 
+def rescale_channels(cfg: ArchConfig, w: Dict[str, np.ndarray], seed: int, log2_span: int = 10,
+                     overflow_log2=None) -> Dict[str, np.ndarray]:
+    """The same voice with the channels of the coupling flow's WN and of the generator multiplied by powers of two, each
+    gain undone exactly by the layers that read the channel (tests only). In exact arithmetic the voice computes the
+    same function: leaky ReLU is positively homogeneous and the rest is linear. A power of two also commutes with f32 and
+    bf16 rounding, so every f32 / bf16 kernel gives the same bits on both voices; only f16's narrow exponent range can
+    tell them apart. Rescaled:
+
+      * coupling-flow WN (flow.flows.*; the duration predictor's flows are not touched): the residual stream (rows of
+        ``pre`` and the "res" rows of every ``res_skip_layers``, undone on the columns of every ``in_layers``) and the
+        skip channels (the "skip" rows of every ``res_skip_layers``, undone on the columns of ``post``);
+      * generator: the stream of every upsampling stage (rows of ``ups[i]`` and of every resblock conv that writes the
+        stream -- ``convs2`` of ResBlock1, ``convs`` of ResBlock2 --, undone on the columns of every conv that reads it and
+        of ``ups[i+1]`` / ``conv_post``), the hidden channels between ``convs1`` and ``convs2`` of ResBlock1, and the
+        rows of ``conv_pre`` with the speaker ``cond`` rows (undone on the columns of ``ups[0]``).
+
+    Gains are 2^e, e uniform over the integers of [-log2_span/2, log2_span/2]; biases scale with their rows.
+    ``overflow_log2`` additionally multiplies the output of ``conv_pre`` and the stream of stage 0 by 2^overflow_log2:
+    activations far beyond f16's range at the inputs of ``ups[0]`` and of the first MRF stage."""
+    rng = np.random.default_rng(seed)
+    half = int(log2_span) // 2
+    out = {k: np.asarray(v, np.float64).copy() for k, v in w.items()}
+
+    def gains(n, extra=0):
+        return np.exp2(rng.integers(-half, half + 1, size=n) + extra)
+
+    def rows(name, g, axis=0, lo=0):
+        wt = out[name + ".weight"]
+        sh = [1] * wt.ndim
+        sh[axis] = len(g)
+        sl = [slice(None)] * wt.ndim
+        sl[axis] = slice(lo, lo + len(g))
+        wt[tuple(sl)] *= g.reshape(sh)
+        if name + ".bias" in out:
+            out[name + ".bias"][lo:lo + len(g)] *= g
+
+    def cols(name, g, axis=1):
+        wt = out[name + ".weight"]
+        sh = [1] * wt.ndim
+        sh[axis] = len(g)
+        wt *= (1.0 / g).reshape(sh)
+
+    H, nl = cfg.hidden, cfg.wn_layers
+    for f in range(cfg.flow_n):
+        p = f"flow.flows.{2 * f}"
+        s, t = gains(H), gains(H)                    # residual stream, skip channels
+        rows(p + ".pre", s)
+        for i in range(nl):
+            cols(f"{p}.enc.in_layers.{i}", s)
+            if i < nl - 1:
+                rows(f"{p}.enc.res_skip_layers.{i}", s, lo=0)
+                rows(f"{p}.enc.res_skip_layers.{i}", t, lo=H)
+            else:
+                rows(f"{p}.enc.res_skip_layers.{i}", t, lo=0)
+        cols(p + ".post", t)
+
+    ov = int(overflow_log2 or 0)
+    u = gains(cfg.up_initial, ov)
+    rows("dec.conv_pre", u)
+    if cfg.gin:
+        rows("dec.cond", u)
+    prev = u
+    nk = len(cfg.rb_kernel_sizes)
+    for i in range(len(cfg.up_rates)):
+        ch = cfg.up_initial // (2 ** (i + 1))
+        s = gains(ch, ov if i == 0 else 0)
+        cols(f"dec.ups.{i}", prev, axis=0)           # ConvTranspose1d [Cin, Cout, k]
+        rows(f"dec.ups.{i}", s, axis=1)
+        for j in range(nk):
+            rb = f"dec.resblocks.{i * nk + j}"
+            for d in range(len(cfg.rb_dilations[j])):
+                if cfg.resblock == 1:
+                    hd = gains(ch)
+                    cols(f"{rb}.convs1.{d}", s)
+                    rows(f"{rb}.convs1.{d}", hd)
+                    cols(f"{rb}.convs2.{d}", hd)
+                    rows(f"{rb}.convs2.{d}", s)
+                else:
+                    cols(f"{rb}.convs.{d}", s)
+                    rows(f"{rb}.convs.{d}", s)
+        prev = s
+    cols("dec.conv_post", prev)
+    res = {}
+    for k, v in out.items():
+        a = v.astype(np.float32)
+        if not np.array_equal(a.astype(np.float64), v):
+            raise ValueError(f"{k}: a rescaled value is not exact in f32")
+        res[k] = np.ascontiguousarray(a)
+    return res
+
+
 def _stride_of(cfg: ArchConfig, name: str) -> int:
     i = int(name.split(".")[2])
     return cfg.up_rates[i]

@@ -67,13 +67,15 @@ def pcm_rms(a, b):
     return float(np.sqrt(np.mean(d * d))) if d.size else 0.0
 
 
-_ORACLE = {}          # (cache_key, utterance) -> oracle result: the split-mode tests compare the SAME inputs as the f32 ones
+_ORACLE = {}          # oracle.content_key(weights, ids, noise, scales, sid) -> oracle result: the split-mode tests compare the
+                      # SAME inputs as the f32 ones, and two different inputs can never share an entry
 
 
 def run_and_check(eng, cfg, w, ids, nw, nz, sample, scales=SCALES, sids=None, audio_tol=TIGHT_AUDIO_TOL, stats=None,
                   cache_key=None):
     """One profiled batched call; utterances `sample` are compared with the oracle, all of them with the
-    size-independent properties (sample count = frames * hop = sum of durations * hop, peak-normalised PCM)."""
+    size-independent properties (sample count = frames * hop = sum of durations * hop, peak-normalised PCM). A truthy
+    `cache_key` (a label for the reader) keeps the oracle's results, keyed on the content of the inputs."""
     from oracle import vits_oracle as O
     eng.profile_enable(2)
     eng.profile_reset()
@@ -98,11 +100,13 @@ def run_and_check(eng, cfg, w, ids, nw, nz, sample, scales=SCALES, sids=None, au
         assert np.max(np.abs(r.pcm[i].astype(np.int32))) >= 32766 or np.max(np.abs(r.audio[i])) < 0.01
     worst = 0.0
     for i in sample:
-        o = _ORACLE.get((cache_key, i)) if cache_key else None
+        sid = None if sids is None else sids[i]
+        key = O.content_key(w, ids[i], nw[i], nz[i], scales, sid) if cache_key else None
+        o = _ORACLE.get(key) if cache_key else None
         if o is None:
-            o = O.synthesize(wt, cfg, ids[i], scales, nw[i], nz[i], sid=None if sids is None else sids[i])
+            o = O.synthesize(wt, cfg, ids[i], scales, nw[i], nz[i], sid=sid)
             if cache_key:
-                _ORACLE[(cache_key, i)] = {k: o[k] for k in ("durations", "audio", "pcm")}
+                _ORACLE[key] = {k: o[k] for k in ("durations", "audio", "pcm")}
         assert np.array_equal(durs[off[i]:off[i + 1]], o["durations"]), f"utterance {i}: durations differ"
         assert r.audio[i].shape == o["audio"].shape
         d = float(np.max(np.abs(r.audio[i] - o["audio"])))
@@ -201,7 +205,10 @@ def test_split_matrix_modes_streaming_chunks_equal_unchunked(monkeypatch, preset
 def test_split_matrix_modes_on_heavy_tailed_weights(monkeypatch, preset, lens, mode):
     """The split modes on the heavy-tailed weight family (Student-t weights of 10+ standard deviations, per-channel gains a
     factor ~4 apart, 4x biases: the dynamic range of trained, weight-normed layers rather than of i.i.d. Gaussians) -- what
-    f16x3's power-of-two weight scaling and its +-65504 activation clamp exist for: same gate as the f32 path."""
+    f16x3's power-of-two weight scaling exists for: same gate as the f32 path. (f16x3 does not scale activations: above
+    65504 its high term saturates and the split saturates at +-131008; below f16's normal range 2^-14 its terms are
+    subnormal and keep fewer bits. Neither happens on this family; tests/test_matrix_truth_emu.py and
+    tests/test_gpu_matrix_truth.py force both with rescaled voices.)"""
     cfg = W.preset(preset)
     w = W.synthetic_weights(cfg, 4321, family="heavy")
     eng = make_engine(monkeypatch, cfg, w, {"PIPER_HIP_MATRIX": mode})
