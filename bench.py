@@ -6,26 +6,33 @@ A "step" is one pass of the hot path over one batch of synthetic input, timed ov
 from host memory, `pe_run` (the whole device pipeline; the ENGINE draws both noise sites -- the graph's two
 RandomNormalLike nodes, vits/models.py:111,718 -- fresh every step) and `pe_fetch` of the int16 PCM into host memory.
 The same step with the ids left resident in HBM (upload once, then `pe_run` + `pe_fetch`) is reported beside it as
-`device_resident_ms`.
+`device_resident_ms` by a `--full` run.
 
-ONE invocation covers every BASELINE.json configuration (the driver only ever runs `python bench.py --gpus N`):
+A plain run does what the headline figure needs and nothing else: it loads the voice, runs the warm-up and the timed
+steps, writes `--dump-outputs` and prints the result line. `--full` adds everything else the benchmark measures, AFTER the
+timed steps (N=1: the headline is the same measurement either way; N>1: rank 0's `single_gpu_reference` runs before
+them), and covers every BASELINE.json configuration in ONE invocation:
 
     python bench.py                  # N=1. Headline line = configs[1]: en_US-lessac-medium architecture, ONE utterance
-                                     # of 128 ids (what one piper::synthesize() call does). `extra_configs` carries
-                                     # time-boxed legs for configs[2] (high, 64 x 128), configs[3]'s per-GPU share
-                                     # (medium, 64 x 128), configs[4] (streaming p50 first chunk) and a B=1 leg with
-                                     # changing text + noise every call (speculation misses), each with its own roofline
+                                     # of 128 ids (what one piper::synthesize() call does)
+    python bench.py --full           # the same headline, then `device_resident_ms`, `sustained`, `api_inclusive`, the
+                                     # per-kernel `roofline`, `cpu_baseline`, and `extra_configs`: time-boxed legs for
+                                     # configs[2] (high, 64 x 128), configs[3]'s per-GPU share (medium, 64 x 128),
+                                     # configs[4] (streaming p50 first chunk), a B=1 leg with changing text + noise
+                                     # every call (speculation misses) and the split-operand matrix modes, each with
+                                     # its own roofline (--no-roofline / --no-cpu-baseline / --no-extra drop parts)
     python bench.py --gpus N         # N>1: launches N ranks itself (torch.distributed.run). Headline = the SAME per-GPU
                                      # workload as N=1 (configs[1]: one utterance per GPU per step, RCCL broadcast of the
-                                     # packed voice at load), so the per-N values are one weak-scaling curve;
+                                     # packed voice at load), so the per-N values are one weak-scaling curve. With
+                                     # --full: `single_gpu_reference` (rank 0 alone on the same workload) and
                                      # `batched_per_gpu` = configs[3] (medium, 64 utterances per GPU, 512 over 8) with
                                      # rank 0's single-GPU rate on that share and the speed-up over it
     python bench.py --config 3       # any single configuration as the headline (2..5, 1-based like SURVEY.md 8d)
 
-The rate of the one-call form `pe_synthesize_batch` (the same span plus the float waveform copied to the host as well) is
-reported beside the headline as `api_inclusive`. Rank 0 prints ONE compact JSON
-line (< 4 KB: headline, roofline, cpu_baseline, one short entry per leg) as the last line of stdout and writes the full
-per-kernel tables of every leg to bench_full.json.
+With --full the rate of the one-call form `pe_synthesize_batch` (the same span plus the float waveform copied to the host
+as well) is reported beside the headline as `api_inclusive`. Rank 0 prints ONE compact JSON line (< 4 KB: headline and,
+with --full, roofline, cpu_baseline, one short entry per leg) as the last line of stdout and writes the full result
+object (with --full: the per-kernel tables of every leg) to bench_full.json.
 """
 import argparse
 import json
@@ -288,9 +295,14 @@ def parse_args():
     ap.add_argument("--preset", default=None)
     ap.add_argument("--ids", type=int, default=None, help="phoneme ids per utterance")
     ap.add_argument("--batch", type=int, default=None, help="utterances per step (per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel event passes (profiling runs)")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: skip the extra_configs legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: device-resident and sustained steps, the "
+                         "one-call API rate, the per-kernel roofline, the CPU baseline, the extra_configs legs and (N>1) the "
+                         "single-GPU reference and the batched share. Off by default: a plain run stops at the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the per-kernel event passes (profiling runs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs")
     ap.add_argument("--matrix", default="f32", choices=["f32"] + sorted(SPLIT_MODES),
                     help="matrix mode of the engine (PIPER_HIP_MATRIX): f32 = the reference's arithmetic (default, the "
                          "headline); bf16x3 / f16x3 / bf16x6 = opt-in split-operand conv GEMMs for flow + generator")
@@ -298,7 +310,7 @@ def parse_args():
                     help="BASELINE configs[4]: p50 time to the first chunk of a chunked (45-frame) decode, then exit")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="after the K timed steps keep stepping (reported separately as `sustained`) until the GPU "
+                    help="with --full: after the K timed steps keep stepping (reported separately as `sustained`) until the GPU "
                          "has been busy this long, so that external samplers see the run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the timed path handed its caller in its last step to "
@@ -620,22 +632,96 @@ def main():
         finish(ctx)
         return
 
-    # ---- N>1: rank 0's rate on the SAME workload with the other GPUs idle, so that the scaling of `value` can be read
-    # against a single-GPU number from the same invocation (the driver's N=1 run has the B=1 headline)
+    # ---- N>1, --full: rank 0's rate on the SAME workload with the other GPUs idle, so that the scaling of `value` can be
+    # read against a single-GPU number from the same invocation (the driver's N=1 run has the B=1 headline)
     single_ref = None
-    if ctx.world > 1:
+    if args.full and ctx.world > 1:
         if ctx.rank == 0:
             r1 = timed_leg(ctx, eng, cfg, preset, B, T, max(3, min(args.steps, 10)), 2, sync_ranks=False)
             single_ref = {"value": r1["value"], "ms_per_step": r1["ms_per_step"], "steps": r1["steps"],
                           "what": "rank 0 alone (other ranks waiting at a barrier), same workload, same build"}
         ctx.barrier()
 
-    leg = timed_leg(ctx, eng, cfg, preset, B, T, args.steps, args.warmup, resident_steps=max(10, args.steps),
-                    keep_last=bool(args.dump_outputs))
+    leg = timed_leg(ctx, eng, cfg, preset, B, T, args.steps, args.warmup,
+                    resident_steps=max(10, args.steps) if args.full else 0, keep_last=bool(args.dump_outputs))
     dbg(f"timed leg done: {leg['ms_per_step']:.3f} ms/step")
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, leg["last"], ctx.rank, ctx.world)
     frames, id_lists, noise_w = leg["frames"], leg["id_lists"], leg["noise_w"]
+
+    # ---- a plain run has measured all it reports; --full goes on to the rest
+    sustained, api, dev_ms, roof, batched_line = \
+        beside_headline(ctx, eng, cfg, args, leg, preset, cfgno, B, T) if args.full else (None,) * 5
+
+    out = None
+    if ctx.rank == 0:
+        value = leg["value"]
+        out = {
+            "metric": "audio samples/sec",
+            "value": value,
+            "unit": "samples/s",
+            "x_realtime": value / cfg.sample_rate,
+            "n_gpus": ctx.world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": leg["ms_per_step"],
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32" if args.matrix == "f32" else DTYPE_SPLIT[args.matrix],
+            "data": "synthetic (seeded random-weight voice of the named architecture, synthetic phoneme ids)",
+            "config": {"workload": workload_text(cfgno, preset, cfg, B, T),
+                       "frames_per_step": int(frames.sum()), "samples_per_step": leg["samples_per_step"],
+                       "frames_per_id": float(leg["avg_frames_per_step"]) / float(B * T),
+                       "kernel_launches_per_step": leg["launches"],
+                       "parallelism": f"utterance-parallel x{ctx.world}, one process per GPU, RCCL weight broadcast"},
+            "ranks": ranks_info,
+            "api_inclusive": api,
+            "device_resident_ms": leg["device_resident_ms"],
+            "device_pipeline_only_ms_per_step": dev_ms,
+            "sustained": sustained,
+            "per_rank_samples_per_s": leg["per_rank"],
+            "weight_broadcast_s": t_bcast,
+            "weight_broadcast_bytes": bcast_bytes,
+            "speculation": dict(zip(("runs", "misses"), eng.speculation_stats)),
+            "xcd_dispatch": dict(zip(("xcc_of_workgroups_0_63", "round_robin_period"), eng.xcc_pattern)),
+        }
+        if single_ref is not None:
+            out["single_gpu_reference"] = single_ref
+        if batched_line is not None:
+            out["batched_per_gpu"] = batched_line
+        if ctx.world > 1 and cfgno == 2:
+            out["headline_note"] = ("N>1 `value` = configs[1] per GPU (1 utterance x 128 ids per rank per step: one weak-scaling "
+                                    "curve with the N=1 line; rounds 1-3 used configs[3] here). The batched 1->N scaling "
+                                    "north_star asks for is `batched_per_gpu` (64 utterances per GPU, --full): value / single_gpu_value")
+        if roof is not None:
+            out["roofline"] = roof
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg, wts, id_lists[0], SCALES, noise_w[0], args.cpu_seconds, preset)
+
+    # ---- --full: the other BASELINE configurations, time-boxed, in the same invocation (single GPU, default headline only)
+    if args.full and ctx.rank == 0 and ctx.world == 1 and cfgno == 2 and args.config is None and not args.no_extra and \
+            not (args.preset or args.batch or args.ids):
+        out["extra_configs"] = extra_configs(ctx, eng, cfg, args)
+    if ctx.rank == 0:
+        dbg("printing the result line")
+        emit(out)
+    finish(ctx)
+    dbg("done")
+
+
+def finish(ctx):
+    if ctx.dist is not None:
+        ctx.dist.barrier()
+        ctx.dist.destroy_process_group()
+
+
+def beside_headline(ctx, eng, cfg, args, leg, preset, cfgno, B, T):
+    """--full: what is measured on the headline's workload after its timed steps -- more of the same step (`sustained`),
+    the one-call API, the device pipeline alone, the per-kernel roofline -- and, N>1, configs[3]'s per-GPU share. Every
+    rank calls it (the batched share is a collective)."""
+    import torch
+    id_lists, noise_w = leg["id_lists"], leg["noise_w"]
 
     # ---- sustained: keep the GPU busy for >= --min-seconds in total (same step), reported separately
     sustained = None
@@ -686,68 +772,7 @@ def main():
             batched_line["single_gpu_value"] = alone["value"]
             batched_line["single_gpu_ms_per_step"] = alone["ms_per_step"]
             batched_line["speedup_over_single_gpu"] = l4["value"] / alone["value"]
-
-    out = None
-    if ctx.rank == 0:
-        value = leg["value"]
-        out = {
-            "metric": "audio samples/sec",
-            "value": value,
-            "unit": "samples/s",
-            "x_realtime": value / cfg.sample_rate,
-            "n_gpus": ctx.world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": leg["ms_per_step"],
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if args.matrix == "f32" else DTYPE_SPLIT[args.matrix],
-            "data": "synthetic (seeded random-weight voice of the named architecture, synthetic phoneme ids)",
-            "config": {"workload": workload_text(cfgno, preset, cfg, B, T),
-                       "frames_per_step": int(frames.sum()), "samples_per_step": leg["samples_per_step"],
-                       "frames_per_id": float(leg["avg_frames_per_step"]) / float(B * T),
-                       "kernel_launches_per_step": leg["launches"],
-                       "parallelism": f"utterance-parallel x{ctx.world}, one process per GPU, RCCL weight broadcast"},
-            "ranks": ranks_info,
-            "api_inclusive": api,
-            "device_resident_ms": leg["device_resident_ms"],
-            "device_pipeline_only_ms_per_step": dev_ms,
-            "sustained": sustained,
-            "per_rank_samples_per_s": leg["per_rank"],
-            "weight_broadcast_s": t_bcast,
-            "weight_broadcast_bytes": bcast_bytes,
-            "speculation": dict(zip(("runs", "misses"), eng.speculation_stats)),
-            "xcd_dispatch": dict(zip(("xcc_of_workgroups_0_63", "round_robin_period"), eng.xcc_pattern)),
-        }
-        if single_ref is not None:
-            out["single_gpu_reference"] = single_ref
-        if batched_line is not None:
-            out["batched_per_gpu"] = batched_line
-        if ctx.world > 1 and cfgno == 2:
-            out["headline_note"] = ("N>1 `value` = configs[1] per GPU (1 utterance x 128 ids per rank per step: one weak-scaling "
-                                    "curve with the N=1 line; rounds 1-3 used configs[3] here). The batched 1->N scaling "
-                                    "north_star asks for is `batched_per_gpu` (64 utterances per GPU): value / single_gpu_value")
-        if roof is not None:
-            out["roofline"] = roof
-        if ctx.world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, wts, id_lists[0], SCALES, noise_w[0], args.cpu_seconds, preset)
-
-    # ---- the other BASELINE configurations, time-boxed, in the same invocation (single GPU, default headline only)
-    if ctx.rank == 0 and ctx.world == 1 and cfgno == 2 and args.config is None and not args.no_extra and \
-            not (args.preset or args.batch or args.ids):
-        out["extra_configs"] = extra_configs(ctx, eng, cfg, args)
-    if ctx.rank == 0:
-        dbg("printing the result line")
-        emit(out)
-    finish(ctx)
-    dbg("done")
-
-
-def finish(ctx):
-    if ctx.dist is not None:
-        ctx.dist.barrier()
-        ctx.dist.destroy_process_group()
+    return sustained, api, dev_ms, roof, batched_line
 
 
 def extra_configs(ctx, eng_medium, cfg_medium, args):

@@ -7,16 +7,16 @@ export TMPDIR=/tmp
 O=gpurun_out/r04
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout 900 python bench.py > $O/bench_default.stdout 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.stdout 2> $O/bench_default.err
 cp bench_full.json $O/bench_default_full.json
 BA="--no-extra --no-cpu-baseline --no-roofline"
 W_b1="--steps 50"
 W_b64="--config 4 --steps 4 --warmup 2 --min-seconds 0"
 W_high="--config 3 --steps 2 --warmup 1 --min-seconds 0"
 # per-workload full result objects (algorithmic flops / bytes per kernel from the engine's level-2 profile rows)
-PIPER_BENCH_FULL=$O/full_b1.json timeout 300 python bench.py --no-extra --no-cpu-baseline --steps 100 > /dev/null 2>> $O/err.log
-PIPER_BENCH_FULL=$O/full_b64.json timeout 300 python bench.py --no-extra --no-cpu-baseline --config 4 --steps 5 --warmup 2 > /dev/null 2>> $O/err.log
-PIPER_BENCH_FULL=$O/full_high_b64.json timeout 300 python bench.py --no-extra --no-cpu-baseline --config 3 --steps 3 --warmup 1 > /dev/null 2>> $O/err.log
+PIPER_BENCH_FULL=$O/full_b1.json timeout 300 python bench.py --full --no-extra --no-cpu-baseline --steps 100 > /dev/null 2>> $O/err.log
+PIPER_BENCH_FULL=$O/full_b64.json timeout 300 python bench.py --full --no-extra --no-cpu-baseline --config 4 --steps 5 --warmup 2 > /dev/null 2>> $O/err.log
+PIPER_BENCH_FULL=$O/full_high_b64.json timeout 300 python bench.py --full --no-extra --no-cpu-baseline --config 3 --steps 3 --warmup 1 > /dev/null 2>> $O/err.log
 prof() {  # dir, rocprofv3 args..., -- bench args
   d=$1; shift
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/$d "$@" > /dev/null 2>&1)

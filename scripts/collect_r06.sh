@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r06
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout 1500 python bench.py > $O/bench_default.stdout 2> $O/bench_default.err
+timeout 1500 python bench.py --full > $O/bench_default.stdout 2> $O/bench_default.err
 cp bench_full.json $O/bench_default_full.json
 BA="--no-extra --no-cpu-baseline --no-roofline"
 W_b1="--steps 50"
@@ -19,7 +19,7 @@ W_b64h="--config 4 --steps 4 --warmup 2 --min-seconds 0 --matrix f16x3"
 W_highh="--config 3 --steps 2 --warmup 1 --min-seconds 0 --matrix f16x3"
 W_b1h="--steps 50 --matrix f16x3"
 # per-workload full result objects (algorithmic flops / bytes per kernel from the engine's level-2 profile rows)
-FA="--no-extra --no-cpu-baseline"
+FA="--full --no-extra --no-cpu-baseline"
 PIPER_BENCH_FULL=$O/full_b1.json timeout 300 python bench.py $FA --steps 100 > /dev/null 2>> $O/err.log
 PIPER_BENCH_FULL=$O/full_b64.json timeout 300 python bench.py $FA --config 4 --steps 5 --warmup 2 > /dev/null 2>> $O/err.log
 PIPER_BENCH_FULL=$O/full_high_b64.json timeout 300 python bench.py $FA --config 3 --steps 3 --warmup 1 > /dev/null 2>> $O/err.log

@@ -7,7 +7,7 @@ mkdir -p $O
 KEXPR="$1"; BARGS="$2"; KFILT="$3"
 cp piper_amd/libpiper_hip.so /tmp/new.so
 if [ -n "$KEXPR" ]; then timeout 900 python -m pytest tests -m gpu -q -x -k "$KEXPR" 2>&1 | tail -4; fi
-BQ="--no-extra --no-cpu-baseline --min-seconds 0.5"
+BQ="--full --no-extra --no-cpu-baseline --min-seconds 0.5"
 for r in 1 2; do
   cp piper_amd/libab_base.so piper_amd/libpiper_hip.so
   timeout 300 python bench.py $BQ $BARGS > $O/base_$r.json 2>> $O/err.log

@@ -3,7 +3,7 @@ bench.py command) into the per-kernel HBM traffic table bench.py reports as roof
 
 usage: pmc_traffic.py <key e.g. medium/b1/t128> <fetch_dir> <write_dir> <out.json> ["command string"] [bench_full.json]
 
-With a bench_full.json of the same workload (bench.py's full result object: roofline.kernels[*].algorithmic_bytes_per_launch,
+With a bench_full.json of the same workload (the full result object of a `bench.py --full` run: roofline.kernels[*].algorithmic_bytes_per_launch,
 from the engine's level-2 profile rows) every kernel also gets its algorithmic bytes and the ratio traffic / algorithmic.
 
 hbm_bytes_per_launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE/WRITE_SIZE are KiB; the factor 2 is

@@ -142,6 +142,33 @@ def test_headline_is_the_infer_seconds_span_and_names_both_clocks():
     assert r["kernel_avg_launch_us"] == 10.02 and r["rocprof_source"].endswith("kernel_stats.csv")
 
 
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse_args()
+    assert a.full is False and a.steps == 20 and a.warmup == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-roofline"])
+    a = bench.parse_args()
+    assert a.full is True and a.no_roofline is True
+
+
+def test_plain_run_line_carries_the_headline_alone():
+    """Without --full nothing beside the headline is measured: the parts that take runs of their own are absent (None in
+    the result object), and the line still says what the headline says with them."""
+    full = _full()
+    want = json.loads(bench.compact_line(full, None))
+    for k in ("roofline", "cpu_baseline", "extra_configs", "single_gpu_reference", "batched_per_gpu"):
+        full.pop(k, None)
+    for k in ("api_inclusive", "sustained", "device_resident_ms", "device_pipeline_only_ms_per_step"):
+        full[k] = None
+    d = json.loads(bench.compact_line(full, None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "x_realtime", "n_gpus", "steps", "warmup",
+              "config"):
+        assert d[k] == want[k], k
+    for k in ("roofline", "cpu_baseline", "extra_configs", "api_inclusive", "sustained", "device_resident_ms",
+              "device_pipeline_only_ms_per_step"):
+        assert k not in d, k
+
+
 def test_rocprof_clock_lookup_reads_the_committed_summaries():
     k = bench.rocprof_kernel_us("medium", 1, "gate4_kernel")
     assert k and 5.0 < k["avg_us"] < 20.0 and k["source"].endswith("_b1_kernel_stats.csv")

@@ -737,6 +737,32 @@ def test_bench_dump_outputs_are_reproducible(tmp_path):
         assert np.array_equal(a[n], got[1][n]), n
 
 
+def test_plain_bench_run_stops_at_the_headline():
+    """`bench.py --gpus 1 --steps N --warmup W` without `--full` does what its headline needs and no more: the line carries
+    the headline and none of the figures that take runs of their own (those are behind `--full`), and the whole process
+    -- interpreter start, voice, engine, graph capture at the first step included -- spends at most 30 s outside its
+    N + W steps."""
+    import subprocess
+    import sys
+    import time
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "audio samples/sec" and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+    assert d["value"] > 1e6 and d["ms_per_step"] > 0
+    for k in ("roofline", "cpu_baseline", "extra_configs", "api_inclusive", "sustained", "device_resident_ms",
+              "device_pipeline_only_ms_per_step", "single_gpu_reference", "batched_per_gpu"):
+        assert k not in d, k
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    print(f"plain bench run: {wall:.1f} s in all, {outside:.1f} s outside its steps")
+    assert outside <= 30.0, outside
+
+
 @pytest.mark.parametrize("devices", [[0, 0], [0, 1]])
 def test_engine_group_two_engines(monkeypatch, devices):
     """pe_group_* on hardware: two engines of one process -- on two GPUs when the box has them (hipMemcpyPeer over xGMI),
@@ -1040,7 +1066,7 @@ def test_bench_n_ranks_on_one_gpu_prints_a_compact_line(ranks):
     env = dict(os.environ, PIPER_BENCH_BACKEND="gloo", PIPER_BENCH_FULL=full)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-                        "--min-seconds", "0", "--no-roofline"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--full", "--min-seconds", "0", "--no-roofline"], capture_output=True, text=True, timeout=1500, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     line = p.stdout.strip().splitlines()[-1]
     assert len(line) < 4096, len(line)
@@ -1071,8 +1097,8 @@ def test_bench_two_gpus_over_rccl_or_refuses(tmp_path):
     ndev = torch.cuda.device_count()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("PIPER_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--min-seconds", "0",
-           "--no-roofline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
+           "--min-seconds", "0", "--no-roofline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     if ndev < 2:
         assert p.returncode != 0, "two nccl ranks on one GPU must not produce a result line"
