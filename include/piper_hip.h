@@ -118,6 +118,34 @@ int pe_stream_begin(pe_engine* e, const int64_t* ids, int64_t n_ids, const float
                     const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames);
 int pe_stream_next(pe_engine* e, int32_t chunk_frames, const float** audio, const int16_t** pcm, int64_t* n_samples);
 
+/* Streaming decode of a whole batch in lock step: B listeners get their first chunk after the text encoder, the duration
+ * predictor, the flow and ONE window decode, instead of after the whole batch (pe_synthesize_batch) or behind each other
+ * (pe_stream_begin, one utterance per handle at a time).
+ *
+ * pe_stream_begin_batch begins B utterances together: text encoder, duration predictor and flow for the whole batch, once.
+ * Arguments as pe_upload_scaled (ids concatenated, offsets[batch+1], one scales triple per utterance, sids / noise may be
+ * NULL). total_frames[batch] receives every utterance's frame count, *halo_frames the generator's receptive half-width. */
+int pe_stream_begin_batch(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                          const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames);
+
+typedef struct pe_stream_chunk {
+  int32_t batch;
+  const int64_t* sample_offsets; /* [batch+1] prefix offsets of THIS chunk into pcm / audio; a finished utterance has 0 samples */
+  const int16_t* pcm;            /* every utterance's chunk, packed back to back; each peak-normalised over ITS OWN chunk */
+  const float* audio;            /* the same samples as floats, or NULL unless want_audio */
+  const int32_t* frames_done;    /* [batch] frames delivered so far, this chunk included */
+} pe_stream_chunk;
+
+/* The next chunk_frames frames of every utterance that still has frames left, decoded as ONE batched generator pass on
+ * exact-halo windows: chunk k of utterance b is what pe_stream_next returns for chunk k of that utterance alone (same frame
+ * ranges, same per-chunk peak normalisation; the floats equal up to summation order). The peak, the int16 conversion and
+ * the packing run on the device and land in pinned host memory: the call ends with one synchronisation. Utterances finish
+ * at different calls; a finished one contributes zero samples and keeps frames_done[b] == total_frames[b].
+ * sample_offsets[batch] == 0 means every utterance is finished. chunk_frames may differ from call to call (a short first
+ * chunk, longer ones after). Views are engine-owned and valid until the next call on the handle. Any other synthesis call
+ * on the handle ends the batch stream: a later pe_stream_next_batch is an error ("no batch stream"), not stale data. */
+int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_stream_chunk* out);
+
 /* Integer per-id durations (ceil(w), reference models.py:703) of the last call, concatenated like ids. */
 int pe_get_durations(pe_engine* e, int32_t* out, int64_t capacity, int64_t* n);
 

@@ -15,6 +15,7 @@ SYMBOLS = [
     "pe_create", "pe_create_from_blob", "pe_weights_bound", "pe_create_in_arena", "pe_weights_used", "pe_arena_ready",
     "pe_onnx_to_blob", "pe_free", "pe_synthesize",
     "pe_synthesize_batch", "pe_synthesize_batch_scaled", "pe_upload", "pe_upload_scaled", "pe_run", "pe_fetch", "pe_stream_begin", "pe_stream_next",
+    "pe_stream_begin_batch", "pe_stream_next_batch",
     "pe_get_durations", "pe_get_info",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
     "pe_stream", "pe_debug_tensor", "pe_debug_randn", "pe_rng_calls", "pe_run_launches", "pe_speculation_stats", "pe_warmup", "pe_graph_stats", "pe_xcc_pattern", "pe_device_pci_bus_id", "pe_policy_describe", "pe_last_error", "pe_destroy",
@@ -34,6 +35,11 @@ class PeResult(C.Structure):
     _fields_ = [("batch", C.c_int32), ("sample_offsets", C.POINTER(C.c_int64)),
                 ("audio", C.POINTER(C.c_float)), ("pcm", C.POINTER(C.c_int16)),
                 ("frames", C.POINTER(C.c_int32)), ("infer_seconds", C.c_double)]
+
+
+class PeStreamChunk(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("sample_offsets", C.POINTER(C.c_int64)), ("pcm", C.POINTER(C.c_int16)),
+                ("audio", C.POINTER(C.c_float)), ("frames_done", C.POINTER(C.c_int32))]
 
 
 def bind(path: str) -> C.CDLL:
@@ -65,6 +71,8 @@ def bind(path: str) -> C.CDLL:
     lib.pe_fetch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PeResult)]
     lib.pe_stream_begin.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_next.argtypes = [vp, C.c_int32, C.POINTER(f32p), C.POINTER(C.POINTER(C.c_int16)), i64p]
+    lib.pe_stream_begin_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
+    lib.pe_stream_next_batch.argtypes = [vp, C.c_int32, C.c_int, C.POINTER(PeStreamChunk)]
     lib.pe_get_durations.argtypes = [vp, i32p, C.c_int64, i64p]
     lib.pe_get_info.argtypes = [vp, i32p, i32p, i32p, i32p, i64p]
     lib.pe_set_seed.argtypes = [vp, C.c_uint64]

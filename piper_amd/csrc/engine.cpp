@@ -71,6 +71,12 @@ void Engine::free_all() {
   if (h_frames_) hipHostFree(h_frames_);
   if (h_in_) hipHostFree(h_in_);
   h_in_ = nullptr; h_in_cap_ = 0;
+  if (sb_host_) hipHostFree(sb_host_);
+  if (sb_dev_) hipFree(sb_dev_);
+  if (sb_pcm_) hipHostFree(sb_pcm_);
+  if (sb_audio_) hipHostFree(sb_audio_);
+  sb_host_ = sb_dev_ = nullptr; sb_pcm_ = nullptr; sb_audio_ = nullptr;
+  sb_cap_ = 0; sb_pcm_cap_ = sb_audio_cap_ = 0; sb_active_ = false;
   if (ev0_) hipEventDestroy(ev0_);
   if (ev1_) hipEventDestroy(ev1_);
   for (auto& k : kev_) { hipEventDestroy(k.a); hipEventDestroy(k.b); }
@@ -341,6 +347,7 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   if (B <= 0 || B > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
   if (!scales) throw std::runtime_error("null scales");
   PE_HIP(hipSetDevice(device_));
+  sb_active_ = false;               // new inputs end a batch stream: its latent and its window state go with them
   B_ = B;
   id_off_.assign(offsets, offsets + B + 1);
   tlens_h_.resize(B);
@@ -486,6 +493,7 @@ void Engine::dispatch_stage(char which) {
     case 'B': issue_stage_b(); break;
     case 'C': issue_stage_a(); issue_stage_b(); break;
     case 'F': issue_flow(); break;
+    case 'V': issue_window_batch(); break;
     default: issue_window(); break;
   }
 }
@@ -815,6 +823,120 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// batch streaming
+// ------------------------------------------------------------------------------------------------
+
+// The state blocks (kernels/params.h: sb_*), sized by the stage-A batch capacity so that they grow when that does -- which
+// drops every graph anyway -- and not from one batch to the next.
+void Engine::ensure_stream_batch(int B) {
+  const int want = (int)((std::max<size_t>(capA_B_, (size_t)B) + 1) & ~(size_t)1);
+  if (sb_host_ && sb_dev_ && sb_cap_ >= want) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  drop_graphs();                                       // the blocks' addresses are kernel arguments inside the 'V' graphs
+  if (sb_host_) { PE_HIP(hipHostFree(sb_host_)); sb_host_ = nullptr; }
+  if (sb_dev_) { PE_HIP(hipFree(sb_dev_)); sb_dev_ = nullptr; }
+  sb_cap_ = 0;
+  const size_t bytes = (size_t)sb_words(want) * sizeof(int);
+  PE_HIP(hipHostMalloc((void**)&sb_host_, bytes));
+  PE_HIP(hipMalloc((void**)&sb_dev_, bytes));
+  memset(sb_host_, 0, bytes);
+  PE_HIP(hipMemset(sb_dev_, 0, bytes));
+  PE_HIP(hipDeviceSynchronize());
+  sb_cap_ = want;
+}
+
+const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
+                                                       const int64_t* sids, const NoiseIn* noise) {
+  EntryLock entry_lock;
+  upload(ids, offsets, B, scales, sids, noise, true);
+  PE_HIP(hipSetDevice(device_));
+  spec_pending_ = false;
+  s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
+  ensure_stream_batch(B);
+  Tg_ = std::min(id_bucket(Tmax_), Ts_);
+  char key[160];
+  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
+  run_stage('A', key);
+  ++call_;
+  PE_HIP(hipStreamSynchronize(stream_));
+  finish_stage_b_sizes();
+  ensure_stage_b(frame_bucket(Fmax_));
+  Fg_ = std::min(frame_bucket(Fmax_), Fs_);
+  lens_b_ = d_frames_;
+  if (have_noise_z_) {
+    issue_flow();
+  } else {
+    snprintf(key, sizeof(key), "F|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
+    run_stage('F', key);
+  }
+  sb_pos_.assign(B, 0);
+  sb_off_.assign(B + 1, 0);
+  sample_off_.assign(B + 1, 0);
+  sb_active_ = true;
+  return frames_h_;
+}
+
+void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out) {
+  EntryLock entry_lock;
+  if (!sb_active_) throw std::runtime_error("no batch stream begun on this handle (pe_stream_begin_batch)");
+  if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
+  PE_HIP(hipSetDevice(device_));
+  const int B = B_, cap = sb_cap_, c = std::min(chunk_frames, Fmax_);
+  // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A finished
+  // utterance gets the one-frame window [0, 1) and no delivery range.
+  int* st = sb_host_;
+  long long* off = reinterpret_cast<long long*>(st + sb_o_off(cap));
+  int wmax = 1;
+  int64_t total = 0;
+  for (int b = 0; b < B; ++b) {
+    const int F = frames_h_[b], f0 = sb_pos_[b], f1 = std::min(F, f0 + c);
+    int a = 0, e = 1, first = 0, count = 0;
+    if (f0 < F) {
+      a = std::max(0, f0 - halo_frames_);
+      e = std::min(F, f1 + halo_frames_);
+      first = (f0 - a) * hop_;
+      count = (f1 - f0) * hop_;
+    }
+    st[b] = a;
+    st[sb_o_len(cap) + b] = e - a;
+    st[sb_o_first(cap) + b] = first;
+    st[sb_o_count(cap) + b] = count;
+    off[b] = (long long)total;
+    sb_off_[b] = total;
+    total += count;
+    wmax = std::max(wmax, e - a);
+  }
+  sb_off_[B] = total;
+  out.batch = B;
+  out.sample_offsets = sb_off_.data();
+  out.frames_done = sb_pos_.data();
+  out.pcm = sb_pcm_;
+  out.audio = nullptr;
+  if (total == 0) return;                              // every utterance is finished
+  if ((size_t)total > sb_pcm_cap_) {
+    if (sb_pcm_) { PE_HIP(hipHostFree(sb_pcm_)); sb_pcm_ = nullptr; sb_pcm_cap_ = 0; }
+    PE_HIP(hipHostMalloc((void**)&sb_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
+    sb_pcm_cap_ = (size_t)total + (size_t)total / 2;
+  }
+  if (want_audio && (size_t)total > sb_audio_cap_) {
+    if (sb_audio_) { PE_HIP(hipHostFree(sb_audio_)); sb_audio_ = nullptr; sb_audio_cap_ = 0; }
+    PE_HIP(hipHostMalloc((void**)&sb_audio_, ((size_t)total + (size_t)total / 2) * sizeof(float)));
+    sb_audio_cap_ = (size_t)total + (size_t)total / 2;
+  }
+  void* ptrs[2] = {sb_pcm_, want_audio ? sb_audio_ : nullptr};
+  memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
+  s_wg_ = std::min(rup(c + 2 * halo_frames_, 32), Fs_);
+  if (s_wg_ < wmax) s_wg_ = std::min(rup(wmax, 32), Fs_);
+  char key[96];
+  snprintf(key, sizeof(key), "V|%d|%d|%d", B, s_wg_, Fs_);
+  run_stage('V', key);
+  PE_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b) sb_pos_[b] = std::min(frames_h_[b], sb_pos_[b] + c);
+  out.pcm = sb_pcm_;
+  out.audio = want_audio ? sb_audio_ : nullptr;
+}
+
 const std::vector<int32_t>& Engine::durations_host() {
   EntryLock entry_lock;
   finish_run();
@@ -867,7 +989,10 @@ void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& ou
     src = zp_keep_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_;
   }
   else if (name == "noise_w") { src = noise_w_ + (size_t)b * 2 * Ts_; R = 2; Cn = tlens_h_[b]; stride = Ts_; }
-  else if (name == "noise_z") { src = noise_z_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_; }
+  else if (name == "noise_z") {
+    if (sb_active_) throw std::runtime_error("noise_z is not available during a batch stream (its buffer holds the windows)");
+    src = noise_z_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_;
+  }
   else if (name == "audio") { src = audio_ + (size_t)b * Ss_; R = 1; Cn = frames_h_[b] * hop_; stride = Ss_; }
   else throw std::runtime_error("unknown debug tensor " + name);
   out.resize((size_t)R * Cn);

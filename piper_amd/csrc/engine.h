@@ -93,6 +93,24 @@ class Engine {
   bool stream_next(int chunk_frames, const float** audio, const int16_t** pcm, int64_t* nsamples);
   int decoder_halo_frames() const { return halo_frames_; }
 
+  // Streaming decode of a whole BATCH in lock step: stream_begin_batch is upload (one scales triple per utterance) + text
+  // encoder + durations + flow for B utterances, once; the latent stays resident. Every stream_next_batch decodes the
+  // next `chunk_frames` frames of every utterance that has frames left as ONE batched generator pass on exact-halo
+  // windows and delivers each utterance's chunk, peak-normalised over its own samples on the device, packed back to
+  // back in pinned host memory. Utterances finish at different calls: a finished one keeps a one-frame window whose
+  // output is not delivered (the generator's kernels have only ever seen lengths >= 1). Any other call that uploads
+  // inputs ends the stream. Views are valid until the next call.
+  struct StreamChunk {
+    int batch = 0;
+    const int64_t* sample_offsets = nullptr;    // [batch + 1] of THIS chunk
+    const int16_t* pcm = nullptr;
+    const float* audio = nullptr;               // null unless wanted
+    const int32_t* frames_done = nullptr;       // [batch]
+  };
+  const std::vector<int32_t>& stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
+                                                 const int64_t* sids, const NoiseIn* noise);
+  void stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out);
+
   int batch() const { return B_; }
   const std::vector<int64_t>& sample_offsets() { finish_run(); return sample_off_; }
   const float* audio_host() const { return h_audio_; }
@@ -224,7 +242,9 @@ class Engine {
   void issue_stage_b();
   void issue_flow();
   void issue_window();
-  void issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax);
+  // zero_absmax: a window pass (the peaks are cleared here, the PCM is not written to the zero-copy host buffer);
+  // with_pcm16 = false additionally leaves out the whole-window pcm16_kernel (batch streaming delivers per chunk)
+  void issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16 = true);
   void run_stage(char which, const std::string& key);
   void dispatch_stage(char which);
   void drop_graphs();
@@ -415,6 +435,20 @@ class Engine {
   int halo_frames_ = 0, s_frames_ = 0, s_pos_ = 0, s_wg_ = 0;
   bool s_active_ = false;
   std::vector<int16_t> s_pcm_;
+  // batch streaming. The window buffer [B][C][Fs] is noise_z_: dead once regulate_kernel has run (debug_tensor refuses
+  // "noise_z" while a batch stream is live). The per-chunk state block (kernels/params.h: sb_*) exists twice, pinned host
+  // and device, both allocated on the first batch stream for the stage-A batch capacity; their addresses are kernel
+  // arguments inside the 'V' graphs (growth drops the graphs), their CONTENT -- windows, delivery ranges, the output
+  // pointers -- is what changes from chunk to chunk.
+  bool sb_active_ = false;
+  int sb_cap_ = 0;
+  int* sb_host_ = nullptr; int* sb_dev_ = nullptr;
+  std::vector<int32_t> sb_pos_;                  // frames delivered per utterance
+  std::vector<int64_t> sb_off_;                  // sample offsets of the current chunk
+  int16_t* sb_pcm_ = nullptr; float* sb_audio_ = nullptr;     // pinned host output of the current chunk
+  size_t sb_pcm_cap_ = 0, sb_audio_cap_ = 0;
+  void ensure_stream_batch(int B);
+  void issue_window_batch();
   float* audio_ = nullptr;
   int16_t* pcm_ = nullptr;
   unsigned* absmax_ = nullptr;

@@ -415,9 +415,32 @@ void Engine::issue_window() {
   issue_decoder(zwin_, d_win_ + 1, s_wg_, (double)s_wg_, true);
 }
 
+// batch streaming: every utterance's window of z -> window buffer (the dead prior-noise buffer) -> generator on the
+// published window lengths -> per-chunk peak and int16 / float delivery into pinned host memory. One linear chain.
+void Engine::issue_window_batch() {
+  const int B = B_, cap = sb_cap_;
+  PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * s_wg_,
+               launch::window_gather(dim3((s_wg_ + 63) / 64, C_, B), stream_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, cap,
+                                     noise_z_, (long)C_ * Fs_, Fs_, s_wg_));
+  // what the cost models see (window geometry of the stage kernels, profile rows): the window bucket for every utterance --
+  // a function of the graph's key, whatever the utterances' real lengths are
+  std::vector<int32_t> win((size_t)B, s_wg_);
+  frames_h_.swap(win);
+  try {
+    issue_decoder(noise_z_, sb_dev_ + sb_o_len(cap), s_wg_, (double)B * s_wg_, true, false);
+  } catch (...) {
+    frames_h_.swap(win);
+    throw;
+  }
+  frames_h_.swap(win);
+  const int steps = std::max(1, (int)(((long)s_wg_ * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
+  PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * s_wg_ * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, sb_dev_, cap, hop_));
+  PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * s_wg_ * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, sb_dev_, cap, hop_));
+}
+
 // HiFiGAN generator + conv_post + int16 on z (already masked by its length semantics). `zsrc` is
 // [B][C][Fs_]; `lens` the per-utterance frame counts in device memory; Fmax the grid bound.
-void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax) {
+void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16) {
   stage_tiled_ = false;
   const int B = B_, Fs = Fs_;
   const View none{nullptr, 0, 0};
@@ -583,7 +606,8 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
       PE_LAUNCH_KB("conv_post_kernel", 4.0 * fsum * hop_ * (post_cin_ + 1.0), launch::conv_post(dim3((Lmax + POST_SPB - 1) / POST_SPB, B), stream_, cur.p, cur.bs, cur.cs, post_w_, post_cin_, 0.01f, lens, hop_, audio_, Ss_, absmax_));
     // (the streaming window path delivers per chunk from the device buffer)
     int16_t* zc = (pol_.pcm_zc && !zero_absmax && h_pcm_zc_cap_ >= (size_t)B * (size_t)Ss_) ? h_pcm_zc_ : nullptr;
-    PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * (4.0 + 2.0 + (zc ? 2.0 : 0.0)), launch::pcm16(dim3((Lmax + 255) / 256, B), stream_, audio_, Ss_, absmax_, lens, hop_, pcm_, Ss_, zc));
+    if (with_pcm16)
+      PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * (4.0 + 2.0 + (zc ? 2.0 : 0.0)), launch::pcm16(dim3((Lmax + 255) / 256, B), stream_, audio_, Ss_, absmax_, lens, hop_, pcm_, Ss_, zc));
     prof_end(4, tail_done ? 0.0 : 2.0 * fsum * hop_ * post_cin_ * K);
   }
 }

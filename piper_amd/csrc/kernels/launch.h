@@ -73,6 +73,12 @@ void conv_post(dim3 grid, hipStream_t stream, const float* x, long x_bs, int x_c
 void pcm16(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const unsigned* absmax, const int* lens,
            int len_mul, short* pcm, long p_bs, short* host);
 void window_copy(dim3 grid, hipStream_t stream, const float* z, int zs, const int* win, float* out, int ws, int C);
+// batch streaming (params.h: sb_*): grid = (64-frame tiles of the window bucket wg, channels, utterances)
+void window_gather(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const int* hst, int* dst, int cap,
+                   float* out, long o_bs, int ws, int wg);
+// ... and the chunk delivery: grid = (steps of CHUNK_SPB samples, utterances), peak first, conversion second
+void chunk_peak(dim3 grid, hipStream_t stream, const float* audio, long a_bs, int* st, int cap, int hop);
+void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop);
 
 }  // namespace launch
 }  // namespace pe

@@ -48,6 +48,19 @@ void window_copy(dim3 grid, hipStream_t stream, const float* z, int zs, const in
   PE_LAUNCH(window_copy_kernel, grid, dim3(64), 0, stream, z, zs, win, out, ws, C);
 }
 
+void window_gather(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const int* hst, int* dst, int cap,
+                   float* out, long o_bs, int ws, int wg) {
+  PE_LAUNCH(window_gather_kernel, grid, dim3(64), 0, stream, z, z_bs, zs, hst, dst, cap, out, o_bs, ws, wg);
+}
+
+void chunk_peak(dim3 grid, hipStream_t stream, const float* audio, long a_bs, int* st, int cap, int hop) {
+  PE_LAUNCH(chunk_peak_kernel, grid, dim3(256), 0, stream, audio, a_bs, st, cap, hop);
+}
+
+void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop) {
+  PE_LAUNCH(chunk_pcm_kernel, grid, dim3(256), 0, stream, audio, a_bs, st, cap, hop);
+}
+
 }  // namespace launch
 }  // namespace pe
 

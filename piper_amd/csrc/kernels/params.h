@@ -226,6 +226,25 @@ static constexpr int REG_MAXT = 4096;          // ids whose cumulative durations
 // ---- generator tail (post.h)
 static constexpr int POST_K = 7, POST_OPT = 4, POST_CU = 8, POST_CG = 4, POST_SPB = 64 * POST_OPT;
 
+// ---- batch streaming (post.h: window_gather_kernel, chunk_peak_kernel, chunk_pcm_kernel)
+// The per-chunk state of a batch stream is DATA, so that one captured graph serves every chunk: a block of 32-bit words
+// for `cap` utterances (cap even, the block 8-byte aligned) that the host fills in pinned memory before each chunk.
+// window_gather_kernel, the first launch of the window stage, reads it in place and publishes it to a device block of the
+// same layout for the launches behind it (the generator reads `len` as its contiguous int[B] frame counts).
+//   start[cap] len[cap]    window of z in frames: [start, start + len)
+//   first[cap] count[cap]  the chunk's own samples inside the window's waveform (the window minus its halo)
+//   off[cap] (64-bit)      where the chunk goes in the packed host output
+//   pcm, audio (pointers)  pinned host output of this chunk; audio null: no floats wanted
+//   peak[cap]              device block only: max |sample| of the chunk as a float's bit pattern, cleared by the gather
+static constexpr int sb_o_len(int cap) { return cap; }
+static constexpr int sb_o_first(int cap) { return 2 * cap; }
+static constexpr int sb_o_count(int cap) { return 3 * cap; }
+static constexpr int sb_o_off(int cap) { return 4 * cap; }
+static constexpr int sb_o_ptrs(int cap) { return 6 * cap; }
+static constexpr int sb_o_peak(int cap) { return 6 * cap + 4; }
+static constexpr int sb_words(int cap) { return 7 * cap + 4; }
+static constexpr int CHUNK_SPB = 1024;         // samples one workgroup of the delivery kernels covers per step
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

@@ -107,6 +107,100 @@ __global__ void window_copy_kernel(const float* z, int zs, const int* win, float
   if (c < C && t < win[1]) out[(long)c * ws + t] = z[(long)c * zs + win[0] + t];
 }
 
+// Batch streaming (pe_stream_next_batch), first launch of the window stage: frames [start_b, start_b + len_b) of z[b] into
+// window buffer [b]; grid = (64-frame tiles over the window bucket `wg`, channels, utterances). Columns [len_b, wg) are
+// zeroed: the buffer held other data before (the prior noise), and not every consumer of the generator's input masks by
+// `lens` before it multiplies. The window bounds come from the pinned host block `hst` (params.h: sb_*), cut to the row so
+// that nothing outside z[b] is ever read; workgroup (0, 0, b) publishes utterance b's state to the device block `dst` and
+// clears its chunk peak there.
+__global__ void window_gather_kernel(const float* z, long z_bs, int zs, const int* hst, int* dst, int cap, float* out,
+                                     long o_bs, int ws, int wg) {
+  PE_KTRACE(23);
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  int start = hst[b], len = hst[sb_o_len(cap) + b];
+  start = start < 0 ? 0 : (start > zs ? zs : start);
+  const int room = zs - start < wg ? zs - start : wg;
+  len = len < 0 ? 0 : (len > room ? room : len);
+  if (blockIdx.x == 0 && c == 0 && threadIdx.x == 0) {
+    dst[b] = start;
+    dst[sb_o_len(cap) + b] = len;
+    dst[sb_o_first(cap) + b] = hst[sb_o_first(cap) + b];
+    dst[sb_o_count(cap) + b] = hst[sb_o_count(cap) + b];
+    dst[sb_o_off(cap) + 2 * b] = hst[sb_o_off(cap) + 2 * b];
+    dst[sb_o_off(cap) + 2 * b + 1] = hst[sb_o_off(cap) + 2 * b + 1];
+    dst[sb_o_peak(cap) + b] = 0;
+    if (b == 0)
+      for (int k = 0; k < 4; ++k) dst[sb_o_ptrs(cap) + k] = hst[sb_o_ptrs(cap) + k];
+  }
+  if (t >= wg || t >= ws) return;
+  out[(long)b * o_bs + (long)c * ws + t] = t < len ? z[(long)b * z_bs + (long)c * zs + start + t] : 0.f;
+}
+
+// Chunk delivery of a batch stream, two launches over grid = (steps of CHUNK_SPB samples, utterances): the chunk is samples
+// [first_b, first_b + count_b) of utterance b's window waveform -- the window minus its halo, so conv_post_kernel's peak
+// (which covers the halo) is not the chunk's. A workgroup walks its steps (the chunk length is the caller's), and a
+// finished utterance (count 0) costs an early return.
+// 1. max |sample| over the chunk: one atomicMax on the float's bit pattern per workgroup (non-negative floats order like
+//    their bit patterns; the maximum does not depend on the order of the updates).
+__device__ __forceinline__ void chunk_range(const int* st, int cap, int b, int hop, int& first, int& count) {
+  const int L = st[sb_o_len(cap) + b] * hop;
+  first = st[sb_o_first(cap) + b];
+  count = st[sb_o_count(cap) + b];
+  first = first < 0 ? 0 : (first > L ? L : first);
+  count = count < 0 ? 0 : (count > L - first ? L - first : count);
+}
+__global__ __launch_bounds__(256) void chunk_peak_kernel(const float* audio, long a_bs, int* st, int cap, int hop) {
+  PE_KTRACE(24);
+  __shared__ float wmax[4];
+  const int b = blockIdx.y;
+  int first, count;
+  chunk_range(st, cap, b, hop, first, count);
+  if ((long)blockIdx.x * CHUNK_SPB >= count) return;
+  const float* a = audio + (long)b * a_bs + first;
+  float m = 0.f;
+  for (long base = (long)blockIdx.x * CHUNK_SPB; base < count; base += (long)gridDim.x * CHUNK_SPB)
+#pragma unroll
+    for (int j = 0; j < CHUNK_SPB / 256; ++j) {
+      const long i = base + j * 256 + threadIdx.x;
+      if (i < count) m = fmaxf(m, fabsf(a[i]));
+    }
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    atomicMax(reinterpret_cast<unsigned*>(st) + sb_o_peak(cap) + b,
+              __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+}
+// 2. float -> int16 as pcm16_kernel, with the chunk's own peak (the reference's streaming script normalises every chunk
+//    by itself, infer_onnx_streaming.py:122), stored packed back to back into pinned host memory at the utterance's
+//    offset; the floats go next to them when the caller wants them.
+__global__ __launch_bounds__(256) void chunk_pcm_kernel(const float* audio, long a_bs, const int* st, int cap, int hop) {
+  PE_KTRACE(25);
+  const int b = blockIdx.y;
+  int first, count;
+  chunk_range(st, cap, b, hop, first, count);
+  if ((long)blockIdx.x * CHUNK_SPB >= count) return;
+  const float* a = audio + (long)b * a_bs + first;
+  const long off = reinterpret_cast<const long long*>(st + sb_o_off(cap))[b];
+  short* pcm = reinterpret_cast<short* const*>(st + sb_o_ptrs(cap))[0] + off;
+  float* fout = reinterpret_cast<float* const*>(st + sb_o_ptrs(cap))[1];
+  const float peak = fmaxf(0.01f, __uint_as_float(reinterpret_cast<const unsigned*>(st)[sb_o_peak(cap) + b]));
+  const float scale = 32767.0f / peak;
+  for (long base = (long)blockIdx.x * CHUNK_SPB; base < count; base += (long)gridDim.x * CHUNK_SPB)
+#pragma unroll
+    for (int j = 0; j < CHUNK_SPB / 256; ++j) {
+      const long i = base + j * 256 + threadIdx.x;
+      if (i < count) {
+        const float x = a[i];
+        float v = x * scale;
+        v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+        pcm[i] = (short)v;
+        if (fout) fout[off + i] = x;
+      }
+    }
+}
+
 // MRF combine for the parallel-branch schedule: out = ((r0 + r1) + r2) * scale  (models.py:356-363)
 __global__ void mrf_sum_kernel(const float* r0, const float* r1, const float* r2, float* out, long bs, int cs,
                                const int* lens, int len_mul, float scale) {

@@ -261,6 +261,32 @@ int pe_stream_next(pe_engine* e, int32_t chunk_frames, const float** audio, cons
   });
 }
 
+int pe_stream_begin_batch(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                          const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    const std::vector<int32_t>& f = e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr);
+    if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
+int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_stream_chunk* out) {
+  return guard([&] {
+    if (!e || !out) throw std::runtime_error("null argument");
+    pe::Engine::StreamChunk c;
+    e->eng->stream_next_batch(chunk_frames, want_audio != 0, c);
+    out->batch = c.batch;
+    out->sample_offsets = c.sample_offsets;
+    out->pcm = c.pcm;
+    out->audio = c.audio;
+    out->frames_done = c.frames_done;
+  });
+}
+
 int pe_get_durations(pe_engine* e, int32_t* out, int64_t capacity, int64_t* n) {
   return guard([&] {
     if (!e || !n) throw std::runtime_error("null argument");

@@ -237,6 +237,48 @@ class Engine:
                 return
             yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
 
+    def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
+                     want_audio: bool = True):
+        """Generator over the chunks of B utterances streamed in lock step (pe_stream_begin_batch / pe_stream_next_batch):
+        text encoder, durations and flow for the whole batch once, then one batched vocoder pass per chunk. Every item
+        is a list of B ``(float chunk or None, int16 chunk)`` pairs -- empty arrays for utterances that are finished;
+        chunk k of utterance b is what ``stream`` yields for that utterance alone. ``chunk_frames``: an int, or a
+        callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales`` as in
+        ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
+        B = len(id_lists)
+        ids, offs = self._pack(id_lists)
+        per = per_utterance_scales(scales, B)
+        if per is None:
+            per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (B, 1)))
+        keep: list = [per]
+        nref = self._noise(noise_w, noise_z, keep)
+        sid_arr = None
+        if sids is not None:
+            sid_np = np.ascontiguousarray(sids, np.int64)
+            keep.append(sid_np)
+            sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
+        frames, halo = np.zeros(max(B, 1), np.int32), C.c_int32()
+        self._check(self._lib.pe_stream_begin_batch(
+            self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
+            per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, frames.ctypes.data_as(C.POINTER(C.c_int32)),
+            C.byref(halo)))
+        self.stream_frames, self.stream_halo = frames[:B].copy(), halo.value
+        self.stream_frames_done = np.zeros(B, np.int32)
+        k = 0
+        while True:
+            cf = int(chunk_frames(k)) if callable(chunk_frames) else int(chunk_frames)
+            ch = L.PeStreamChunk()
+            self._check(self._lib.pe_stream_next_batch(self._h, cf, int(bool(want_audio)), C.byref(ch)))
+            offs_k = np.frombuffer(C.string_at(ch.sample_offsets, 8 * (B + 1)), np.int64)
+            self.stream_frames_done = np.frombuffer(C.string_at(ch.frames_done, 4 * B), np.int32).copy()
+            total = int(offs_k[-1])
+            if total == 0:
+                return
+            p = np.frombuffer(bytearray(C.string_at(ch.pcm, 2 * total)), np.int16)
+            a = np.frombuffer(bytearray(C.string_at(ch.audio, 4 * total)), np.float32) if ch.audio else None
+            yield [(None if a is None else a[offs_k[b]:offs_k[b + 1]], p[offs_k[b]:offs_k[b + 1]]) for b in range(B)]
+            k += 1
+
     def durations(self) -> np.ndarray:
         n = C.c_int64()
         self._check(self._lib.pe_get_durations(self._h, None, 0, C.byref(n)))
