@@ -146,6 +146,44 @@ typedef struct pe_stream_chunk {
  * on the handle ends the batch stream: a later pe_stream_next_batch is an error ("no batch stream"), not stale data. */
 int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_stream_chunk* out);
 
+/* Stream pool: listeners join and leave a live batch stream. A fixed number of slots whose latents and decoder
+ * conditioning live in storage OWNED BY THE POOL, outside the engine's workspaces; every pe_stream_pool_next is one batched
+ * window stage over all slots, each slot advancing from its own position.
+ *
+ * pe_stream_pool_open allocates and zeroes the pool -- latents [slots][channels][max_frames rounded up to 64], conditioning
+ * rows, state blocks -- and sizes the workspaces once for a window stage of `slots` utterances. One pool per handle: a
+ * second open is an error. *halo_frames receives the generator's receptive half-width.
+ *
+ * pe_stream_pool_join begins n utterances (arguments as pe_stream_begin_batch: text encoder, durations and flow for the n
+ * newcomers, once) and moves their latents into free slots, lowest free slot first, in input order: slot_of[n] receives the
+ * slots, total_frames[n] the frame counts. With fewer than n free slots, or an utterance of more than max_frames frames,
+ * the whole join fails and the pool is exactly as it was. Like any other upload a join ends a pe_stream_begin /
+ * pe_stream_begin_batch stream on the handle.
+ *
+ * pe_stream_pool_next delivers the next chunk of every occupied slot: chunk_frames frames, or chunk_frames_per_slot[s]
+ * where that array is given and its entry is > 0 (a newcomer's short first chunk next to the residents' long ones). The
+ * result is a pe_stream_chunk with batch == slots and every array indexed by slot; a listener that joined before call k
+ * gets its frames [0, c) at call k, and every chunk is what pe_stream_next returns for that utterance alone. Free slots
+ * contribute zero samples. A slot whose last frame has been delivered is free from the next call on; its frames_done
+ * stays readable until the slot is reused. sample_offsets[slots] == 0: no slot has frames left (not an error).
+ *
+ * pe_stream_pool_leave frees an occupied slot at once (the listener hung up); leaving a free slot is an error.
+ *
+ * The pool survives every other call on the handle -- pe_synthesize*, pe_upload / pe_run / pe_fetch, pe_stream_begin*,
+ * pe_warmup, workspace growth -- because nothing it needs between two next calls lives in a workspace. The device-side
+ * results of a pe_run that has not been fetched do not: fetch before the next chunk. pe_stream_pool_close and pe_destroy
+ * free it. next, join or leave without an open pool: "no stream pool". */
+int pe_stream_pool_open(pe_engine* e, int32_t slots, int32_t max_frames, int32_t* halo_frames);
+int pe_stream_pool_join(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                        const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames);
+int pe_stream_pool_next(pe_engine* e, int32_t chunk_frames, const int32_t* chunk_frames_per_slot, int want_audio,
+                        pe_stream_chunk* out);
+int pe_stream_pool_leave(pe_engine* e, int32_t slot);
+int pe_stream_pool_close(pe_engine* e);
+/* Host view of the pool: *slots (0: no pool open, the arrays are not written), and per slot the utterance's frame count,
+ * the frames delivered so far and whether the slot is occupied (1) or free (0). Any pointer may be NULL. */
+int pe_stream_pool_state(pe_engine* e, int32_t* slots, int32_t* total_frames, int32_t* frames_done, int32_t* occupied);
+
 /* Integer per-id durations (ceil(w), reference models.py:703) of the last call, concatenated like ids. */
 int pe_get_durations(pe_engine* e, int32_t* out, int64_t capacity, int64_t* n);
 

@@ -16,6 +16,8 @@ SYMBOLS = [
     "pe_onnx_to_blob", "pe_free", "pe_synthesize",
     "pe_synthesize_batch", "pe_synthesize_batch_scaled", "pe_upload", "pe_upload_scaled", "pe_run", "pe_fetch", "pe_stream_begin", "pe_stream_next",
     "pe_stream_begin_batch", "pe_stream_next_batch",
+    "pe_stream_pool_open", "pe_stream_pool_join", "pe_stream_pool_next", "pe_stream_pool_leave", "pe_stream_pool_close",
+    "pe_stream_pool_state",
     "pe_get_durations", "pe_get_info",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
     "pe_stream", "pe_debug_tensor", "pe_debug_randn", "pe_rng_calls", "pe_run_launches", "pe_speculation_stats", "pe_warmup", "pe_graph_stats", "pe_xcc_pattern", "pe_device_pci_bus_id", "pe_policy_describe", "pe_last_error", "pe_destroy",
@@ -73,6 +75,12 @@ def bind(path: str) -> C.CDLL:
     lib.pe_stream_next.argtypes = [vp, C.c_int32, C.POINTER(f32p), C.POINTER(C.POINTER(C.c_int16)), i64p]
     lib.pe_stream_begin_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_next_batch.argtypes = [vp, C.c_int32, C.c_int, C.POINTER(PeStreamChunk)]
+    lib.pe_stream_pool_open.argtypes = [vp, C.c_int32, C.c_int32, i32p]
+    lib.pe_stream_pool_join.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
+    lib.pe_stream_pool_next.argtypes = [vp, C.c_int32, i32p, C.c_int, C.POINTER(PeStreamChunk)]
+    lib.pe_stream_pool_leave.argtypes = [vp, C.c_int32]
+    lib.pe_stream_pool_close.argtypes = [vp]
+    lib.pe_stream_pool_state.argtypes = [vp, i32p, i32p, i32p, i32p]
     lib.pe_get_durations.argtypes = [vp, i32p, C.c_int64, i64p]
     lib.pe_get_info.argtypes = [vp, i32p, i32p, i32p, i32p, i64p]
     lib.pe_set_seed.argtypes = [vp, C.c_uint64]

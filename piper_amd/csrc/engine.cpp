@@ -77,6 +77,7 @@ void Engine::free_all() {
   if (sb_audio_) hipHostFree(sb_audio_);
   sb_host_ = sb_dev_ = nullptr; sb_pcm_ = nullptr; sb_audio_ = nullptr;
   sb_cap_ = 0; sb_pcm_cap_ = sb_audio_cap_ = 0; sb_active_ = false;
+  stream_pool_free();
   if (ev0_) hipEventDestroy(ev0_);
   if (ev1_) hipEventDestroy(ev1_);
   for (auto& k : kev_) { hipEventDestroy(k.a); hipEventDestroy(k.b); }
@@ -494,6 +495,7 @@ void Engine::dispatch_stage(char which) {
     case 'C': issue_stage_a(); issue_stage_b(); break;
     case 'F': issue_flow(); break;
     case 'V': issue_window_batch(); break;
+    case 'P': issue_window_pool(); break;
     default: issue_window(); break;
   }
 }
@@ -846,14 +848,9 @@ void Engine::ensure_stream_batch(int B) {
   sb_cap_ = want;
 }
 
-const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                                                       const int64_t* sids, const NoiseIn* noise) {
-  EntryLock entry_lock;
-  upload(ids, offsets, B, scales, sids, noise, true);
-  PE_HIP(hipSetDevice(device_));
-  spec_pending_ = false;
-  s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
-  ensure_stream_batch(B);
+// Front half of both batch streams, on the uploaded batch: text encoder and durations, the frame counts read back, the
+// length regulator and the flow. The latent is left in zp_.
+void Engine::stream_front(int B, int max_frames) {
   Tg_ = std::min(id_bucket(Tmax_), Ts_);
   char key[160];
   snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
@@ -861,6 +858,11 @@ const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const
   ++call_;
   PE_HIP(hipStreamSynchronize(stream_));
   finish_stage_b_sizes();
+  if (max_frames > 0)
+    for (int b = 0; b < B; ++b)
+      if (frames_h_[b] > max_frames)
+        throw std::runtime_error("utterance " + std::to_string(b) + " has " + std::to_string(frames_h_[b]) +
+                                 " frames, the stream pool holds at most " + std::to_string(max_frames) + " (max_frames)");
   ensure_stage_b(frame_bucket(Fmax_));
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
@@ -870,6 +872,17 @@ const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const
     snprintf(key, sizeof(key), "F|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
     run_stage('F', key);
   }
+}
+
+const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
+                                                       const int64_t* sids, const NoiseIn* noise) {
+  EntryLock entry_lock;
+  upload(ids, offsets, B, scales, sids, noise, true);
+  PE_HIP(hipSetDevice(device_));
+  spec_pending_ = false;
+  s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
+  ensure_stream_batch(B);
+  stream_front(B, 0);
   sb_pos_.assign(B, 0);
   sb_off_.assign(B + 1, 0);
   sample_off_.assign(B + 1, 0);
@@ -937,6 +950,223 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   out.audio = want_audio ? sb_audio_ : nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// stream pool
+// ------------------------------------------------------------------------------------------------
+
+void Engine::stream_pool_require() const {
+  if (!sp_slots_) throw std::runtime_error("no stream pool open on this handle (pe_stream_pool_open)");
+}
+
+void Engine::stream_pool_free() {
+  if (sp_z_) hipFree(sp_z_);
+  if (sp_cond_) hipFree(sp_cond_);
+  if (sp_dev_) hipFree(sp_dev_);
+  if (sp_host_) hipHostFree(sp_host_);
+  if (sp_join_) hipHostFree(sp_join_);
+  if (sp_pcm_) hipHostFree(sp_pcm_);
+  if (sp_audio_) hipHostFree(sp_audio_);
+  sp_z_ = sp_cond_ = nullptr; sp_dev_ = sp_host_ = sp_join_ = nullptr; sp_pcm_ = nullptr; sp_audio_ = nullptr;
+  sp_pcm_cap_ = sp_audio_cap_ = 0;
+  sp_slots_ = sp_cap_ = sp_fcap_ = sp_maxf_ = 0;
+}
+
+int Engine::stream_pool_open(int slots, int max_frames) {
+  EntryLock entry_lock;
+  if (sp_slots_) throw std::runtime_error("a stream pool is already open on this handle (pe_stream_pool_close)");
+  if (slots < 1 || slots > 4096) throw std::runtime_error("stream pool slots must be in [1, 4096]");
+  if (max_frames < 1 || max_frames > MAX_FRAMES)
+    throw std::runtime_error("stream pool max_frames must be in [1, " + std::to_string(MAX_FRAMES) + "]");
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const int fcap = rup(max_frames, 64), cap = (slots + 1) & ~1;
+  // both workspaces for `slots` utterances, stage B for windows up to a whole row: once, here, so that a steady server's
+  // joins and chunks never grow them (growth drops every graph)
+  ensure_stage_a(slots, 1);
+  ensure_stage_b(fcap, slots);
+  PE_HIP(hipStreamSynchronize(stream_));
+  const size_t zbytes = (size_t)slots * C_ * fcap * sizeof(float);
+  const size_t cbytes = (size_t)slots * std::max(cond_dec_.rows, 1) * sizeof(float);
+  const size_t sbytes = (size_t)sb_words(cap) * sizeof(int), jbytes = (size_t)sj_words(cap) * sizeof(int);
+  try {
+    if (hipMalloc((void**)&sp_z_, zbytes) != hipSuccess) {
+      (void)hipGetLastError();
+      sp_z_ = nullptr;
+      throw std::runtime_error("out of device memory: " + std::to_string(zbytes >> 20) + " MiB of stream pool latents");
+    }
+    PE_HIP(hipMalloc((void**)&sp_cond_, cbytes));
+    PE_HIP(hipMalloc((void**)&sp_dev_, sbytes));
+    PE_HIP(hipHostMalloc((void**)&sp_host_, sbytes));
+    PE_HIP(hipHostMalloc((void**)&sp_join_, jbytes));
+    PE_HIP(hipMemset(sp_z_, 0, zbytes));
+    PE_HIP(hipMemset(sp_cond_, 0, cbytes));
+    PE_HIP(hipMemset(sp_dev_, 0, sbytes));
+    memset(sp_host_, 0, sbytes);
+    memset(sp_join_, 0, jbytes);
+    PE_HIP(hipDeviceSynchronize());
+  } catch (...) {
+    stream_pool_free();
+    throw;
+  }
+  sp_slots_ = slots; sp_cap_ = cap; sp_fcap_ = fcap; sp_maxf_ = max_frames;
+  sp_frames_.assign(slots, 0);
+  sp_pos_.assign(slots, 0);
+  sp_live_.assign(slots, 0);
+  sp_off_.assign(slots + 1, 0);
+  return halo_frames_;
+}
+
+void Engine::stream_pool_close() {
+  EntryLock entry_lock;
+  stream_pool_require();
+  PE_HIP(hipSetDevice(device_));
+  PE_HIP(hipStreamSynchronize(stream_));
+#ifndef PE_EMU
+  for (auto it = graphs_.begin(); it != graphs_.end();)      // the pool's addresses are kernel arguments inside the 'P' graphs
+    if (it->key.compare(0, 2, "P|") == 0) {
+      hipGraphExecDestroy((hipGraphExec_t)it->exec);
+      graph_of_.erase(it->key);
+      it = graphs_.erase(it);
+    } else {
+      ++it;
+    }
+#endif
+  stream_pool_free();
+}
+
+int Engine::stream_pool_state(int32_t* frames, int32_t* frames_done, int32_t* live) const {
+  for (int s = 0; s < sp_slots_; ++s) {
+    if (frames) frames[s] = sp_frames_[s];
+    if (frames_done) frames_done[s] = sp_pos_[s];
+    if (live) live[s] = sp_live_[s];
+  }
+  return sp_slots_;
+}
+
+void Engine::stream_pool_leave(int slot) {
+  EntryLock entry_lock;
+  stream_pool_require();
+  if (slot < 0 || slot >= sp_slots_) throw std::runtime_error("stream pool slot outside [0, slots)");
+  if (!sp_live_[slot]) throw std::runtime_error("stream pool slot " + std::to_string(slot) + " is free");
+  sp_live_[slot] = 0;
+}
+
+void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
+                              const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames) {
+  EntryLock entry_lock;
+  stream_pool_require();
+  if (n < 1) throw std::runtime_error("batch size must be in [1, 4096]");
+  std::vector<int> take;
+  for (int s = 0; s < sp_slots_ && (int)take.size() < n; ++s)
+    if (!sp_live_[s]) take.push_back(s);
+  if ((int)take.size() < n) {
+    int nfree = 0;
+    for (int s = 0; s < sp_slots_; ++s) nfree += sp_live_[s] ? 0 : 1;
+    throw std::runtime_error("stream pool has " + std::to_string(nfree) + " free slots, " + std::to_string(n) +
+                             " utterances want to join");
+  }
+  // from here to the adopt launch nothing of the pool is touched: whatever fails, the pool is as it was
+  upload(ids, offsets, n, scales, sids, noise, true);
+  PE_HIP(hipSetDevice(device_));
+  spec_pending_ = false;
+  s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent)
+  stream_front(n, sp_maxf_);
+  // the previous join ended with a synchronisation: nothing on the device reads the pinned join block any more
+  const int cap = sp_cap_;
+  sp_join_[0] = n;
+  for (int j = 0; j < n; ++j) {
+    sp_join_[sj_o_slot(cap) + j] = take[j];
+    sp_join_[sj_o_frames(cap) + j] = frames_h_[j];
+  }
+  const float* cond = nspk_ > 1 ? cond_ + cond_off_dec_ : nullptr;
+  PE_LAUNCH_KB("stream_adopt_kernel", 4.0 * n * C_ * ((double)Fg_ + sp_fcap_),
+               launch::stream_adopt(dim3((Fg_ + 63) / 64, C_, n), stream_, zp_, (long)C_ * Fs_, Fs_, cond, cond_bs_,
+                                    cond ? cond_dec_.rows : 0, sp_join_, cap, sp_z_, (long)C_ * sp_fcap_, sp_fcap_, sp_cond_,
+                                    sp_slots_));
+  PE_HIP(hipStreamSynchronize(stream_));
+  for (int j = 0; j < n; ++j) {
+    const int s = take[j];
+    sp_frames_[s] = frames_h_[j];
+    sp_pos_[s] = 0;
+    sp_live_[s] = 1;
+    if (slot_of) slot_of[j] = s;
+    if (total_frames) total_frames[j] = frames_h_[j];
+  }
+}
+
+void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool want_audio, StreamChunk& out) {
+  EntryLock entry_lock;
+  stream_pool_require();
+  if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles its sizes first)
+  const int S = sp_slots_, cap = sp_cap_;
+  // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A slot with
+  // nothing to deliver -- empty, finished, left -- gets the one-frame window [0, 1) of its own row and no delivery range.
+  int* st = sp_host_;
+  long long* off = reinterpret_cast<long long*>(st + sb_o_off(cap));
+  int wmax = 1, cmax = 1;
+  int64_t total = 0;
+  std::vector<int32_t> f1s(S);
+  for (int s = 0; s < S; ++s) {
+    const int F = sp_frames_[s], f0 = sp_pos_[s];
+    const int c = std::min(per_slot && per_slot[s] > 0 ? per_slot[s] : chunk_frames, sp_fcap_);
+    int a = 0, e = 1, first = 0, count = 0, f1 = f0;
+    if (sp_live_[s] && f0 < F) {
+      f1 = std::min(F, f0 + c);
+      a = std::max(0, f0 - halo_frames_);
+      e = std::min(F, f1 + halo_frames_);
+      first = (f0 - a) * hop_;
+      count = (f1 - f0) * hop_;
+      cmax = std::max(cmax, c);
+    }
+    f1s[s] = f1;
+    st[s] = a;
+    st[sb_o_len(cap) + s] = e - a;
+    st[sb_o_first(cap) + s] = first;
+    st[sb_o_count(cap) + s] = count;
+    off[s] = (long long)total;
+    sp_off_[s] = total;
+    total += count;
+    wmax = std::max(wmax, e - a);
+  }
+  sp_off_[S] = total;
+  out.batch = S;
+  out.sample_offsets = sp_off_.data();
+  out.frames_done = sp_pos_.data();
+  out.pcm = sp_pcm_;
+  out.audio = nullptr;
+  if (total == 0) return;                              // no slot has frames left
+  if ((size_t)total > sp_pcm_cap_) {
+    if (sp_pcm_) { PE_HIP(hipHostFree(sp_pcm_)); sp_pcm_ = nullptr; sp_pcm_cap_ = 0; }
+    PE_HIP(hipHostMalloc((void**)&sp_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
+    sp_pcm_cap_ = (size_t)total + (size_t)total / 2;
+  }
+  if (want_audio && (size_t)total > sp_audio_cap_) {
+    if (sp_audio_) { PE_HIP(hipHostFree(sp_audio_)); sp_audio_ = nullptr; sp_audio_cap_ = 0; }
+    PE_HIP(hipHostMalloc((void**)&sp_audio_, ((size_t)total + (size_t)total / 2) * sizeof(float)));
+    sp_audio_cap_ = (size_t)total + (size_t)total / 2;
+  }
+  void* ptrs[2] = {sp_pcm_, want_audio ? sp_audio_ : nullptr};
+  memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
+  // the workspaces as open sized them, should another call have shrunk them since (an exact-size fallback under memory
+  // pressure): a no-op otherwise
+  if (capA_B_ < (size_t)S) ensure_stage_a(S, 1);
+  ensure_stage_b(sp_fcap_, S);
+  sp_wg_ = std::min(rup(cmax + 2 * halo_frames_, 32), Fs_);
+  if (sp_wg_ < wmax) sp_wg_ = std::min(rup(wmax, 32), Fs_);
+  char key[96];
+  snprintf(key, sizeof(key), "P|%d|%d|%d", S, sp_wg_, Fs_);
+  run_stage('P', key);
+  PE_HIP(hipStreamSynchronize(stream_));
+  for (int s = 0; s < S; ++s) {
+    sp_pos_[s] = f1s[s];
+    if (sp_live_[s] && sp_pos_[s] >= sp_frames_[s]) sp_live_[s] = 0;      // free from the next call on
+  }
+  out.pcm = sp_pcm_;
+  out.audio = want_audio ? sp_audio_ : nullptr;
+}
+
 const std::vector<int32_t>& Engine::durations_host() {
   EntryLock entry_lock;
   finish_run();
@@ -971,7 +1201,7 @@ void Engine::debug_randn(int site, uint64_t call, int64_t row, int64_t n, float*
 }
 
 // Per-stage tensors for parity debugging (tests only): name in {x_enc, stats (m_p | logs_p), xg, logw, z_p, z, noise_w,
-// noise_z, audio}.
+// noise_z, audio, pool_z, pool_cond}.
 void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& out, int* rows, int* cols) {
   EntryLock entry_lock;
   finish_run();
@@ -994,6 +1224,13 @@ void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& ou
     src = noise_z_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_;
   }
   else if (name == "audio") { src = audio_ + (size_t)b * Ss_; R = 1; Cn = frames_h_[b] * hop_; stride = Ss_; }
+  else if (name == "pool_z" || name == "pool_cond") {
+    // stream pool: the WHOLE resident row of slot b (all Fcap frames, whatever its tenant's length), its conditioning row
+    stream_pool_require();
+    if (b < 0 || b >= sp_slots_) throw std::runtime_error("stream pool slot outside [0, slots)");
+    if (name == "pool_z") { src = sp_z_ + (size_t)b * C_ * sp_fcap_; R = C_; Cn = sp_fcap_; stride = sp_fcap_; }
+    else { src = sp_cond_ + (size_t)b * cond_dec_.rows; R = 1; Cn = cond_dec_.rows; stride = cond_dec_.rows; }
+  }
   else throw std::runtime_error("unknown debug tensor " + name);
   out.resize((size_t)R * Cn);
   for (int r = 0; r < R; ++r)

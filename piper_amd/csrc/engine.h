@@ -111,6 +111,26 @@ class Engine {
                                                  const int64_t* sids, const NoiseIn* noise);
   void stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out);
 
+  // Stream pool: a fixed number of slots whose latents and decoder conditioning rows live in storage OWNED BY THE POOL,
+  // outside both stage workspaces, so that listeners join and leave while others are in mid-stream. stream_pool_join is
+  // stream_begin_batch's front half for n newcomers (upload, text encoder, durations, flow -- it may overwrite every
+  // workspace) plus stream_adopt_kernel, which moves their latents into the lowest free slots in input order.
+  // stream_pool_next is ONE batched window stage over all slots: every live slot advances from its own position by
+  // chunk_frames, or by per_slot[s] where that is > 0; an empty, finished or left slot keeps the one-frame window of its
+  // own (zeroed or stale) row with nothing delivered. A slot whose last frame has been delivered is free from the next
+  // call on; its frames_done stays readable until it is reused. The pool survives every other call on the handle --
+  // nothing it needs between two next calls lives in a workspace -- and is freed by stream_pool_close and the destructor.
+  // A join that fails (too few free slots, an utterance over max_frames, an upload error) leaves the pool as it was.
+  int stream_pool_open(int slots, int max_frames);                 // returns the halo in frames
+  void stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
+                        const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames);
+  void stream_pool_next(int chunk_frames, const int32_t* per_slot, bool want_audio, StreamChunk& out);   // out.batch == slots
+  void stream_pool_leave(int slot);
+  void stream_pool_close();
+  // host view: slots (0: no pool; then the arrays are not touched), per slot total frames, frames delivered, 1 = occupied
+  int stream_pool_state(int32_t* frames, int32_t* frames_done, int32_t* live) const;
+  void stream_pool_require() const;                                // throws "no stream pool"
+
   int batch() const { return B_; }
   const std::vector<int64_t>& sample_offsets() { finish_run(); return sample_off_; }
   const float* audio_host() const { return h_audio_; }
@@ -449,6 +469,26 @@ class Engine {
   size_t sb_pcm_cap_ = 0, sb_audio_cap_ = 0;
   void ensure_stream_batch(int B);
   void issue_window_batch();
+  // text encoder, durations and flow of the uploaded batch, the latent left in zp_ (front half of both batch streams);
+  // max_frames > 0: an utterance with more frames is an error, raised before stage B is sized for it
+  void stream_front(int B, int max_frames);
+  // the window stage on B utterances: gather from `src` by the pinned state block `hst`, generator, chunk delivery
+  void issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg);
+  // stream pool (see above). Resident: the latent [slots][C][sp_fcap_], the decoder conditioning rows [slots][cond_dec
+  // rows] (multi-speaker voices), state blocks of its own in the sb_* layout at cap = sp_cap_ (slots rounded up to even),
+  // the pinned join block (params.h: sj_*) and the pinned chunk output. All of them are allocations of their own: workspace
+  // growth, which frees and poisons both workspaces and drops every graph, does not touch them. Their addresses are kernel
+  // arguments inside the 'P' graphs, which stream_pool_close destroys.
+  int sp_slots_ = 0, sp_cap_ = 0, sp_fcap_ = 0, sp_maxf_ = 0, sp_wg_ = 0;   // slots, block capacity, row width, max_frames, window bucket
+  float* sp_z_ = nullptr; float* sp_cond_ = nullptr;
+  int* sp_host_ = nullptr; int* sp_dev_ = nullptr; int* sp_join_ = nullptr;
+  std::vector<int32_t> sp_frames_, sp_pos_, sp_live_;
+  std::vector<int64_t> sp_off_;
+  int16_t* sp_pcm_ = nullptr; float* sp_audio_ = nullptr;
+  size_t sp_pcm_cap_ = 0, sp_audio_cap_ = 0;
+  const float* dec_cond_ = nullptr; int dec_cond_bs_ = 0;   // the decoder's conditioning rows while the pool's stage is issued (null: cond_)
+  void issue_window_pool();
+  void stream_pool_free();
   float* audio_ = nullptr;
   int16_t* pcm_ = nullptr;
   unsigned* absmax_ = nullptr;

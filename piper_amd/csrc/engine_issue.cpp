@@ -418,24 +418,40 @@ void Engine::issue_window() {
 // batch streaming: every utterance's window of z -> window buffer (the dead prior-noise buffer) -> generator on the
 // published window lengths -> per-chunk peak and int16 / float delivery into pinned host memory. One linear chain.
 void Engine::issue_window_batch() {
-  const int B = B_, cap = sb_cap_;
-  PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * s_wg_,
-               launch::window_gather(dim3((s_wg_ + 63) / 64, C_, B), stream_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, cap,
-                                     noise_z_, (long)C_ * Fs_, Fs_, s_wg_));
+  issue_window_stage(B_, sb_cap_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, s_wg_);
+}
+
+// stream pool: the same stage over all slots, reading the pool's resident rows and conditioning by the pool's state blocks.
+// The stage is issued as a call of `slots` utterances, whatever the handle's last upload was; that call's state comes back.
+void Engine::issue_window_pool() {
+  struct Restore {                                      // whichever way the stage is left
+    Engine* e; int B0;
+    ~Restore() { e->B_ = B0; e->dec_cond_ = nullptr; e->dec_cond_bs_ = 0; }
+  } restore{this, B_};
+  B_ = sp_slots_;
+  dec_cond_ = sp_cond_;
+  dec_cond_bs_ = cond_dec_.rows;
+  issue_window_stage(sp_slots_, sp_cap_, sp_z_, (long)C_ * sp_fcap_, sp_fcap_, sp_host_, sp_dev_, sp_wg_);
+}
+
+void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg) {
+  PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * wg,
+               launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, src, src_bs, src_cs, hst, dst, cap,
+                                     noise_z_, (long)C_ * Fs_, Fs_, wg));
   // what the cost models see (window geometry of the stage kernels, profile rows): the window bucket for every utterance --
   // a function of the graph's key, whatever the utterances' real lengths are
-  std::vector<int32_t> win((size_t)B, s_wg_);
+  std::vector<int32_t> win((size_t)B, wg);
   frames_h_.swap(win);
   try {
-    issue_decoder(noise_z_, sb_dev_ + sb_o_len(cap), s_wg_, (double)B * s_wg_, true, false);
+    issue_decoder(noise_z_, dst + sb_o_len(cap), wg, (double)B * wg, true, false);
   } catch (...) {
     frames_h_.swap(win);
     throw;
   }
   frames_h_.swap(win);
-  const int steps = std::max(1, (int)(((long)s_wg_ * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
-  PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * s_wg_ * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, sb_dev_, cap, hop_));
-  PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * s_wg_ * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, sb_dev_, cap, hop_));
+  const int steps = std::max(1, (int)(((long)wg * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
+  PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
+  PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * wg * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
 }
 
 // HiFiGAN generator + conv_post + int16 on z (already masked by its length semantics). `zsrc` is
@@ -444,7 +460,8 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
   stage_tiled_ = false;
   const int B = B_, Fs = Fs_;
   const View none{nullptr, 0, 0};
-  const float* cb_dec = nspk_ > 1 ? cond_ + cond_off_dec_ : nullptr;
+  const float* cb_dec = nspk_ > 1 ? (dec_cond_ ? dec_cond_ : cond_ + cond_off_dec_) : nullptr;
+  const int cb_dec_bs = dec_cond_ ? dec_cond_bs_ : cond_bs_;
   double fl = 0;
   bool tail_done = false;      // conv_post + tanh + peak computed inside the last stage's mrf_kernel
   // (zero_absmax marks the streaming window path; the whole-utterance path clears the peaks in regulate_kernel)
@@ -455,7 +472,7 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
   {
     View cur{hb_[0], (long)U_ * Fs, Fs};
     conv(dec_pre_, View{const_cast<float*>(zsrc), (long)C_ * Fs, Fs}, cur, lens, 1, Fmax, EPI_STORE, 1.f, ACT_NONE, none, none, 0, 1.f,
-         cb_dec, cond_bs_);
+         cb_dec, cb_dec_bs);
     fl += 2.0 * fsum * dec_pre_.macs_per_col;
     int mult = 1;
     int cur_buf = 0;

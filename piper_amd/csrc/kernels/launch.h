@@ -79,6 +79,9 @@ void window_gather(dim3 grid, hipStream_t stream, const float* z, long z_bs, int
 // ... and the chunk delivery: grid = (steps of CHUNK_SPB samples, utterances), peak first, conversion second
 void chunk_peak(dim3 grid, hipStream_t stream, const float* audio, long a_bs, int* st, int cap, int hop);
 void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop);
+// stream pool (params.h: sj_*): grid = (64-frame tiles of the newcomers' frame bucket, channels, newcomers)
+void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
+                  int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots);
 
 }  // namespace launch
 }  // namespace pe

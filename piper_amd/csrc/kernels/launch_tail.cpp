@@ -61,6 +61,12 @@ void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, con
   PE_LAUNCH(chunk_pcm_kernel, grid, dim3(256), 0, stream, audio, a_bs, st, cap, hop);
 }
 
+void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
+                  int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots) {
+  PE_LAUNCH(stream_adopt_kernel, grid, dim3(64), 0, stream, z, z_bs, zs, cond, cond_bs, cond_rows, join, cap, pool, p_bs, ps,
+            pcond, slots);
+}
+
 }  // namespace launch
 }  // namespace pe
 

@@ -245,6 +245,14 @@ static constexpr int sb_o_peak(int cap) { return 6 * cap + 4; }
 static constexpr int sb_words(int cap) { return 7 * cap + 4; }
 static constexpr int CHUNK_SPB = 1024;         // samples one workgroup of the delivery kernels covers per step
 
+// ---- stream pool (post.h: stream_adopt_kernel). The join block, pinned host memory for `cap` newcomers that the kernel
+// reads in place: which slot every newcomer of a join takes and how many frames it has -- data, not kernel arguments.
+//   n, (pad)               newcomers of this join
+//   slot[cap] frames[cap]  newcomer j goes to pool row slot[j] with frames[j] frames
+static constexpr int sj_o_slot(int cap) { (void)cap; return 2; }
+static constexpr int sj_o_frames(int cap) { return 2 + cap; }
+static constexpr int sj_words(int cap) { return 2 + 2 * cap; }
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

@@ -201,6 +201,52 @@ __global__ __launch_bounds__(256) void chunk_pcm_kernel(const float* audio, long
     }
 }
 
+// Stream pool (pe_stream_pool_join): the newcomers' latents move from the stage-B workspace, which the next upload
+// overwrites, into the pool's resident rows; grid = (64-frame tiles over the newcomers' frame bucket, channels, newcomers).
+// Newcomer j goes to row slot[j] (join block `join`, pinned host memory read in place; params.h: sj_*): frames [0, F_j) of
+// z[j][c] are copied, [F_j, ps) of the pool row are zeroed -- the row is ps frames wide, whatever the bucket is, and a
+// reused slot must not keep its previous tenant's tail -- so a workgroup walks from its tile in steps of the grid's width.
+// Workgroups (., 0, j) also copy the newcomer's decoder conditioning row (cond null: a single-speaker voice). Slot and
+// frame count are cut to the pool, so that nothing outside a row is read or written. With rows that start on 16-byte
+// boundaries -- every row the engine allocates does -- and the 64 threads it is launched with, a quarter wave owns a tile
+// and moves four frames per lane; anything else takes the one-frame-per-lane loop.
+__global__ __launch_bounds__(64) void stream_adopt_kernel(const float* z, long z_bs, int zs, const float* cond, int cond_bs,
+                                                          int cond_rows, const int* join, int cap, float* pool, long p_bs,
+                                                          int ps, float* pcond, int slots) {
+  PE_KTRACE(26);
+  const int j = blockIdx.z, c = blockIdx.y;
+  if (j >= cap || j >= join[0]) return;
+  const int slot = join[sj_o_slot(cap) + j];
+  if (slot < 0 || slot >= slots) return;
+  int F = join[sj_o_frames(cap) + j];
+  const int room = zs < ps ? zs : ps;
+  F = F < 0 ? 0 : (F > room ? room : F);
+  if (c == 0 && cond)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cond_rows; i += gridDim.x * blockDim.x)
+      pcond[(long)slot * cond_rows + i] = cond[(long)j * cond_bs + i];
+  const float* src = z + (long)j * z_bs + (long)c * zs;
+  float* dst = pool + (long)slot * p_bs + (long)c * ps;
+  const bool v4 = blockDim.x == 64 && ((zs | ps | (int)(z_bs & 3) | (int)(p_bs & 3)) & 3) == 0 &&
+                  ((reinterpret_cast<size_t>(z) | reinterpret_cast<size_t>(pool)) & 15) == 0;
+  if (v4) {
+    const int q = threadIdx.x & 15, r = threadIdx.x >> 4;
+    for (long tile = blockIdx.x + (long)r * gridDim.x; tile * 64 < ps; tile += 4L * gridDim.x) {
+      const int t = (int)(tile * 64) + q * 4;
+      if (t >= ps) continue;
+      f32x4 v;
+      if (t + 4 <= F) {
+        v = *reinterpret_cast<const f32x4*>(src + t);
+      } else {
+        for (int k = 0; k < 4; ++k) v[k] = t + k < F ? src[t + k] : 0.f;
+      }
+      *reinterpret_cast<f32x4*>(dst + t) = v;
+    }
+  } else {
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < ps; t += (long)gridDim.x * blockDim.x)
+      dst[t] = t < F ? src[t] : 0.f;
+  }
+}
+
 // MRF combine for the parallel-branch schedule: out = ((r0 + r1) + r2) * scale  (models.py:356-363)
 __global__ void mrf_sum_kernel(const float* r0, const float* r1, const float* r2, float* out, long bs, int cs,
                                const int* lens, int len_mul, float scale) {

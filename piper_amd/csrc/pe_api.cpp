@@ -287,6 +287,65 @@ int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_
   });
 }
 
+int pe_stream_pool_open(pe_engine* e, int32_t slots, int32_t max_frames, int32_t* halo_frames) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    const int halo = e->eng->stream_pool_open(slots, max_frames);
+    if (halo_frames) *halo_frames = halo;
+  });
+}
+
+int pe_stream_pool_join(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                        const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_require();
+    if (!ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, n, 4096);
+    pe::NoiseIn nz;
+    to_noise(noise, nz);
+    e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames);
+  });
+}
+
+int pe_stream_pool_next(pe_engine* e, int32_t chunk_frames, const int32_t* chunk_frames_per_slot, int want_audio,
+                        pe_stream_chunk* out) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_require();
+    if (!out) throw std::runtime_error("null argument");
+    pe::Engine::StreamChunk c;
+    e->eng->stream_pool_next(chunk_frames, chunk_frames_per_slot, want_audio != 0, c);
+    out->batch = c.batch;
+    out->sample_offsets = c.sample_offsets;
+    out->pcm = c.pcm;
+    out->audio = c.audio;
+    out->frames_done = c.frames_done;
+  });
+}
+
+int pe_stream_pool_leave(pe_engine* e, int32_t slot) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_leave(slot);
+  });
+}
+
+int pe_stream_pool_close(pe_engine* e) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_close();
+  });
+}
+
+int pe_stream_pool_state(pe_engine* e, int32_t* slots, int32_t* total_frames, int32_t* frames_done, int32_t* occupied) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    const int s = e->eng->stream_pool_state(total_frames, frames_done, occupied);
+    if (slots) *slots = s;
+  });
+}
+
 int pe_get_durations(pe_engine* e, int32_t* out, int64_t capacity, int64_t* n) {
   return guard([&] {
     if (!e || !n) throw std::runtime_error("null argument");

@@ -279,6 +279,11 @@ class Engine:
             yield [(None if a is None else a[offs_k[b]:offs_k[b + 1]], p[offs_k[b]:offs_k[b + 1]]) for b in range(B)]
             k += 1
 
+    def stream_pool(self, slots: int, max_frames: int) -> "StreamPool":
+        """Open a stream pool of ``slots`` listeners with utterances of up to ``max_frames`` frames (pe_stream_pool_open):
+        listeners join and leave while others are in mid-stream. Use as a context manager, or ``close()`` it."""
+        return StreamPool(self, slots, max_frames)
+
     def durations(self) -> np.ndarray:
         n = C.c_int64()
         self._check(self._lib.pe_get_durations(self._h, None, 0, C.byref(n)))
@@ -369,3 +374,102 @@ class Engine:
         self._check(self._lib.pe_debug_tensor(self._h, name.encode(), b, out.ctypes.data_as(C.POINTER(C.c_float)),
                                               capacity, C.byref(r), C.byref(c)))
         return out[: r.value * c.value].reshape(r.value, c.value).copy()
+
+
+class StreamPool:
+    """A live batch stream that listeners join and leave (pe_stream_pool_*). The latents of the utterances in flight are
+    resident in storage the pool owns, so every other call on the engine may run between two chunks. ``halo``: the
+    generator's receptive half-width in frames. ``frames`` / ``frames_done``: per slot, the utterance's frame count and the
+    frames delivered so far (a finished slot's stay readable until the slot is reused). ``free_slots``: the slots a join
+    may take, in the order it takes them."""
+
+    def __init__(self, engine: Engine, slots: int, max_frames: int):
+        self._eng, self.slots, self.max_frames, self._open = engine, int(slots), int(max_frames), False
+        halo = C.c_int32()
+        engine._check(engine._lib.pe_stream_pool_open(engine._h, self.slots, self.max_frames, C.byref(halo)))
+        self.halo, self._open = halo.value, True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._open and self._eng._h:
+            self._open = False
+            self._eng._check(self._eng._lib.pe_stream_pool_close(self._eng._h))
+        self._open = False
+
+    def _state(self):
+        n = C.c_int32()
+        arr = np.zeros((3, max(self.slots, 1)), np.int32)
+        p = [arr[i].ctypes.data_as(C.POINTER(C.c_int32)) for i in range(3)]
+        self._eng._check(self._eng._lib.pe_stream_pool_state(self._eng._h, C.byref(n), p[0], p[1], p[2]))
+        if n.value != self.slots:
+            raise EngineError("no stream pool open on this handle")
+        return arr[:, :self.slots]
+
+    @property
+    def frames(self) -> np.ndarray:
+        return self._state()[0].copy()
+
+    @property
+    def frames_done(self) -> np.ndarray:
+        return self._state()[1].copy()
+
+    @property
+    def free_slots(self) -> list:
+        return [int(s) for s in np.flatnonzero(self._state()[2] == 0)]
+
+    def join(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None) -> list:
+        """Begin the utterances of ``id_lists`` and give each a free slot, lowest first, in input order; returns the slots.
+        ``scales``: one triple, or a (B, 3) array of per-utterance triples. Fails as a whole, the pool unchanged, when
+        there are too few free slots or an utterance has more than ``max_frames`` frames."""
+        eng, n = self._eng, len(id_lists)
+        ids, offs = eng._pack(id_lists)
+        per = per_utterance_scales(scales, n)
+        if per is None:
+            per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (max(n, 1), 1)))
+        keep: list = [per]
+        nref = eng._noise(noise_w, noise_z, keep)
+        sid_arr = None
+        if sids is not None:
+            sid_np = np.ascontiguousarray(sids, np.int64)
+            keep.append(sid_np)
+            sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
+        slot_of, frames = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        eng._check(eng._lib.pe_stream_pool_join(
+            eng._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
+            per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, slot_of.ctypes.data_as(C.POINTER(C.c_int32)),
+            frames.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [int(s) for s in slot_of[:n]]
+
+    def next(self, chunk_frames: int = 45, per_slot=None, want_audio: bool = True) -> dict:
+        """The next chunk of every listener, one batched vocoder pass: ``{slot: (float chunk or None, int16 chunk)}`` for the
+        slots that got samples -- empty when no slot has frames left. ``per_slot``: ``{slot: frames}`` (or an array of
+        ``slots`` entries, 0 = default) overriding ``chunk_frames``, e.g. a short first chunk for a newcomer."""
+        eng, S = self._eng, self.slots
+        ps = None
+        if per_slot is not None:
+            ps_np = np.zeros(S, np.int32)
+            if isinstance(per_slot, dict):
+                for s, c in per_slot.items():
+                    ps_np[int(s)] = int(c)
+            else:
+                ps_np[:] = np.asarray(per_slot, np.int32)
+            ps = ps_np.ctypes.data_as(C.POINTER(C.c_int32))
+        ch = L.PeStreamChunk()
+        eng._check(eng._lib.pe_stream_pool_next(eng._h, int(chunk_frames), ps, int(bool(want_audio)), C.byref(ch)))
+        offs = np.frombuffer(C.string_at(ch.sample_offsets, 8 * (S + 1)), np.int64)
+        total = int(offs[-1])
+        if total == 0:
+            return {}
+        p = np.frombuffer(bytearray(C.string_at(ch.pcm, 2 * total)), np.int16)
+        a = np.frombuffer(bytearray(C.string_at(ch.audio, 4 * total)), np.float32) if ch.audio else None
+        return {s: (None if a is None else a[offs[s]:offs[s + 1]], p[offs[s]:offs[s + 1]])
+                for s in range(S) if offs[s + 1] > offs[s]}
+
+    def leave(self, slot: int):
+        """Free an occupied slot at once (the listener hung up)."""
+        self._eng._check(self._eng._lib.pe_stream_pool_leave(self._eng._h, int(slot)))
