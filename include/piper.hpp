@@ -89,6 +89,11 @@ struct SynthesisConfig {
 
   // Audio settings
   int sampleRate = 22050;
+  // Rate of the audio that is delivered; 0 = sampleRate, the voice's own. Anything else is resampled on the GPU before the
+  // int16 conversion (piper_hip.h: pe_set_output_rate, with sampleRate as the native rate): synthesize / synthesizeBatch /
+  // textToAudio set the engine accordingly, and the silences and the WAV header of textToWavFile use this rate. (Beyond the
+  // reference, which always delivers sampleRate.)
+  int outputSampleRate = 0;
   int sampleWidth = 2;  // 16-bit
   int channels = 1;     // mono
 

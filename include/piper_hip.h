@@ -41,7 +41,7 @@ typedef struct pe_result {
   const int64_t* sample_offsets; /* [batch+1] prefix offsets into audio / pcm */
   const float* audio;            /* float waveform in [-1,1], what Ort "output" [1,1,1,S] held (piper.cpp:397-400) */
   const int16_t* pcm;            /* peak-normalised int16 as piper.cpp:410-431 / util.py:5-12 produce */
-  const int32_t* frames;         /* [batch] spectrogram frames per utterance (S = frames * hop) */
+  const int32_t* frames;         /* [batch] spectrogram frames per utterance (S = frames * hop native samples; take lengths from sample_offsets) */
   double infer_seconds;          /* wall time of the device pipeline, the reference's inferSeconds (piper.cpp:385-395) */
 } pe_result;
 
@@ -191,12 +191,43 @@ int pe_get_durations(pe_engine* e, int32_t* out, int64_t capacity, int64_t* n);
 int pe_get_info(pe_engine* e, int32_t* sample_rate, int32_t* hop, int32_t* n_speakers, int32_t* n_symbols,
                 int64_t* weight_bytes);
 
+/* Output sample rate. Everything the engine delivers -- pe_result.audio / pcm of pe_synthesize*, pe_fetch, the groups and
+ * the coalescer; the chunks of pe_stream_next, pe_stream_next_batch and pe_stream_pool_next -- comes out at the voice's own
+ * rate (16 000 Hz for x_low / low voices, 22 050 Hz for medium / high) unless a rate is set here: then the float waveform is
+ * resampled ON THE DEVICE, before the int16 conversion, by a polyphase Kaiser-windowed sinc (pass band
+ * to 0.92 of the lower Nyquist within 0.07 dB, images and aliases below -90 dB). The reference never resamples; its rule for
+ * the int16 conversion -- scale by the maximum of what is delivered, piper.cpp:410-431 -- is kept: the peak is the RESAMPLED
+ * waveform's (whole utterance, or chunk), since a band-limited interpolation can overshoot the native one.
+ *   native_rate  the voice's rate; 0 = the rate in the voice's header. An .onnx carries none: pass "audio.sample_rate" of the
+ *                voice's .onnx.json. A value that contradicts a header's rate is an error, and so is 0 without one.
+ *   output_rate  8000 .. 48000 with output / gcd(native, output) <= 640 and a filter half-width (16 * native / (0.92 * the
+ *                lower rate) native samples) of at most one hop: 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100 and
+ *                48000 qualify for both voice rates. 0 or == native: off -- the engine is exactly the native-rate engine.
+ * With a rate set, pe_result.sample_offsets / audio / pcm are in OUTPUT samples: an utterance of S = frames * hop native
+ * samples has ceil(S * output / native) of them; `frames` stays in native frames. A stream chunk that covers native samples
+ * [s0, s1) delivers outputs [ceil(s0 * output / native), ceil(s1 * output / native)), so an utterance's chunks add up to
+ * its whole length and their floats are the whole utterance's resampling; windows are decoded with one more halo frame on
+ * each side (*halo_frames reports it), which keeps every chunk stateless. One rate per handle, not per utterance. Setting
+ * a rate while a stream, a batch stream or a stream pool is live is an error that changes nothing; any other failure leaves
+ * the previous setting in force too. A change drops the captured graphs (a server at a fixed rate stops capturing, as
+ * before). pe_get_info keeps reporting the native rate; pe_get_output_rate reports both and the half-width K in native
+ * samples (0 while off). */
+int pe_set_output_rate(pe_engine* e, int32_t native_rate, int32_t output_rate);
+int pe_get_output_rate(pe_engine* e, int32_t* native_rate, int32_t* output_rate, int32_t* half_width);
+
+/* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
+ * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them
+ * counts as zero. out[b][0 .. count[b]) receives outputs n0[b] .. n0[b] + count[b] - 1 of that utterance (out_stride floats
+ * per row). Lets a test feed tones and place n0 beyond 2^31 / M without a long utterance. An error while no rate is set. */
+int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
+                      const int32_t* count, const int64_t* origin, float* out, int64_t out_stride);
+
 void pe_set_seed(pe_engine* e, uint64_t seed);
 
 /* Timing with HIP events on the engine's stream. level 1: one pair per pipeline stage (rows
  * text_encoder, duration_predictor, regulate+flow, hifigan, post+pcm). level 2: additionally one pair
  * around every conv / attention / layer-norm launch (rows named after the kernel), with the launch's
- * algorithmic FLOPs. ms/flops/launches accumulate until pe_profile_reset(); 0 switches it off. */
+ * algorithmic FLOPs (the output-rate conversion: row resample_kernel, with its algorithmic bytes). ms/flops/launches accumulate until pe_profile_reset(); 0 switches it off. */
 int pe_profile_enable(pe_engine* e, int level);
 int pe_profile_reset(pe_engine* e);
 int pe_profile_rows(pe_engine* e);

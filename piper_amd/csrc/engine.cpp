@@ -4,6 +4,9 @@
 // kernel form a launch takes: policy.h.
 #include "engine_internal.h"
 
+#include <array>
+#include <numeric>
+
 namespace pe {
 
 thread_local long g_launches = 0;
@@ -78,6 +81,7 @@ void Engine::free_all() {
   sb_host_ = sb_dev_ = nullptr; sb_pcm_ = nullptr; sb_audio_ = nullptr;
   sb_cap_ = 0; sb_pcm_cap_ = sb_audio_cap_ = 0; sb_active_ = false;
   stream_pool_free();
+  rs_free();
   if (ev0_) hipEventDestroy(ev0_);
   if (ev1_) hipEventDestroy(ev1_);
   for (auto& k : kev_) { hipEventDestroy(k.a); hipEventDestroy(k.b); }
@@ -308,7 +312,8 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
   carve(wsB_, capB_B_, capB_F_);
   const size_t Bc = capB_B_, hmax = hmax_of(capB_F_);
   // zero-copy PCM: room for every utterance of the batch capacity, up to 256 MiB of pinned memory (beyond: copies)
-  const size_t zc_want = Bc * (size_t)Ss_;
+  So_ = rs_on_ ? (long)rup((int)out_samples(Ss_), 4) : Ss_;
+  const size_t zc_want = Bc * (size_t)So_;
   if (pol_.pcm_zc && zc_want * sizeof(int16_t) <= ((size_t)256 << 20) && h_pcm_zc_cap_ < zc_want) {
     PE_HIP(hipStreamSynchronize(stream_));
     drop_graphs();                                     // the pointer is a kernel argument inside the graphs
@@ -336,6 +341,7 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
     }
     side_floats_ = want;
   }
+  if (rs_on_) ensure_resample();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -677,7 +683,7 @@ void Engine::finish_stage_b_sizes() {
   // is followed within ~50 calls
   last_ratio_ = std::max(ratio, last_ratio_ * 0.98f + ratio * 0.02f);
   sample_off_.assign(B + 1, 0);
-  for (int b = 0; b < B; ++b) sample_off_[b + 1] = sample_off_[b] + (int64_t)frames_h_[b] * hop_;
+  for (int b = 0; b < B; ++b) sample_off_[b + 1] = sample_off_[b] + out_samples((int64_t)frames_h_[b] * hop_);
 }
 
 bool Engine::finish_run() {
@@ -719,15 +725,19 @@ void Engine::download(bool want_audio, bool want_pcm) {
     }
   };
   // pcm16_kernel already wrote the samples into pinned host memory (zero-copy), packed back to back: nothing to enqueue
-  const bool zc = pol_.pcm_zc && h_pcm_zc_ != nullptr && h_pcm_zc_cap_ >= (size_t)B_ * (size_t)Ss_;
+  const bool zc = pol_.pcm_zc && h_pcm_zc_ != nullptr && h_pcm_zc_cap_ >= (size_t)B_ * (size_t)So_;
+  // what is delivered: the generator's waveform, or its resampling (row stride So_; Ss_ at the native rate)
+  // (read where a copy is enqueued, not here: a missed guess re-sizes the workspace, and the buffers move with it)
+  auto asrc = [&]() -> const float* { return rs_on_ ? raudio_ : audio_; };
+  auto psrc = [&]() -> const int16_t* { return rs_on_ ? rpcm_ : pcm_; };
   pcm_zc_live_ = false;
   if (spec_pending_ && B_ == 1 && (want_audio || want_pcm)) {
     // one utterance, speculative run: the copies are enqueued for the guessed length (>= the real one when the guess
     // holds) behind stage B, so that one synchronisation ends the whole call; the host view is trimmed afterwards
-    const size_t n = (size_t)spec_fg_ * hop_;
+    const size_t n = (size_t)out_samples((int64_t)spec_fg_ * hop_);
     grow(n);
-    if (want_audio) PE_HIP(hipMemcpyAsync(h_audio_, audio_, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (want_pcm && !zc) PE_HIP(hipMemcpyAsync(h_pcm_, pcm_, n * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
+    if (want_audio) PE_HIP(hipMemcpyAsync(h_audio_, asrc(), n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (want_pcm && !zc) PE_HIP(hipMemcpyAsync(h_pcm_, psrc(), n * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
     if (finish_run()) {                        // synchronises; sample_off_ now holds the real length
       pcm_zc_live_ = zc;
       return;
@@ -740,12 +750,12 @@ void Engine::download(bool want_audio, bool want_pcm) {
   grow(total);
   if (want_audio)
     for (int b = 0; b < B_; ++b)
-      PE_HIP(hipMemcpyAsync(h_audio_ + sample_off_[b], audio_ + (size_t)b * Ss_,
+      PE_HIP(hipMemcpyAsync(h_audio_ + sample_off_[b], asrc() + (size_t)b * So_,
                             (size_t)(sample_off_[b + 1] - sample_off_[b]) * sizeof(float), hipMemcpyDeviceToHost,
                             stream_));
   if (want_pcm && !zc)
     for (int b = 0; b < B_; ++b)
-      PE_HIP(hipMemcpyAsync(h_pcm_ + sample_off_[b], pcm_ + (size_t)b * Ss_,
+      PE_HIP(hipMemcpyAsync(h_pcm_ + sample_off_[b], psrc() + (size_t)b * So_,
                             (size_t)(sample_off_[b + 1] - sample_off_[b]) * sizeof(int16_t), hipMemcpyDeviceToHost,
                             stream_));
   PE_HIP(hipStreamSynchronize(stream_));
@@ -792,21 +802,26 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
   if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
   PE_HIP(hipSetDevice(device_));
   const int f0 = s_pos_, f1 = std::min(s_frames_, s_pos_ + chunk_frames);
-  const int a = std::max(0, f0 - halo_frames_), b = std::min(s_frames_, f1 + halo_frames_);
+  const int hf = decoder_halo_frames();
+  const int a = std::max(0, f0 - hf), b = std::min(s_frames_, f1 + hf);
   const int win[2] = {a, b - a};
   PE_HIP(hipMemcpyAsync(d_win_, win, sizeof(win), hipMemcpyHostToDevice, stream_));
-  s_wg_ = std::min(rup(chunk_frames + 2 * halo_frames_, 32), Fs_);
+  // at a converted rate the chunk is outputs [ceil(s0 L / M), ceil(s1 L / M)) of the utterance, resampled out of the window
+  const int64_t o0 = out_samples((int64_t)f0 * hop_), o1 = out_samples((int64_t)f1 * hop_);
+  if (rs_on_) rs_host_row(0, o0, (int64_t)a * hop_, (int)(o1 - o0), (b - a) * hop_);
+  s_wg_ = std::min(rup(chunk_frames + 2 * hf, 32), Fs_);
   if (s_wg_ < b - a) s_wg_ = std::min(rup(b - a, 32), Fs_);
   char key[96];
   snprintf(key, sizeof(key), "W|%d|%d", s_wg_, Fs_);
   run_stage('W', key);
-  const size_t n = (size_t)(f1 - f0) * hop_;
+  const size_t n = (size_t)(o1 - o0);
   if (n > h_audio_cap_) {
     if (h_audio_) PE_HIP(hipHostFree(h_audio_));
     h_audio_cap_ = n + n / 2;
     PE_HIP(hipHostMalloc((void**)&h_audio_, h_audio_cap_ * sizeof(float)));
   }
-  PE_HIP(hipMemcpyAsync(h_audio_, audio_ + (size_t)(f0 - a) * hop_, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  PE_HIP(hipMemcpyAsync(h_audio_, rs_on_ ? raudio_ : audio_ + (size_t)(f0 - a) * hop_, n * sizeof(float), hipMemcpyDeviceToHost,
+                        stream_));
   PE_HIP(hipStreamSynchronize(stream_));
   // per-chunk peak normalisation, as the reference's streaming script does (infer_onnx_streaming.py:122)
   float peak = 0.01f;
@@ -895,7 +910,7 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   if (!sb_active_) throw std::runtime_error("no batch stream begun on this handle (pe_stream_begin_batch)");
   if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
   PE_HIP(hipSetDevice(device_));
-  const int B = B_, cap = sb_cap_, c = std::min(chunk_frames, Fmax_);
+  const int B = B_, cap = sb_cap_, c = std::min(chunk_frames, Fmax_), hf = decoder_halo_frames();
   // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A finished
   // utterance gets the one-frame window [0, 1) and no delivery range.
   int* st = sb_host_;
@@ -905,19 +920,22 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   for (int b = 0; b < B; ++b) {
     const int F = frames_h_[b], f0 = sb_pos_[b], f1 = std::min(F, f0 + c);
     int a = 0, e = 1, first = 0, count = 0;
+    int64_t ocount = 0;
     if (f0 < F) {
-      a = std::max(0, f0 - halo_frames_);
-      e = std::min(F, f1 + halo_frames_);
+      a = std::max(0, f0 - hf);
+      e = std::min(F, f1 + hf);
       first = (f0 - a) * hop_;
       count = (f1 - f0) * hop_;
+      ocount = out_samples((int64_t)f1 * hop_) - out_samples((int64_t)f0 * hop_);
     }
     st[b] = a;
     st[sb_o_len(cap) + b] = e - a;
     st[sb_o_first(cap) + b] = first;
     st[sb_o_count(cap) + b] = count;
+    if (rs_on_) rs_host_row(b, out_samples((int64_t)f0 * hop_), (int64_t)a * hop_, (int)ocount, (e - a) * hop_);
     off[b] = (long long)total;
     sb_off_[b] = total;
-    total += count;
+    total += ocount;
     wmax = std::max(wmax, e - a);
   }
   sb_off_[B] = total;
@@ -939,7 +957,7 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   }
   void* ptrs[2] = {sb_pcm_, want_audio ? sb_audio_ : nullptr};
   memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
-  s_wg_ = std::min(rup(c + 2 * halo_frames_, 32), Fs_);
+  s_wg_ = std::min(rup(c + 2 * hf, 32), Fs_);
   if (s_wg_ < wmax) s_wg_ = std::min(rup(wmax, 32), Fs_);
   char key[96];
   snprintf(key, sizeof(key), "V|%d|%d|%d", B, s_wg_, Fs_);
@@ -1013,7 +1031,7 @@ int Engine::stream_pool_open(int slots, int max_frames) {
   sp_pos_.assign(slots, 0);
   sp_live_.assign(slots, 0);
   sp_off_.assign(slots + 1, 0);
-  return halo_frames_;
+  return decoder_halo_frames();
 }
 
 void Engine::stream_pool_close() {
@@ -1100,7 +1118,8 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
   PE_HIP(hipSetDevice(device_));
   finish_run();                                        // (a speculative run still in flight settles its sizes first)
-  const int S = sp_slots_, cap = sp_cap_;
+  const int S = sp_slots_, cap = sp_cap_, hf = decoder_halo_frames();
+  std::vector<std::array<int64_t, 4>> rows;            // converted rate: every slot's row of the resampling launch
   // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A slot with
   // nothing to deliver -- empty, finished, left -- gets the one-frame window [0, 1) of its own row and no delivery range.
   int* st = sp_host_;
@@ -1112,12 +1131,14 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
     const int F = sp_frames_[s], f0 = sp_pos_[s];
     const int c = std::min(per_slot && per_slot[s] > 0 ? per_slot[s] : chunk_frames, sp_fcap_);
     int a = 0, e = 1, first = 0, count = 0, f1 = f0;
+    int64_t ocount = 0;
     if (sp_live_[s] && f0 < F) {
       f1 = std::min(F, f0 + c);
-      a = std::max(0, f0 - halo_frames_);
-      e = std::min(F, f1 + halo_frames_);
+      a = std::max(0, f0 - hf);
+      e = std::min(F, f1 + hf);
       first = (f0 - a) * hop_;
       count = (f1 - f0) * hop_;
+      ocount = out_samples((int64_t)f1 * hop_) - out_samples((int64_t)f0 * hop_);
       cmax = std::max(cmax, c);
     }
     f1s[s] = f1;
@@ -1125,9 +1146,10 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
     st[sb_o_len(cap) + s] = e - a;
     st[sb_o_first(cap) + s] = first;
     st[sb_o_count(cap) + s] = count;
+    rows.push_back({out_samples((int64_t)f0 * hop_), (int64_t)a * hop_, ocount, (int64_t)(e - a) * hop_});
     off[s] = (long long)total;
     sp_off_[s] = total;
-    total += count;
+    total += ocount;
     wmax = std::max(wmax, e - a);
   }
   sp_off_[S] = total;
@@ -1153,7 +1175,10 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   // pressure): a no-op otherwise
   if (capA_B_ < (size_t)S) ensure_stage_a(S, 1);
   ensure_stage_b(sp_fcap_, S);
-  sp_wg_ = std::min(rup(cmax + 2 * halo_frames_, 32), Fs_);
+  // (the row block exists once the workspaces are sized: the previous chunk's synchronisation freed it for writing)
+  if (rs_on_)
+    for (int s = 0; s < S; ++s) rs_host_row(s, rows[s][0], rows[s][1], (int)rows[s][2], (int)rows[s][3]);
+  sp_wg_ = std::min(rup(cmax + 2 * hf, 32), Fs_);
   if (sp_wg_ < wmax) sp_wg_ = std::min(rup(wmax, 32), Fs_);
   char key[96];
   snprintf(key, sizeof(key), "P|%d|%d|%d", S, sp_wg_, Fs_);
@@ -1165,6 +1190,222 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   }
   out.pcm = sp_pcm_;
   out.audio = want_audio ? sp_audio_ : nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// output-rate conversion
+// ------------------------------------------------------------------------------------------------
+
+void Engine::rs_free() {
+  if (rs_coef_) hipFree(rs_coef_);
+  if (raudio_) hipFree(raudio_);
+  if (rpcm_) hipFree(rpcm_);
+  if (rs_dev_) hipFree(rs_dev_);
+  if (rs_host_) hipHostFree(rs_host_);
+  rs_coef_ = raudio_ = nullptr; rpcm_ = nullptr; rs_dev_ = rs_host_ = nullptr;
+  rs_buf_elems_ = 0; rs_cap_ = 0;
+}
+
+// modified Bessel function of the first kind, order 0 (power series; x <= 8.6 here: ~30 terms to 1e-17 relative)
+static double bessel_i0(double x) {
+  double sum = 1.0, term = 1.0;
+  const double q = x * x / 4.0;
+  for (int k = 1; k < 200; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < 1e-17 * sum) break;
+  }
+  return sum;
+}
+
+void Engine::set_output_rate(int native, int output) {
+  EntryLock entry_lock;
+  const int header = arch_[A_SR];
+  if (native < 0 || output < 0) throw std::runtime_error("sample rates must not be negative");
+  if (native == 0) {
+    if (header <= 0 && rs_native_ <= 0)
+      throw std::runtime_error("native_rate 0 means the voice header's sample rate, and this voice carries none (an .onnx "
+                               "does not): pass the sample rate of its .onnx.json");
+    native = header > 0 ? header : rs_native_;
+  } else if (header > 0 && native != header) {
+    throw std::runtime_error("native_rate " + std::to_string(native) + " contradicts the voice header's sample rate " +
+                             std::to_string(header));
+  }
+  bool live = s_active_ && s_pos_ < s_frames_;
+  if (sb_active_)
+    for (int b = 0; b < B_ && b < (int)sb_pos_.size(); ++b) live = live || sb_pos_[b] < frames_h_[b];
+  if (live || sp_slots_)
+    throw std::runtime_error(std::string("the output rate cannot change while a ") +
+                             (sp_slots_ ? "stream pool is open" : "stream is live") + " on this handle");
+  const bool on = output != 0 && output != native;
+  const std::string pair = std::to_string(native) + " -> " + std::to_string(output) + " Hz";
+  int L = 1, M = 1, K = 0, Tp = 0, tile = RS_TILE;
+  std::vector<float> table;
+  if (on) {
+    if (output < 8000 || output > 48000)
+      throw std::runtime_error("output rate outside [8000, 48000]: " + pair);
+    const int g = std::gcd(native, output);
+    L = output / g; M = native / g;
+    if (L > 640)
+      throw std::runtime_error("rate pair " + pair + " needs a table of " + std::to_string(L) + " phases (output / gcd), more than 640");
+    const double fmin = std::min(native, output), fc = 0.92 * fmin / 2.0, Z = 16.0, beta = 8.6, Th = Z / (2.0 * fc);
+    K = (int)std::ceil(Z * (double)native / (0.92 * fmin) - 1e-9);
+    if (K > hop_)
+      throw std::runtime_error("rate pair " + pair + " needs a filter half-width of " + std::to_string(K) +
+                               " native samples, more than the voice's hop size " + std::to_string(hop_));
+    Tp = rup(2 * K, 4);
+    // output samples per workgroup: as many as keep the native span (tile * M / L + Tp + alignment slack) inside the LDS array
+    const long room = (long)(RS_SPAN - Tp - 6) * L / M;
+    tile = (int)std::min<long>(RS_TILE, room / 64 * 64);
+    if (tile < 64) throw std::runtime_error("rate pair " + pair + ": the native span of 64 outputs exceeds the staging buffer");
+    table.assign((size_t)L * Tp, 0.f);
+    const double i0b = bessel_i0(beta), pi = 3.14159265358979323846;
+    for (int ph = 0; ph < L; ++ph)
+      for (int k = 0; k < 2 * K; ++k) {
+        const double t = ((double)ph + (double)(K - 1 - k) * (double)L) / ((double)L * (double)native);
+        const double u = t / Th;
+        if (std::fabs(u) > 1.0) continue;
+        const double x = 2.0 * fc * t;
+        const double sinc = std::fabs(x) < 1e-12 ? 1.0 : std::sin(pi * x) / (pi * x);
+        table[(size_t)ph * Tp + k] =
+            (float)((2.0 * fc / (double)native) * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b);
+      }
+  }
+  if (on == rs_on_ && (!on || (native == rs_native_ && output == rs_out_))) {      // nothing changes (the native rate is noted)
+    rs_native_ = native;
+    return;
+  }
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles first)
+  PE_HIP(hipStreamSynchronize(stream_));
+  float* coef = nullptr;
+  if (on) {
+    PE_HIP(hipMalloc((void**)&coef, table.size() * sizeof(float)));
+    if (hipMemcpy(coef, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(coef);
+      throw std::runtime_error("upload of the resampling table failed");
+    }
+  }
+  // from here on nothing throws before the new setting is complete
+  drop_graphs();                                       // the stage sequences and their buffer addresses depend on the rate
+  if (rs_coef_) hipFree(rs_coef_);
+  rs_coef_ = coef;
+  rs_on_ = on; rs_native_ = native; rs_out_ = on ? output : 0;
+  rs_L_ = L; rs_M_ = M; rs_K_ = K; rs_Tp_ = Tp; rs_tile_ = tile;
+  s_active_ = false; sb_active_ = false;               // (finished streams end here: their windows were sized for the old rate)
+  pcm_zc_live_ = false;
+  if (!on) {                                           // back to the native engine: its buffers and strides
+    if (raudio_) hipFree(raudio_);
+    if (rpcm_) hipFree(rpcm_);
+    raudio_ = nullptr; rpcm_ = nullptr; rs_buf_elems_ = 0;
+    So_ = Ss_;
+  }
+  // (on: the next call's ensure_stage_b derives So_ and sizes the zero-copy PCM buffer and the resampled rows)
+}
+
+// The resampled rows [capB_B_][So_] (floats + int16) and the two row blocks, (re)allocated when the workspace capacity or
+// the rate changed; called at the end of ensure_stage_b, which has set So_.
+void Engine::ensure_resample() {
+  const size_t need = capB_B_ * (size_t)So_;
+  const int want_cap = (int)((std::max<size_t>(std::max(capA_B_, capB_B_), 64) + 1) & ~(size_t)1);
+  if (raudio_ && rpcm_ && rs_buf_elems_ >= need && rs_host_ && rs_dev_ && rs_cap_ >= want_cap) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  drop_graphs();
+  if (!(raudio_ && rpcm_ && rs_buf_elems_ >= need)) {
+    if (raudio_) { PE_HIP(hipFree(raudio_)); raudio_ = nullptr; }
+    if (rpcm_) { PE_HIP(hipFree(rpcm_)); rpcm_ = nullptr; }
+    rs_buf_elems_ = 0;
+    if (hipMalloc((void**)&raudio_, need * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&rpcm_, need * sizeof(int16_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (raudio_) hipFree(raudio_);
+      raudio_ = nullptr; rpcm_ = nullptr;
+      throw std::runtime_error("out of device memory: " + std::to_string((need * 6) >> 20) + " MiB of resampled output");
+    }
+    rs_buf_elems_ = need;
+    if (pol_.debug_poison) { poison(raudio_, need * sizeof(float)); poison(rpcm_, need * sizeof(int16_t)); }
+  }
+  if (!(rs_host_ && rs_dev_ && rs_cap_ >= want_cap)) {
+    if (rs_host_) { PE_HIP(hipHostFree(rs_host_)); rs_host_ = nullptr; }
+    if (rs_dev_) { PE_HIP(hipFree(rs_dev_)); rs_dev_ = nullptr; }
+    rs_cap_ = 0;
+    const size_t bytes = (size_t)rs_words(want_cap) * sizeof(int);
+    PE_HIP(hipHostMalloc((void**)&rs_host_, bytes));
+    PE_HIP(hipMalloc((void**)&rs_dev_, bytes));
+    memset(rs_host_, 0, bytes);
+    PE_HIP(hipMemset(rs_dev_, 0, bytes));
+    PE_HIP(hipDeviceSynchronize());
+    rs_cap_ = want_cap;
+  }
+}
+
+void Engine::rs_host_row(int b, int64_t n0, int64_t org, int count, int vlen) {
+  if (!rs_host_ || b < 0 || b >= rs_cap_) return;
+  reinterpret_cast<long long*>(rs_host_)[b] = n0;
+  reinterpret_cast<long long*>(rs_host_ + rs_o_org(rs_cap_))[b] = org;
+  rs_host_[rs_o_count(rs_cap_) + b] = count;
+  rs_host_[rs_o_vlen(rs_cap_) + b] = vlen;
+}
+
+void Engine::debug_resample(const float* x, int batch, int64_t stride, const int32_t* vlen, const int64_t* n0,
+                            const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
+  EntryLock entry_lock;
+  if (!rs_on_) throw std::runtime_error("no output rate set (pe_set_output_rate)");
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!x || !vlen || !n0 || !count || !origin || !out) throw std::runtime_error("null argument");
+  int maxc = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (vlen[b] < 0 || vlen[b] > stride) throw std::runtime_error("row " + std::to_string(b) + ": valid length outside [0, stride]");
+    if (count[b] < 0 || count[b] > out_stride) throw std::runtime_error("row " + std::to_string(b) + ": output count outside [0, out_stride]");
+    if (n0[b] < 0 || n0[b] > ((int64_t)1 << 40)) throw std::runtime_error("row " + std::to_string(b) + ": first output index out of range");
+    maxc = std::max(maxc, count[b]);
+  }
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const int cap = (batch + 1) & ~1;
+  const long xs = (long)((stride + 3) & ~(int64_t)3), ys = (long)((std::max<int64_t>(out_stride, 1) + 3) & ~(int64_t)3);
+  float *dx = nullptr, *dy = nullptr;
+  int *hrows = nullptr, *drows = nullptr;
+  auto release = [&]() {
+    if (dx) hipFree(dx);
+    if (dy) hipFree(dy);
+    if (drows) hipFree(drows);
+    if (hrows) hipHostFree(hrows);
+  };
+  try {
+    PE_HIP(hipMalloc((void**)&dx, (size_t)batch * std::max<long>(xs, 4) * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&dy, (size_t)batch * ys * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&drows, (size_t)rs_words(cap) * sizeof(int)));
+    PE_HIP(hipHostMalloc((void**)&hrows, (size_t)rs_words(cap) * sizeof(int)));
+    memset(hrows, 0, (size_t)rs_words(cap) * sizeof(int));
+    for (int b = 0; b < batch; ++b) {
+      reinterpret_cast<long long*>(hrows)[b] = n0[b];
+      reinterpret_cast<long long*>(hrows + rs_o_org(cap))[b] = origin[b];
+      hrows[rs_o_count(cap) + b] = count[b];
+      hrows[rs_o_vlen(cap) + b] = vlen[b];
+      if (stride > 0)
+        PE_HIP(hipMemcpyAsync(dx + (size_t)b * xs, x + (size_t)b * stride, (size_t)stride * sizeof(float), hipMemcpyHostToDevice, stream_));
+    }
+    PE_HIP(hipMemsetAsync(dy, 0xFF, (size_t)batch * ys * sizeof(float), stream_));
+    launch::resample_rows(stream_, hrows, nullptr, 0, drows, cap, batch, (long)stride, (long)out_stride, rs_L_, rs_M_);
+    if (maxc > 0) {
+      RsP p{};
+      p.x = dx; p.x_bs = xs; p.y = dy; p.y_bs = ys;
+      p.coef = rs_coef_; p.L = rs_L_; p.M = rs_M_; p.K = rs_K_; p.Tp = rs_Tp_;
+      p.rows = drows; p.cap = cap; p.tile = rs_tile_;
+      launch::resample(dim3((maxc + rs_tile_ - 1) / rs_tile_, batch), stream_, p);
+    }
+    for (int b = 0; b < batch; ++b)
+      if (count[b] > 0)
+        PE_HIP(hipMemcpyAsync(out + (size_t)b * out_stride, dy + (size_t)b * ys, (size_t)count[b] * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
 }
 
 const std::vector<int32_t>& Engine::durations_host() {

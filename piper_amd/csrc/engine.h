@@ -91,7 +91,27 @@ class Engine {
   // waveform (the reference pads by a heuristic 5-10 frames and does not). Returns false when done.
   int stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise);
   bool stream_next(int chunk_frames, const float** audio, const int16_t** pcm, int64_t* nsamples);
-  int decoder_halo_frames() const { return halo_frames_; }
+  // halo of a stream window in frames: the generator's receptive half-width, plus one frame while an output rate is set
+  // (the resampler needs exact native samples up to K <= hop beyond a chunk's edges)
+  int decoder_halo_frames() const { return halo_frames_ + (rs_on_ ? 1 : 0); }
+
+  // Output-rate conversion on the device (kernels/resample.h): every waveform the engine delivers -- whole utterances and
+  // stream chunks -- is resampled from the voice's rate to `output` by a polyphase Kaiser-windowed sinc before the int16
+  // conversion, whose peak is then the RESAMPLED waveform's. native == 0: the rate of the voice's header (an .onnx has
+  // none: the caller passes the value of its .onnx.json); output == 0 or == native: off, the engine is exactly the
+  // native-rate engine. Throws, and changes nothing, for a rate pair outside the supported set (8000 <= output <= 48000,
+  // L = output / gcd <= 640, half-width K <= hop), a native rate that contradicts the header, or while a stream, a batch
+  // stream or a stream pool is live. A change drops every captured graph.
+  void set_output_rate(int native, int output);
+  int native_rate() const { return rs_native_ ? rs_native_ : arch_[A_SR]; }
+  int output_rate() const { return rs_on_ ? rs_out_ : native_rate(); }
+  int resample_half_width() const { return rs_on_ ? rs_K_ : 0; }
+  // output samples of s native ones: ceil(s * L / M) (s itself at the native rate)
+  int64_t out_samples(int64_t s) const { return rs_on_ ? (s * rs_L_ + rs_M_ - 1) / rs_M_ : s; }
+  // test hook: resample_kernel with the current rate pair on host rows x[batch][stride]: row b holds vlen[b] native samples
+  // whose first one has native index origin[b]; outputs n0[b] .. n0[b] + count[b] - 1 go to out[b][out_stride]
+  void debug_resample(const float* x, int batch, int64_t stride, const int32_t* vlen, const int64_t* n0, const int32_t* count,
+                      const int64_t* origin, float* out, int64_t out_stride);
 
   // Streaming decode of a whole BATCH in lock step: stream_begin_batch is upload (one scales triple per utterance) + text
   // encoder + durations + flow for B utterances, once; the latent stays resident. Every stream_next_batch decodes the
@@ -489,6 +509,23 @@ class Engine {
   const float* dec_cond_ = nullptr; int dec_cond_bs_ = 0;   // the decoder's conditioning rows while the pool's stage is issued (null: cond_)
   void issue_window_pool();
   void stream_pool_free();
+  // output-rate conversion. The table, the resampled waveform [capB_B_][So_] with its int16 twin and the two row blocks
+  // (pinned host + device, params.h: rs_*) are allocations of their own; their addresses are kernel arguments inside the
+  // graphs, so (re)allocating them drops every graph. So_ is the row stride of what is delivered: Ss_ at the native rate.
+  bool rs_on_ = false;
+  int rs_native_ = 0, rs_out_ = 0, rs_L_ = 1, rs_M_ = 1, rs_K_ = 0, rs_Tp_ = 0, rs_tile_ = RS_TILE;
+  float* rs_coef_ = nullptr;
+  float* raudio_ = nullptr; int16_t* rpcm_ = nullptr; size_t rs_buf_elems_ = 0;
+  long So_ = 0;
+  int* rs_host_ = nullptr; int* rs_dev_ = nullptr; int rs_cap_ = 0;
+  void ensure_resample();                       // after ensure_stage_b sized the workspace
+  void rs_free();
+  // rows + resample launches on B rows of x (row stride x_bs, x_cap valid-capacity per row) into raudio_; hst: the pinned
+  // row block, or null with lens: whole utterances; max_out bounds every row's output count (grid)
+  void issue_resample(int B, const float* x, long x_bs, const int* hst, const int* lens, long max_out, double native_samples);
+  void rs_host_row(int b, int64_t n0, int64_t org, int count, int vlen);
+  const unsigned* rs_peaks() const { return reinterpret_cast<const unsigned*>(rs_dev_) + rs_o_peak(rs_cap_); }
+  const int* rs_counts() const { return rs_dev_ + rs_o_count(rs_cap_); }
   float* audio_ = nullptr;
   int16_t* pcm_ = nullptr;
   unsigned* absmax_ = nullptr;

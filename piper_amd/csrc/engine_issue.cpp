@@ -413,6 +413,24 @@ void Engine::issue_stage_b() {
 void Engine::issue_window() {
   PE_LAUNCH_K("window_copy_kernel", launch::window_copy(dim3((s_wg_ + 63) / 64, C_), stream_, zp_, Fs_, d_win_, zwin_, Fs_, C_));
   issue_decoder(zwin_, d_win_ + 1, s_wg_, (double)s_wg_, true);
+  // converted rate: the chunk is resampled out of the window's waveform (row 0 of the pinned row block)
+  if (rs_on_) issue_resample(1, audio_, Ss_, rs_host_, nullptr, out_samples((long)s_wg_ * hop_) + 1, (double)s_wg_ * hop_);
+}
+
+// Output-rate conversion of B rows of x into raudio_: the row block (from the pinned block `hst`, or whole utterances of
+// lens[b] * hop native samples), then resample_kernel on tiles of rs_tile_ outputs; max_out bounds every row's count.
+void Engine::issue_resample(int B, const float* x, long x_bs, const int* hst, const int* lens, long max_out, double native_samples) {
+  if (B > rs_cap_ || !raudio_ || !rs_coef_) throw std::runtime_error("resampling buffers are not sized for this call");
+  max_out = std::max<long>(1, std::min<long>(max_out, So_));
+  PE_LAUNCH_K("resample_rows_kernel",
+              launch::resample_rows(stream_, hst, lens, hop_, rs_dev_, rs_cap_, B, std::min<long>(x_bs, Ss_), So_, rs_L_, rs_M_));
+  RsP p{};
+  p.x = x; p.x_bs = x_bs; p.y = raudio_; p.y_bs = So_;
+  p.coef = rs_coef_; p.L = rs_L_; p.M = rs_M_; p.K = rs_K_; p.Tp = rs_Tp_;
+  p.rows = rs_dev_; p.cap = rs_cap_; p.tile = rs_tile_;
+  // algorithmic bytes: every native sample in once, every output out once (the table stays in cache)
+  PE_LAUNCH_KB("resample_kernel", 4.0 * native_samples * (1.0 + (double)rs_L_ / rs_M_),
+               launch::resample(dim3((unsigned)((max_out + rs_tile_ - 1) / rs_tile_), B), stream_, p));
 }
 
 // batch streaming: every utterance's window of z -> window buffer (the dead prior-noise buffer) -> generator on the
@@ -449,6 +467,16 @@ void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, i
     throw;
   }
   frames_h_.swap(win);
+  if (rs_on_) {
+    // converted rate: every chunk is resampled out of its window (rows in the pinned row block); the peak the kernel folds
+    // is the chunk's own, so the delivery is the conversion alone
+    const long max_out = out_samples((long)wg * hop_) + 1;
+    issue_resample(B, audio_, Ss_, rs_host_, nullptr, max_out, (double)B * wg * hop_);
+    const int rsteps = std::max(1, (int)((max_out + CHUNK_SPB - 1) / CHUNK_SPB));
+    PE_LAUNCH_KB("chunk_pcm_rs_kernel", 10.0 * B * (double)max_out,
+                 launch::chunk_pcm_rs(dim3(rsteps, B), stream_, raudio_, So_, rs_dev_, rs_cap_, dst, cap));
+    return;
+  }
   const int steps = std::max(1, (int)(((long)wg * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
   PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
   PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * wg * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
@@ -622,8 +650,16 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
     if (!tail_done)
       PE_LAUNCH_KB("conv_post_kernel", 4.0 * fsum * hop_ * (post_cin_ + 1.0), launch::conv_post(dim3((Lmax + POST_SPB - 1) / POST_SPB, B), stream_, cur.p, cur.bs, cur.cs, post_w_, post_cin_, 0.01f, lens, hop_, audio_, Ss_, absmax_));
     // (the streaming window path delivers per chunk from the device buffer)
-    int16_t* zc = (pol_.pcm_zc && !zero_absmax && h_pcm_zc_cap_ >= (size_t)B * (size_t)Ss_) ? h_pcm_zc_ : nullptr;
-    if (with_pcm16)
+    int16_t* zc = (pol_.pcm_zc && !zero_absmax && h_pcm_zc_cap_ >= (size_t)B * (size_t)So_) ? h_pcm_zc_ : nullptr;
+    if (rs_on_ && !zero_absmax) {
+      // converted rate, whole utterances: resample, then the int16 conversion on output lengths with the peak of the
+      // RESAMPLED waveform (a band-limited interpolation can overshoot the native peak)
+      const long max_out = out_samples((long)Lmax);
+      issue_resample(B, audio_, Ss_, nullptr, lens, max_out, fsum * hop_);
+      PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * ((double)rs_L_ / rs_M_) * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
+                   launch::pcm16(dim3((unsigned)((max_out + 255) / 256), B), stream_, raudio_, So_, rs_peaks(), rs_counts(), 1,
+                                 rpcm_, So_, zc));
+    } else if (with_pcm16)
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * (4.0 + 2.0 + (zc ? 2.0 : 0.0)), launch::pcm16(dim3((Lmax + 255) / 256, B), stream_, audio_, Ss_, absmax_, lens, hop_, pcm_, Ss_, zc));
     prof_end(4, tail_done ? 0.0 : 2.0 * fsum * hop_ * post_cin_ * K);
   }

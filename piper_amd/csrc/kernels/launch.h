@@ -82,6 +82,12 @@ void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, con
 // stream pool (params.h: sj_*): grid = (64-frame tiles of the newcomers' frame bucket, channels, newcomers)
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
                   int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots);
+// output-rate conversion (params.h: rs_*): the row block first (one thread per row), then grid = (tiles of p.tile output
+// samples, rows); chunk_pcm_rs = chunk_pcm on the resampled rows, grid = (steps of CHUNK_SPB samples, rows)
+void resample_rows(hipStream_t stream, const int* hst, const int* lens, int len_mul, int* rows, int cap, int B, long x_cap,
+                   long y_cap, int L, int M);
+void resample(dim3 grid, hipStream_t stream, const RsP& p);
+void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap);
 
 }  // namespace launch
 }  // namespace pe

@@ -3,6 +3,7 @@
 
 #include "mrf.h"
 #include "post.h"
+#include "resample.h"
 
 namespace pe {
 namespace launch {
@@ -65,6 +66,19 @@ void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int 
                   int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots) {
   PE_LAUNCH(stream_adopt_kernel, grid, dim3(64), 0, stream, z, z_bs, zs, cond, cond_bs, cond_rows, join, cap, pool, p_bs, ps,
             pcond, slots);
+}
+
+void resample_rows(hipStream_t stream, const int* hst, const int* lens, int len_mul, int* rows, int cap, int B, long x_cap,
+                   long y_cap, int L, int M) {
+  PE_LAUNCH(resample_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, hst, lens, len_mul, rows, cap, B, x_cap, y_cap, L, M);
+}
+
+void resample(dim3 grid, hipStream_t stream, const RsP& p) {
+  PE_LAUNCH(resample_kernel, grid, dim3(256), 0, stream, p);
+}
+
+void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap) {
+  PE_LAUNCH(chunk_pcm_rs_kernel, grid, dim3(256), 0, stream, y, y_bs, rows, rcap, st, cap);
 }
 
 }  // namespace launch

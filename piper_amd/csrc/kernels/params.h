@@ -253,6 +253,31 @@ static constexpr int sj_o_slot(int cap) { (void)cap; return 2; }
 static constexpr int sj_o_frames(int cap) { return 2 + cap; }
 static constexpr int sj_words(int cap) { return 2 + 2 * cap; }
 
+// ---- output-rate conversion (resample.h: resample_rows_kernel, resample_kernel, chunk_pcm_rs_kernel)
+// What a row of a resampling launch covers is DATA, like the window state above: a block of 32-bit words for `cap` rows
+// (cap even, the block 8-byte aligned). resample_rows_kernel fills the device block -- from the frame counts of a whole-
+// utterance call, or from a pinned host block of the same layout that a stream fills before each chunk -- and clears the peaks.
+//   n0[cap] (64-bit)       index of the row's first output sample within its utterance
+//   org[cap] (64-bit)      native index, within the utterance, of element 0 of the buffer the row reads
+//   count[cap]             output samples of the row
+//   vlen[cap]              elements [0, vlen) of that buffer are the utterance's samples; everything else reads as zero
+//   peak[cap]              device block only: max |output| as a float's bit pattern
+static constexpr int rs_o_org(int cap) { return 2 * cap; }
+static constexpr int rs_o_count(int cap) { return 4 * cap; }
+static constexpr int rs_o_vlen(int cap) { return 5 * cap; }
+static constexpr int rs_o_peak(int cap) { return 6 * cap; }
+static constexpr int rs_words(int cap) { return 7 * cap; }
+static constexpr int RS_TILE = 1024;           // output samples per workgroup, fewer where the native span would not fit
+static constexpr int RS_SPAN = 3072;           // floats of LDS that hold a tile's native span (12 KB)
+struct RsP {
+  const float* x; long x_bs;                   // native rows x[b][.]
+  float* y; long y_bs;                         // resampled rows y[b][0 .. count_b)
+  const float* coef;                           // [L][Tp] polyphase table, row = phase (n * M) mod L, 16-byte aligned rows
+  int L, M, K, Tp;                             // fs_out / g, fs_in / g, half-width in native samples, taps per row (2K rounded up to 4)
+  int* rows; int cap;                          // device row block
+  int tile;                                    // output samples per workgroup: its native span fits RS_SPAN
+};
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

@@ -370,6 +370,30 @@ int pe_get_info(pe_engine* e, int32_t* sample_rate, int32_t* hop, int32_t* n_spe
   });
 }
 
+int pe_set_output_rate(pe_engine* e, int32_t native_rate, int32_t output_rate) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_output_rate(native_rate, output_rate);
+  });
+}
+
+int pe_get_output_rate(pe_engine* e, int32_t* native_rate, int32_t* output_rate, int32_t* half_width) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (native_rate) *native_rate = e->eng->native_rate();
+    if (output_rate) *output_rate = e->eng->output_rate();
+    if (half_width) *half_width = e->eng->resample_half_width();
+  });
+}
+
+int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
+                      const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_resample(x, batch, stride, valid, n0, count, origin, out, out_stride);
+  });
+}
+
 void pe_set_seed(pe_engine* e, uint64_t seed) {
   if (e) e->eng->set_seed(seed);
 }

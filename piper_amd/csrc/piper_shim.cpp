@@ -340,9 +340,27 @@ void loadVoice(PiperConfig& config, std::string modelPath, std::string modelConf
   check(pe_create(modelPath.c_str(), voice.session.device, &voice.session.engine));
 }
 
+// SynthesisConfig::outputSampleRate (0 = the voice's own rate): the rate of what is delivered, and the engine setting that
+// goes with it -- pe_set_output_rate only when the engine is not already there, so code that never sets the field makes
+// exactly the calls it made before.
+static int delivered_rate(const SynthesisConfig& sc) {
+  return sc.outputSampleRate > 0 ? sc.outputSampleRate : sc.sampleRate;
+}
+static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) {
+  int32_t native = 0, out = 0, half = 0;
+  check(pe_get_output_rate(session.engine, &native, &out, &half));
+  const bool on = half > 0, want = sc.outputSampleRate > 0 && sc.outputSampleRate != sc.sampleRate;
+  if (!want) {
+    if (on) check(pe_set_output_rate(session.engine, sc.sampleRate, 0));
+  } else if (!on || out != sc.outputSampleRate) {
+    check(pe_set_output_rate(session.engine, sc.sampleRate, sc.outputSampleRate));
+  }
+}
+
 void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisConfig, ModelSession& session,
                 std::vector<int16_t>& audioBuffer, SynthesisResult& result) {
   if (!session.engine) throw std::runtime_error("voice model is not loaded");
+  apply_output_rate(synthesisConfig, session);
   const float scales[3] = {synthesisConfig.noiseScale, synthesisConfig.lengthScale, synthesisConfig.noiseW};
   const int64_t offsets[2] = {0, (int64_t)phonemeIds.size()};
   // "sid" is only fed for multi-speaker voices (piper.cpp:367-377); single-speaker graphs have no such input
@@ -358,7 +376,7 @@ void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisCo
   check(pe_fetch(session.engine, 0, 1, &r));
   result.inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   const int64_t n = r.sample_offsets[1];
-  result.audioSeconds = (double)n / (double)synthesisConfig.sampleRate;
+  result.audioSeconds = (double)n / (double)delivered_rate(synthesisConfig);
   result.realTimeFactor = result.audioSeconds > 0 ? result.inferSeconds / result.audioSeconds : 0.0;
   audioBuffer.insert(audioBuffer.end(), r.pcm, r.pcm + n);
 }
@@ -370,6 +388,7 @@ void synthesizeBatch(std::vector<std::vector<PhonemeId>>& phonemeIdLists, Synthe
   const int32_t nb = (int32_t)phonemeIdLists.size();
   audioBuffers.assign(nb, {});
   if (nb == 0) return;
+  apply_output_rate(synthesisConfig, session);
   const float scales[3] = {synthesisConfig.noiseScale, synthesisConfig.lengthScale, synthesisConfig.noiseW};
   std::vector<PhonemeId> flat;
   std::vector<int64_t> offsets(1, 0), sids(nb, synthesisConfig.speakerId.value_or(0));
@@ -386,7 +405,7 @@ void synthesizeBatch(std::vector<std::vector<PhonemeId>>& phonemeIdLists, Synthe
   result.inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (int32_t i = 0; i < nb; ++i)
     audioBuffers[i].assign(r.pcm + r.sample_offsets[i], r.pcm + r.sample_offsets[i + 1]);
-  result.audioSeconds = (double)r.sample_offsets[nb] / (double)synthesisConfig.sampleRate;
+  result.audioSeconds = (double)r.sample_offsets[nb] / (double)delivered_rate(synthesisConfig);
   result.realTimeFactor = result.audioSeconds > 0 ? result.inferSeconds / result.audioSeconds : 0.0;
 }
 
@@ -417,7 +436,7 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
   const SynthesisConfig& sc = voice.synthesisConfig;
   std::size_t sentenceSilenceSamples = 0;
   if (sc.sentenceSilenceSeconds > 0)
-    sentenceSilenceSamples = (std::size_t)(sc.sentenceSilenceSeconds * sc.sampleRate * sc.channels);
+    sentenceSilenceSamples = (std::size_t)(sc.sentenceSilenceSeconds * delivered_rate(sc) * sc.channels);
 
   if (config.useTashkeel) {     // piper.cpp:457-464: diacritize first; the model lives on the host, behind the slot
     if (!config.tashkeel) throw std::runtime_error("Tashkeel model is not loaded");
@@ -455,7 +474,7 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
         parts.back().push_back(p);
         auto it = sc.phonemeSilenceSeconds->find(p);
         if (it != sc.phonemeSilenceSeconds->end()) {
-          partSilence.push_back((std::size_t)(it->second * sc.sampleRate * sc.channels));
+          partSilence.push_back((std::size_t)(it->second * delivered_rate(sc) * sc.channels));
           parts.emplace_back();
         }
       }
@@ -532,10 +551,11 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     out.resize(g.p1 - g.p0);
     for (std::size_t k = 0; k < out.size(); ++k) out[k].assign(r.pcm + r.sample_offsets[k], r.pcm + r.sample_offsets[k + 1]);
-    result.audioSeconds += (double)r.sample_offsets[out.size()] / (double)sc.sampleRate;
+    result.audioSeconds += (double)r.sample_offsets[out.size()] / (double)delivered_rate(sc);
     return dt;
   };
   if (!voice.session.engine) throw std::runtime_error("voice model is not loaded");
+  apply_output_rate(sc, voice.session);
   std::size_t open_sentence = (std::size_t)-1;     // sentence whose audio is being assembled in audioBuffer
   auto close_sentence = [&]() {
     if (open_sentence == (std::size_t)-1) return;
@@ -605,8 +625,8 @@ void textToWavFile(PiperConfig& config, Voice& voice, std::string text, std::ost
   write_le(audioFile, 16, 4);
   write_le(audioFile, 1, 2);
   write_le(audioFile, (uint32_t)sc.channels, 2);
-  write_le(audioFile, (uint32_t)sc.sampleRate, 4);
-  write_le(audioFile, (uint32_t)(sc.sampleRate * sc.sampleWidth * sc.channels), 4);
+  write_le(audioFile, (uint32_t)delivered_rate(sc), 4);
+  write_le(audioFile, (uint32_t)(delivered_rate(sc) * sc.sampleWidth * sc.channels), 4);
   write_le(audioFile, (uint32_t)(sc.sampleWidth * sc.channels), 2);
   write_le(audioFile, 16, 2);
   audioFile.write("data", 4);

@@ -292,6 +292,55 @@ class Engine:
                                                C.byref(n)))
         return out
 
+    def set_output_rate(self, rate: Optional[int], native: Optional[int] = None):
+        """Deliver everything -- whole utterances and stream chunks -- at ``rate`` Hz, resampled on the device before the
+        int16 conversion (include/piper_hip.h: pe_set_output_rate). ``native``: the voice's own rate, needed where the
+        voice's header carries none (an .onnx: pass ``audio.sample_rate`` of its .onnx.json). ``rate`` None, 0 or the
+        native rate: off. Sample counts are then in output samples; ``frames`` stays in native frames."""
+        self._check(self._lib.pe_set_output_rate(self._h, int(native or 0), int(rate or 0)))
+
+    def _rates(self):
+        nat, out, k = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._lib.pe_get_output_rate(self._h, C.byref(nat), C.byref(out), C.byref(k)))
+        return nat.value, out.value, k.value
+
+    @property
+    def output_rate(self) -> int:
+        """The rate of what the engine delivers: the rate set by ``set_output_rate``, else the voice's own."""
+        return self._rates()[1]
+
+    @property
+    def native_rate(self) -> int:
+        return self._rates()[0]
+
+    @property
+    def resample_half_width(self) -> int:
+        """K: native samples on each side of an output's position that its filter taps reach (0 at the native rate)."""
+        return self._rates()[2]
+
+    def debug_resample(self, rows, n0=None, count=None, origin=None) -> List[np.ndarray]:
+        """Test hook (pe_debug_resample): the resampling kernel with the current rate pair on ``rows``, a list of 1-D float
+        arrays of native samples. Row b's first sample has native index ``origin[b]`` (default 0); outputs ``n0[b]`` ..
+        ``n0[b] + count[b] - 1`` are returned (default: all ceil(len * rate / native) outputs from 0)."""
+        B = len(rows)
+        nat, out, _ = self._rates()
+        valid = np.asarray([len(r) for r in rows], np.int32)
+        stride = max(1, int(valid.max()))
+        x = np.zeros((B, stride), np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        n0_a = np.zeros(B, np.int64) if n0 is None else np.ascontiguousarray(n0, np.int64)
+        org_a = np.zeros(B, np.int64) if origin is None else np.ascontiguousarray(origin, np.int64)
+        cnt_a = (np.asarray([-((-int(v) * out) // max(nat, 1)) for v in valid], np.int32) if count is None
+                 else np.ascontiguousarray(count, np.int32))
+        ostride = max(1, int(cnt_a.max()))
+        y = np.zeros((B, ostride), np.float32)
+        self._check(self._lib.pe_debug_resample(
+            self._h, x.ctypes.data_as(C.POINTER(C.c_float)), B, stride, valid.ctypes.data_as(C.POINTER(C.c_int32)),
+            n0_a.ctypes.data_as(C.POINTER(C.c_int64)), cnt_a.ctypes.data_as(C.POINTER(C.c_int32)),
+            org_a.ctypes.data_as(C.POINTER(C.c_int64)), y.ctypes.data_as(C.POINTER(C.c_float)), ostride))
+        return [y[b, :cnt_a[b]].copy() for b in range(B)]
+
     def set_seed(self, seed: int):
         self._lib.pe_set_seed(self._h, int(seed))
 

@@ -4,7 +4,8 @@ per stdin line with ``phoneme_ids`` (and optionally ``speaker_id``), one ``<line
 ``--output-dir``, same scale options and defaults. The ONNX Runtime session is replaced by the HIP engine;
 ``--batch N`` (new) groups N consecutive lines into one batched GPU call. A line may carry its own ``length_scale``,
 ``noise_scale`` and / or ``noise_w`` (new): they override the command-line values for that utterance alone, and the group
-it belongs to still runs as one call (one scale triple per utterance).
+it belongs to still runs as one call (one scale triple per utterance). ``--output-rate R`` (new) delivers the audio at R Hz,
+resampled on the GPU from ``--sample-rate`` (the voice's own rate); the WAV headers then say R.
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -69,6 +70,8 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     parser.add_argument("--model", required=True, help="Path to model (.onnx)")
     parser.add_argument("--output-dir", required=True, help="Path to write WAV files")
     parser.add_argument("--sample-rate", type=int, default=22050)
+    parser.add_argument("--output-rate", type=int, default=0,
+                        help="deliver the audio at this rate, resampled on the GPU from --sample-rate (0: off)")
     parser.add_argument("--noise-scale", type=float, default=0.667)
     parser.add_argument("--noise-scale-w", type=float, default=0.8)
     parser.add_argument("--length-scale", type=float, default=1.0)
@@ -84,6 +87,10 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     _LOGGER.info("Loaded model from %s", args.model)
     if args.seed is not None:
         engine.set_seed(args.seed)
+    wav_rate = args.sample_rate
+    if args.output_rate:
+        engine.set_output_rate(args.output_rate, native=args.sample_rate)
+        wav_rate = args.output_rate
     scales = (args.noise_scale, args.length_scale, args.noise_scale_w)
     lines = list(stdin if stdin is not None else sys.stdin)
     utts = read_utterances(lines)
@@ -99,11 +106,11 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
         res = engine.synthesize_batch([u[1] for u in group], call_scales,
                                       sids=None if all(s is None for s in sids) else [s or 0 for s in sids])
         infer_sec = time.perf_counter() - t0
-        audio_sec = sum(p.shape[-1] for p in res.pcm) / args.sample_rate
+        audio_sec = sum(p.shape[-1] for p in res.pcm) / wav_rate
         _LOGGER.debug("Real-time factor for %s..%s: %0.4f (infer=%0.4f sec, audio=%0.2f sec)", group[0][0] + 1,
                       group[-1][0] + 1, infer_sec / audio_sec if audio_sec > 0 else 0.0, infer_sec, audio_sec)
         for (idx, _, _), pcm in zip(group, res.pcm):
-            write_wav(out_dir / f"{idx}.wav", args.sample_rate, pcm)
+            write_wav(out_dir / f"{idx}.wav", wav_rate, pcm)
     engine.close()
     return 0
 

@@ -52,18 +52,28 @@ _LOGGER = logging.getLogger(__name__)
 class PiperVoice:
     session: Engine
     config: PiperConfig
+    output_sample_rate: Optional[int] = None      # None: the voice's own rate (config.sample_rate)
 
     @staticmethod
     def load(model_path: Union[str, Path], config_path: Optional[Union[str, Path]] = None,
-             use_cuda: bool = True, device: int = 0) -> "PiperVoice":
+             use_cuda: bool = True, device: int = 0, output_sample_rate: Optional[int] = None) -> "PiperVoice":
         """Load an ONNX voice and its config. ``use_cuda`` is accepted for signature compatibility;
-        the engine always runs on the GPU (``device``)."""
+        the engine always runs on the GPU (``device``). ``output_sample_rate`` (new): deliver the audio at this rate,
+        resampled on the GPU before the int16 conversion (Engine.set_output_rate; the config's rate is the native one)."""
         if config_path is None:
             config_path = f"{model_path}.json"
         with open(config_path, "r", encoding="utf-8") as config_file:
             config_dict = json.load(config_file)
-        return PiperVoice(config=PiperConfig.from_dict(config_dict),
-                          session=Engine(onnx_path=str(model_path), device=device))
+        config = PiperConfig.from_dict(config_dict)
+        session = Engine(onnx_path=str(model_path), device=device)
+        if output_sample_rate:
+            session.set_output_rate(int(output_sample_rate), native=int(config.sample_rate))
+        return PiperVoice(config=config, session=session, output_sample_rate=output_sample_rate or None)
+
+    @property
+    def sample_rate(self) -> int:
+        """The rate of the audio this voice delivers: ``output_sample_rate`` when set, else the config's."""
+        return int(self.output_sample_rate or self.config.sample_rate)
 
     def phonemize(self, text: str) -> List[List[str]]:
         """Text to phonemes grouped by sentence."""
@@ -99,7 +109,7 @@ class PiperVoice:
                    length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                    noise_w: Optional[float] = None, sentence_silence: float = 0.0):
         """Synthesize WAV audio from text."""
-        wav_file.setframerate(self.config.sample_rate)
+        wav_file.setframerate(self.sample_rate)
         wav_file.setsampwidth(2)
         wav_file.setnchannels(1)
         for audio_bytes in self.synthesize_stream_raw(text, speaker_id=speaker_id, length_scale=length_scale,
@@ -112,7 +122,7 @@ class PiperVoice:
                               noise_w: Optional[float] = None, sentence_silence: float = 0.0) -> Iterable[bytes]:
         """Synthesize raw audio per sentence from text."""
         sentence_phonemes = self.phonemize(text)
-        num_silence_samples = int(sentence_silence * self.config.sample_rate)
+        num_silence_samples = int(sentence_silence * self.sample_rate)
         silence_bytes = bytes(num_silence_samples * 2)
         for phonemes in sentence_phonemes:
             phoneme_ids = self.phonemes_to_ids(phonemes)
