@@ -12,11 +12,16 @@ LIB := piper_amd/libpiper_hip.so
 EMULIB := tests/emu/libpiper_hip_emu.so
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -Wno-unused-result -Wno-unused-value
 EMUFLAGS := -DPE_EMU -O2 -mfma -mf16c -std=c++17 -Wno-psabi -fPIC -Itests/emu
+# Leading scalar kernel parameters arrive in SGPRs at wave launch (up to 14 dwords): the launch units whose kernels are written
+# for it (pe_rt.h PE_ENTRY_BATCH; scripts/entry_waits.py shows what each kernel gets)
+PRELOAD := -mllvm -amdgpu-kernarg-preload-count=14
+PRELOAD_UNITS := kernels/launch_front kernels/launch_conv kernels/launch_tail
 OBJ := $(patsubst $(CSRC)/%.cpp,build/gfx950/%.o,$(SRCS))
 OBJ_STAMPS := $(patsubst $(CSRC)/%.cpp,build/stamps/%.o,$(SRCS))
 OBJ_EMU := $(patsubst $(CSRC)/%.cpp,build/emu/%.o,$(SRCS)) build/emu/hip_emu.o
 
 all: $(LIB)
+$(foreach u,$(PRELOAD_UNITS),build/gfx950/$(u).o build/stamps/$(u).o): HIPFLAGS += $(PRELOAD)
 
 build/gfx950/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(dir $@)

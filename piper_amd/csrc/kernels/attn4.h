@@ -30,18 +30,22 @@ namespace pe {
 // second register set before the current unit's MFMAs (T = 384: 28.9 -> 20.9 us per launch); up to 128 ids there is no next
 // unit and the second set only costs registers (10.9 -> 12.4 us), so the launcher picks <DK, false> there.
 template <int DK, bool DB>
-__global__ __launch_bounds__(256) void attn4_kernel(AttnOP p) {
+__global__ __launch_bounds__(256) void attn4_kernel(const int* lens, const float* qkv, long q_bs, const float* kT, long kt_bs,
+                                                    int nx, int xcd, int q_cs, int window, AttnOP p) {
   PE_KTRACE(14);
   constexpr int NH = 2, H = NH * DK, NC = 4, NVT = 3, KS1 = Col4W<H>::KS, QS = DK + 4, NREL = 9;
   static_assert(H == C4_H && DK % 16 == 0, "compiled for the 192-channel voices (two heads of 96)");
   PE_DYN_SMEM(float, sm);
+  // kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names (14 dwords), nx = gridDim.x
+  p.lens = lens; p.xcd = xcd; p.qkv = qkv; p.q_bs = q_bs; p.q_cs = q_cs; p.kT = kT; p.kt_bs = kt_bs; p.window = window;
+  PE_ENTRY_BATCH(p.SP, p.relk, p.relv, p.vQ);
   const int b = blockIdx.y;
   PE_STAMP(0, 0);
   // The utterance length lives in device memory: nothing below touches it until Q, the tables, the first K unit and the
   // first V chunk are requested (against the row stride; what lies beyond the length is masked where it is used), so its
   // latency overlaps theirs instead of preceding them.
   const int T = p.lens[b];
-  const int i0 = c4_tile(blockIdx.x, gridDim.x, p.xcd) * NC;
+  const int i0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
   const int tid = threadIdx.x, lane = tid & 63, wv = PE_UNIFORM(tid >> 6);
   const int l3 = lane & 3, lb = lane >> 2;
   const int SP = p.SP, nrel = 2 * p.window + 1;

@@ -102,14 +102,27 @@ __device__ __forceinline__ float pe_col_sum4(float v, float* red, int& flip, int
 // the post conv's input is (W0.in0 + b0) + in1 instead of in1 (in1 = the skip sum of the layers before; `first`: not
 // read). The same additions in the same order as the mode-2 launch it replaces, whose output is not written at all: the
 // skip sum of a coupling layer has no other reader.
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs
+// (14 dwords); nx = gridDim.x. The length decides whether the workgroup runs at all, so its pointer comes first: lens[b]
+// is requested together with the rest of the struct and both are waited for once.
+// Tuning build, colchain4_kernel<false>: stamps 0 entry, 1 struct and length arrived, 2 operand loads and fragments requested.
 template <bool FRONT>
-__global__ __launch_bounds__(256) void colchain4_kernel(ColP p) {
+__global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const float* in1, long in1_bs, int nx, int xcd, int mode,
+                                                        int in1_cs, int K1r, int rows1, int first, int out_cs, ColP p) {
   PE_KTRACE(3);
   constexpr int NC = 4, NVT = 3, K1 = C4_H, K2 = C4_H / 2, KS1 = Col4W<K1>::KS, KS2 = Col4W<K2>::KS;
   PE_DYN_SMEM(float, sm);                       // YT[4][KS1] | P[4 waves][192][4] | red[2][4][4]
-  const int b = blockIdx.y, L = p.lens[b];
-  const int t0 = c4_tile(blockIdx.x, gridDim.x, p.xcd) * NC;
+  if constexpr (!FRONT) PE_STAMP(3, 0);
+  p.lens = lens; p.xcd = xcd; p.mode = mode; p.in1 = in1; p.in1_bs = in1_bs; p.in1_cs = in1_cs; p.K1 = K1r; p.rows1 = rows1;
+  p.first = first; p.out_cs = out_cs;
+  const int b = blockIdx.y;
+  int L = PE_UNIFORM(lens[b]);                              // decides whether the workgroup runs: part of the batch, one wait for both
+  if constexpr (FRONT) PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1,
+                                      p.in0, p.in0_bs, p.in0_cs, p.w0, p.b0);
+  else PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1);
+  const int t0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
   if (t0 >= L) return;
+  if constexpr (!FRONT) PE_STAMP(3, 1);
   float* YT = sm;
   float* P = YT + NC * KS1;
   float* red = P + 4 * C4_H * NC;
@@ -173,6 +186,7 @@ __global__ __launch_bounds__(256) void colchain4_kernel(ColP p) {
     }
     PE_SCHED_FENCE();
     if constexpr (!FRONT) fetch_gw();
+    if constexpr (!FRONT) PE_STAMP(3, 2);
 #pragma unroll
     for (int k = 0; k < NVT; ++k) YT[col * KS1 + rl + 64 * k] = xin[k];
   }
@@ -263,12 +277,17 @@ __global__ __launch_bounds__(256) void colchain4_kernel(ColP p) {
 // lngemm_kernel on 4-column workgroups: norm_layers_2 of an encoder layer fused with the 1x1 conv that consumes it
 // (attentions.py:73-74, 60-69; models.py:207); grid.z = 192-row parts of the GEMM, every part normalises its 4 columns
 // itself, part 0 writes LN(y) back for the residual readers.
-__global__ __launch_bounds__(256) void lngemm4_kernel(LnGemmP p) {
+// Kernel entry: as colchain4_kernel (13 dwords of leading parameters, nx = gridDim.x).
+__global__ __launch_bounds__(256) void lngemm4_kernel(const int* lens, int nx, int xcd, const float* in, long in_bs, int in_cs,
+                                                      int rows, const float* parts, int nparts, LnGemmP p) {
   PE_KTRACE(7);
   constexpr int NC = 4, NVT = 3, H = C4_H, KS = Col4W<H>::KS;
   PE_DYN_SMEM(float, sm);                       // YT[4][KS] | P[4 waves][192][4] | red[2][4][4]
-  const int b = blockIdx.y, L = p.lens[b];
-  const int t0 = c4_tile(blockIdx.x, gridDim.x, p.xcd) * NC;
+  p.lens = lens; p.xcd = xcd; p.in = in; p.in_bs = in_bs; p.in_cs = in_cs; p.rows = rows; p.parts = parts; p.nparts = nparts;
+  const int b = blockIdx.y;
+  int L = PE_UNIFORM(lens[b]);                              // decides whether the workgroup runs: part of the batch, one wait for both
+  PE_ENTRY_BATCH(L, p.gamma, p.beta, p.bias, p.pbias, p.p_bs, p.w16);
+  const int t0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
   if (t0 >= L) return;
   float* YT = sm;
   float* P = YT + NC * KS;

@@ -187,8 +187,19 @@ __device__ __forceinline__ void conv_mfma_body(const ConvP& p, const int bx, con
 #define PE_CONV_MFMA_BOUNDS(MT, NT, WN, GATE, HALO) \
   __launch_bounds__(256, (MT * NT == 1 ? ((HALO == 128 && WN == 4) ? 3 : 4) : ((GATE && MT * NT == 2) ? 3 : 2)))
 template <int WM, int WN, int MT, int NT, int KS, bool GATE, int HALO>
-__global__ PE_CONV_MFMA_BOUNDS(MT, NT, WN, GATE, HALO) void conv_mfma_kernel(ConvP p) {
+__global__ PE_CONV_MFMA_BOUNDS(MT, NT, WN, GATE, HALO) void conv_mfma_kernel(const int* lens, const float* x, long x_bs, int len_mul, int epi, int tpb,
+                                                                                int x_cs, int Cin, int padl, int ntaps, int nchunks, ConvP p) {
   PE_KTRACE(11);
+  // kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names (14 dwords); the
+  // length bounds the row descriptors of the first slab, so lens[b] is requested together with the rest of the struct
+  p.lens = lens; p.len_mul = len_mul; p.epi = epi; p.tpb = tpb; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl;
+  p.ntaps = ntaps; p.nchunks = nchunks;
+  // The body reads p.lens[b] itself (it is shared with the grouped kernel). Lr is the SAME load -- same pointer, same index,
+  // nothing in between that may write memory, so the compiler merges the two -- listed in the batch so that it is requested
+  // with the struct fields and shares their wait. If a compiler ever stops merging them the result stays right and the
+  // entry gets a second scalar wait, which scripts/entry_waits.py shows.
+  int Lr = PE_UNIFORM(lens[blockIdx.z]);
+  PE_ENTRY_BATCH(Lr, p.wp, p.in_slope, p.dil);
   conv_mfma_body<WM, WN, MT, NT, KS, GATE, HALO>(p, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 // Up to three INDEPENDENT convs of the same tile configuration in one launch (grid.z = conv x utterance): the sibling

@@ -268,10 +268,16 @@ __device__ __forceinline__ void conv_splitk_body(const ConvP& p, const int b, fl
   PE_STAMP(1, 4);
 }
 
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs
+// (14 dwords: what the x slab's and the first weight fragments' requests need).
 template <int MT, bool GATE, int NW, int D>
-__global__ __launch_bounds__(64 * NW) void conv_splitk_kernel(ConvP p) {
+__global__ __launch_bounds__(64 * NW) void conv_splitk_kernel(const int* lens, const float* x, long x_bs, int x_cs, int Cin, int padl,
+                                                              int ntaps, int nchunks, int tgroups, const float* wp, ConvP p) {
   PE_KTRACE(1);
   PE_DYN_SMEM(float, sm);
+  p.lens = lens; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl; p.ntaps = ntaps; p.nchunks = nchunks;
+  p.tgroups = tgroups; p.wp = wp;
+  PE_ENTRY_BATCH(p.len_mul, p.dil, p.in_slope);
   conv_splitk_body<MT, GATE, NW, D, 64>(p, blockIdx.z, sm);
 }
 
@@ -281,13 +287,17 @@ __global__ __launch_bounds__(64 * NW) void conv_splitk_kernel(ConvP p) {
 // Launch bounds ask for 4 workgroups per CU with the 64-column slab (<= 128 registers, 32 KB of LDS each): a group of
 // 3 x ~420 workgroups then runs as ~1.2 rounds over the chip instead of 1.6-2.5.
 template <int NW, int D, int XW>
-__global__ __launch_bounds__(64 * NW, XW == 64 ? 4 : 2) void conv_splitk_group_kernel(ConvG g) {
+__global__ __launch_bounds__(64 * NW, XW == 64 ? 4 : 2) void conv_splitk_group_kernel(int B, ConvG g) {
   PE_KTRACE(6);
   PE_DYN_SMEM(float, sm);
-  const int gi = PE_UNIFORM((int)blockIdx.z / g.B);
+  // kernel entry (pe_rt.h PE_ENTRY_BATCH): B = g.B arrives in an SGPR, so the sibling is known at once and what the body
+  // reads of it before its first loads is requested together
+  const int gi = PE_UNIFORM((int)blockIdx.z / B);
   const ConvP& p = g.c[gi];
+  int b = (int)blockIdx.z - gi * B;
+  PE_ENTRY_NEED(b, p.lens, p.len_mul, p.x, p.x_bs, p.x_cs, p.Cin, p.padl, p.ntaps, p.nchunks, p.tgroups, p.wp, p.dil, p.in_slope, p.rows);
   if ((int)blockIdx.y * 32 >= p.rows) return;              // a sibling with fewer row tiles than the grid
-  conv_splitk_body<1, false, NW, D, XW>(p, (int)blockIdx.z - gi * g.B, sm);
+  conv_splitk_body<1, false, NW, D, XW>(p, b, sm);
 }
 // The siblings' LAST convs, whose outputs the MRF sums: one GEMM over the concatenated K (MS form of the body), one
 // output tensor -- no per-sibling outputs, no summing pass.
@@ -297,6 +307,8 @@ template <int NW, int D>
 __global__ __launch_bounds__(64 * NW, 2) void conv_splitk_sum_kernel(ConvP p) {
   PE_KTRACE(8);
   PE_DYN_SMEM(float, sm);
+  // (this kernel keeps the plain by-value entry: its per-segment tables are looked up by a run-time index, so the struct
+  // has to stay in kernel-argument memory, and the lookups are dependent scalar reads whatever is requested in front of them)
   conv_splitk_body<1, false, NW, D, 128, true>(p, blockIdx.z, sm);
 }
 
@@ -311,9 +323,14 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_splitk_sum_kernel(ConvP p) {
 // GT (gate only): 16-row sub-tiles per workgroup -- 4 = a whole 32-channel group (tanh a, tanh b, sigmoid a, sigmoid b), 2 =
 // half of one (tanh h, sigmoid h; blockIdx.y = 2 * group + h): twice the workgroups with half the matrix time each, for
 // launches whose workgroups fit the chip either way (one utterance through the WN gate conv: 162 -> 324).
+// Kernel entry: as conv_splitk_kernel (wp16 in place of wp).
 template <bool GATE, int NW, int D, int GT = 4>
-__global__ __launch_bounds__(64 * NW) void conv_splitk16_kernel(ConvP p) {
+__global__ __launch_bounds__(64 * NW) void conv_splitk16_kernel(const int* lens, const float* x, long x_bs, int x_cs, int Cin, int padl,
+                                                                int ntaps_, int nchunks_, int tgroups, const float* wp16, ConvP p) {
   PE_KTRACE(4);
+  p.lens = lens; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl; p.ntaps = ntaps_; p.nchunks = nchunks_;
+  p.tgroups = tgroups; p.wp16 = wp16;
+  PE_ENTRY_BATCH(p.len_mul, p.dil, p.in_slope);
   constexpr int BN = 16, XW = 64, KS8 = KC / 4, MT16 = GATE ? GT : 2;
   constexpr int TSTR = (GATE && GT == 2) ? 2 : 1;             // sub-tile stride of a workgroup's tiles in the packed order
   constexpr int NSLOT = GATE ? 2 * GT : MT16 * 4;             // result slots per lane position (gate: tanh/sigmoid pairs)

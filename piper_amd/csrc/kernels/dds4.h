@@ -23,13 +23,21 @@ namespace pe {
 // Weights: engine_pack.cpp pack4 -- [64-row tile][k quad = K/4][lane][4]: lane l <-> row 64 * tile + l, element j <-> input
 // channel 4 * quad + j. Each workgroup streams the layer's 147 KB of weights from L2, so the form is for small calls
 // only (engine_launch.cpp: Engine::dds; 4x the workgroups of the 16-column form read 4x the weight bytes).
-__global__ __launch_bounds__(256) void dds_layer4_kernel(DdsP p) {
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs
+// (13 dwords); nx = gridDim.x. lens[b] and z_scale[3 b] are needed late: they are requested behind the batch's wait, just
+// ahead of the operand loads, and nothing waits for them before those loads are out (profiles/kernel_entry.md).
+// Tuning build: stamps 0 entry, 1 operand loads and weight fragments requested, 2 length known.
+__global__ __launch_bounds__(256) void dds_layer4_kernel(const int* lens, const float* z_scale, int nx, int xcd, const float* x,
+                                                         long x_bs, int x_cs, int dw_k, int dw_dil, DdsP p) {
   PE_KTRACE(2);
   PE_DYN_SMEM(float, sm);                       // YT[4][KS] | P[4 waves][192][4] | red[2][4][4] | ZL[64][4]
   constexpr int NC = 4, NVT = 3, H = C4_H, C4_KS = Col4W<C4_H>::KS;
+  PE_STAMP(2, 0);
+  p.lens = lens; p.z_scale = z_scale; p.xcd = xcd; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.dw_k = dw_k; p.dw_dil = dw_dil;
+  PE_ENTRY_BATCH(p.dw_w, p.dw_b, p.g1, p.b1, p.pre_z, p.pre_z_bs, p.pre_w, p.pre_b, p.wp4);
   const int b = blockIdx.y;
   const int L = p.lens[b];                      // first used after every operand load is in flight (dds.h)
-  const int t0 = c4_tile(blockIdx.x, gridDim.x, p.xcd) * NC;
+  const int t0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
   const int Lb = p.x_cs;
   float* YT = sm;
   float* P = YT + NC * C4_KS;
@@ -86,8 +94,10 @@ __global__ __launch_bounds__(256) void dds_layer4_kernel(DdsP p) {
     }
     PE_SCHED_FENCE();
     col_gemm4_fetch<C4_H>(gw, p.wp4, C4_NT, wv, lane);
+    PE_STAMP(2, 1);
     // first use of the length
     if (t0 >= L) return;
+    PE_STAMP(2, 2);
 #pragma unroll
     for (int kk = 0; kk < MAXK; ++kk) {
       const int tt = t + kk * p.dw_dil - pad;

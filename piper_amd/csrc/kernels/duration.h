@@ -88,8 +88,11 @@ __global__ void randn_kernel(float* out, long rows, int cols, long stride, long 
 // ids, integer results, so every workgroup gets the same table -- and workgroup (0, 0, b) publishes them (dur, cum,
 // logw, the frame counts for the host and for the kernels behind this one): one launch instead of three at the only
 // data-dependent point of the pipeline. `cum` lives in LDS, so the four 7-step searches never leave the CU.
-__global__ __launch_bounds__(256) void regulate_kernel(RegP p) {
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs.
+__global__ __launch_bounds__(256) void regulate_kernel(unsigned* absmax, const int* tlens, const unsigned long long* rng, int gen,
+                                                       int C, int fold, RegP p) {
   PE_KTRACE(16);
+  p.absmax = absmax; p.tlens = tlens; p.rng = rng; p.gen = gen; p.C = C; p.fold = fold;
   __shared__ int scum[REG_MAXT];
   __shared__ long long part[256];
   __shared__ int sF;

@@ -32,15 +32,19 @@ namespace pe {
 // hidden channel 48 slice + 4 (4Q + j) + k.
 constexpr int FFN_SL = 48, FFN_H = 192, FFN_NC = 16, FFN_NO = 12, FFN_XS = 48;      // slice rows, channels, MFMA columns, output columns per tile, LDS row stride (== 16 mod 32)
 
-__global__ __launch_bounds__(256) void ffn_kernel(FfnP p) {
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): everything in front of the first loads arrives in SGPRs (12 dwords); the leading
+// parameters repeat p's fields of the same names, (nx, ny) = gridDim.
+__global__ __launch_bounds__(256) void ffn_kernel(const int* lens, int xcd, int nx, int ny, const float* x, long x_bs, int x_cs,
+                                                  const float* w1p, FfnP p) {
   PE_KTRACE(9);
   PE_DYN_SMEM(float, sm);                         // XS[192][48] | PA[4][48][16] | HS[48][48]
+  p.lens = lens; p.xcd = xcd; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.w1p = w1p;
   float* XS = sm;
   float* PA = XS + FFN_H * FFN_XS;
   float* HS = PA + 4 * FFN_SL * FFN_NC;
   // (column tile, slice), slice-major over the XCDs: an XCD's workgroups share one or two slices' weights (pe_rt.h)
   int bx = blockIdx.x, by = blockIdx.y;
-  pe_xcd_xy(p.xcd, bx, by);
+  pe_xcd_xy(p.xcd, nx, ny, bx, by);
   const int b = blockIdx.z, s = PE_UNIFORM(by);
   const int o0 = PE_UNIFORM(bx) * FFN_NO;             // first output column of the tile; hidden columns o0 - 1 .. o0 + 14, x columns o0 - 2 .. o0 + 15
                                                   // (outputs o0 .. o0 + 11 are kept)

@@ -19,9 +19,14 @@ namespace pe {
 //   * the twelve partial tiles meet in LDS in wave order (deterministic), then bias + speaker bias + tanh * sigmoid.
 // Weights: engine_pack.cpp pack_gate4 -- [group][tap][k quad 48][lane][4].
 constexpr int G4_NC = 12, G4_WC = 16, G4_NW = 12, G4_K = 192, G4_XS = G4_K + 4;
-__global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(ConvP p) {
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): everything in front of the loads arrives in SGPRs (13 dwords); the leading
+// parameters repeat p's fields of the same names.
+__global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int len_mul, const float* x, long x_bs, int x_cs,
+                                                           int Cin, int padl, int ntaps_, const float* wpg4, ConvP p) {
   PE_KTRACE(4);
   PE_DYN_SMEM(float, sm);                         // XT[16][196] | P[12 waves][64][12]
+  p.lens = lens; p.len_mul = len_mul; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl; p.ntaps = ntaps_;
+  p.wpg4 = wpg4;
   float* XT = sm;
   float* P = XT + G4_WC * G4_XS;
   const int b = blockIdx.z, grp = blockIdx.y;

@@ -25,7 +25,9 @@ void init_front() {
 #endif
 }
 
-void embed(dim3 grid, hipStream_t stream, const EmbedP& p) { PE_LAUNCH(embed_kernel, grid, dim3(64), 0, stream, p); }
+void embed(dim3 grid, hipStream_t stream, const EmbedP& p) {
+  PE_LAUNCH(embed_kernel, grid, dim3(64), 0, stream, p);
+}
 
 // compiled per head width (96 / 48); <0> = any even width <= 128 with guarded loops
 void attention(int dk, dim3 grid, size_t smem, hipStream_t stream, const AttnP& p) {
@@ -45,8 +47,8 @@ void attno(dim3 grid, size_t smem, hipStream_t stream, const AttnOP& p) {
 }
 
 void attn4(bool long_rows, dim3 grid, size_t smem, hipStream_t stream, const AttnOP& p) {
-  if (long_rows) PE_LAUNCH((attn4_kernel<96, true>), grid, dim3(256), smem, stream, p);
-  else PE_LAUNCH((attn4_kernel<96, false>), grid, dim3(256), smem, stream, p);
+  if (long_rows) PE_LAUNCH((attn4_kernel<96, true>), grid, dim3(256), smem, stream, p.lens, p.qkv, p.q_bs, p.kT, p.kt_bs, (int)grid.x, p.xcd, p.q_cs, p.window, p);
+  else PE_LAUNCH((attn4_kernel<96, false>), grid, dim3(256), smem, stream, p.lens, p.qkv, p.q_bs, p.kT, p.kt_bs, (int)grid.x, p.xcd, p.q_cs, p.window, p);
 }
 
 void layer_norm(dim3 grid, hipStream_t stream, const LnP& p) { PE_LAUNCH(ln_kernel, grid, dim3(256), 0, stream, p); }
@@ -59,7 +61,7 @@ void dds_layer(int nchunks, dim3 grid, size_t smem, hipStream_t stream, const Dd
 }
 
 void dds_layer4(dim3 grid, size_t smem, hipStream_t stream, const DdsP& p) {
-  PE_LAUNCH(dds_layer4_kernel, grid, dim3(256), smem, stream, p);
+  PE_LAUNCH(dds_layer4_kernel, grid, dim3(256), smem, stream, p.lens, p.z_scale, (int)grid.x, p.xcd, p.x, p.x_bs, p.x_cs, p.dw_k, p.dw_dil, p);
 }
 
 void colchain(dim3 grid, size_t smem, hipStream_t stream, const ColP& p) {
@@ -71,16 +73,16 @@ void lngemm(dim3 grid, size_t smem, hipStream_t stream, const LnGemmP& p) {
 }
 
 void colchain4(dim3 grid, size_t smem, hipStream_t stream, const ColP& p) {
-  if (p.w0) PE_LAUNCH(colchain4_kernel<true>, grid, dim3(256), smem, stream, p);
-  else PE_LAUNCH(colchain4_kernel<false>, grid, dim3(256), smem, stream, p);
+  if (p.w0) PE_LAUNCH(colchain4_kernel<true>, grid, dim3(256), smem, stream, p.lens, p.in1, p.in1_bs, (int)grid.x, p.xcd, p.mode, p.in1_cs, p.K1, p.rows1, p.first, p.out_cs, p);
+  else PE_LAUNCH(colchain4_kernel<false>, grid, dim3(256), smem, stream, p.lens, p.in1, p.in1_bs, (int)grid.x, p.xcd, p.mode, p.in1_cs, p.K1, p.rows1, p.first, p.out_cs, p);
 }
 
 void lngemm4(dim3 grid, size_t smem, hipStream_t stream, const LnGemmP& p) {
-  PE_LAUNCH(lngemm4_kernel, grid, dim3(256), smem, stream, p);
+  PE_LAUNCH(lngemm4_kernel, grid, dim3(256), smem, stream, p.lens, (int)grid.x, p.xcd, p.in, p.in_bs, p.in_cs, p.rows, p.parts, p.nparts, p);
 }
 
 void ffn(dim3 grid, size_t smem, hipStream_t stream, const FfnP& p) {
-  PE_LAUNCH(ffn_kernel, grid, dim3(256), smem, stream, p);
+  PE_LAUNCH(ffn_kernel, grid, dim3(256), smem, stream, p.lens, p.xcd, (int)grid.x, (int)grid.y, p.x, p.x_bs, p.x_cs, p.w1p, p);
 }
 
 void xcc_probe(hipStream_t stream, int* out64) { PE_LAUNCH(xcc_probe_kernel, dim3(64), dim3(64), 0, stream, out64); }
@@ -106,7 +108,9 @@ void randn(hipStream_t stream, float* out, long rows, int cols, long stride, lon
   PE_LAUNCH(randn_kernel, dim3(randn_blocks(rows, cols)), dim3(256), 0, stream, out, rows, cols, stride, row0, state, site);
 }
 
-void regulate(dim3 grid, hipStream_t stream, const RegP& p) { PE_LAUNCH(regulate_kernel, grid, dim3(256), 0, stream, p); }
+void regulate(dim3 grid, hipStream_t stream, const RegP& p) {
+  PE_LAUNCH(regulate_kernel, grid, dim3(256), 0, stream, p.absmax, p.tlens, p.rng, p.gen, p.C, p.fold, p);
+}
 
 void cond(dim3 grid, hipStream_t stream, const float* emb_g, int gin, const int* sids, const float* w, const float* bias,
           int rows, float* out, int o_bs) {

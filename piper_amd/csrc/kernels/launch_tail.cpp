@@ -21,7 +21,9 @@ void init_tail() {
 // groups, 2 halo units per wave); ou = output units per wave (N = 16 * column groups * ou)
 void mrf(int cp, int ou, dim3 grid, hipStream_t stream, const MrfP& p) {
   const size_t smem = mrf_smem_bytes(cp, ou);
-#define PE_MRF(CP_, OU_, HU_) PE_LAUNCH((mrf_kernel<CP_, OU_, HU_>), grid, dim3(64 * MRF_NW), smem, stream, p)
+#define PE_MRF(CP_, OU_, HU_) \
+  PE_LAUNCH((mrf_kernel<CP_, OU_, HU_>), grid, dim3(64 * MRF_NW), smem, stream, p.lens, p.wstream, p.phases, p.x, p.len_mul, p.stride, p.n0off, p.hxa, \
+            p.wfloats, p.nphases, p)
   if (cp == 32) {
     if (ou == 1) PE_MRF(32, 1, 1); else if (ou == 2) PE_MRF(32, 2, 1); else if (ou == 3) PE_MRF(32, 3, 1); else PE_MRF(32, 4, 1);
   } else {
@@ -42,7 +44,7 @@ void conv_post(dim3 grid, hipStream_t stream, const float* x, long x_bs, int x_c
 
 void pcm16(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const unsigned* absmax, const int* lens,
            int len_mul, short* pcm, long p_bs, short* host) {
-  PE_LAUNCH(pcm16_kernel, grid, dim3(256), 0, stream, audio, a_bs, absmax, lens, len_mul, pcm, p_bs, host);
+  PE_LAUNCH(pcm16_kernel, grid, dim3(PCM16_TPB), 0, stream, lens, len_mul, absmax, audio, a_bs, pcm, p_bs, host);
 }
 
 void window_copy(dim3 grid, hipStream_t stream, const float* z, int zs, const int* win, float* out, int ws, int C) {

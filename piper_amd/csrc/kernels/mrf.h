@@ -61,16 +61,24 @@ __device__ __forceinline__ void mrf_interleave() {
 #endif
 template <int CP, int OU, int HU> struct MRF_HALF_B { static constexpr bool value = PE_MRF_HALF == 2 || (PE_MRF_HALF == 1 && OU + HU >= 5); };
 
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs
+// (14 dwords). The length decides whether the workgroup runs at all and bounds the window's row descriptors, so its
+// pointer comes first: lens[b] is requested together with the rest of the struct and both are waited for once.
 template <int CP, int OU, int HU>
-__global__ __launch_bounds__(64 * MRF_NW) void mrf_kernel(MrfP p) {
+__global__ __launch_bounds__(64 * MRF_NW) void mrf_kernel(const int* lens, const float* wstream, const MrfPhase* phases, const float* x, int len_mul,
+                                                          int stride, int n0off, int hxa, int wfloats, int nphases, MrfP p) {
   PE_KTRACE(20);
+  p.lens = lens; p.len_mul = len_mul; p.stride = stride; p.n0off = n0off; p.hxa = hxa; p.wstream = wstream; p.wfloats = wfloats;
+  p.phases = phases; p.nphases = nphases; p.x = x;
+  int Lr = PE_UNIFORM(lens[blockIdx.y]);                    // part of the batch: one wait for the struct and the length
+  PE_ENTRY_BATCH(Lr, p.x_bs, p.x_cs, p.slope, p.C, p.wcols);
   constexpr int NW = MRF_NW, WS = mrf_ws(CP, OU), MS = CP / 16, MSW = 2, NRG = MS / MSW, NCG = NW / NRG, NT = 64 * NW;
   constexpr int UPW = OU + HU, NCH = CP / KC, STEPF = MS * 512;
   static_assert(MS % MSW == 0 && NW % NRG == 0, "waves split evenly over the row groups");
   static_assert(WS % 32 == 16, "row stride == 16 (mod 32): the two k rows of a half-wave hit disjoint banks");
   PE_DYN_SMEM(float, sm);
   const int b = blockIdx.y;
-  const int L = p.lens[b] * p.len_mul;
+  const int L = Lr * p.len_mul;
   if (blockIdx.x * p.stride >= L) return;
   const int n0 = blockIdx.x * p.stride - p.n0off;     // first column of the window's N output columns (fused tail: -3 + ...)
   // LDS: [pad][buffer 0: CP x WS][buffer 1][pad][phase table]. Reads of never-used columns may leave a buffer on the

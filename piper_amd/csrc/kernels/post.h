@@ -80,11 +80,14 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* x, long x_b
 
 // float -> int16 exactly as piper.cpp:420-431 (scale 32767/max(0.01,peak), clamp, truncate)
 // `host`: pinned host memory that also receives the samples, utterances packed back to back (zero-copy delivery), or null
-__global__ void pcm16_kernel(const float* audio, long a_bs, const unsigned* absmax, const int* lens,
-                             int len_mul, short* pcm, long p_bs, short* host) {
+// Kernel entry: the parameters arrive in SGPRs in the order the kernel needs them (the two data-dependent scalars' pointers
+// first), and the block size is a constant instead of the hidden blockDim argument.
+constexpr int PCM16_TPB = 256;
+__global__ __launch_bounds__(PCM16_TPB) void pcm16_kernel(const int* lens, int len_mul, const unsigned* absmax, const float* audio,
+                                                          long a_bs, short* pcm, long p_bs, short* host) {
   PE_KTRACE(18);
   const int b = blockIdx.y, L = lens[b] * len_mul;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t = blockIdx.x * PCM16_TPB + threadIdx.x;
   if (t >= L) return;
   const float peak = fmaxf(0.01f, __uint_as_float(absmax[b]));
   const float scale = 32767.0f / peak;

@@ -19,6 +19,8 @@ namespace pe { inline const char* g_emu_kernel = ""; }   // the kernel the emula
 #define PE_OPAQUE(x) ((void)0)
 #define PE_UNIFORM(x) (emu::uniform_check((long long)(x)), (x))     // checked: readfirstlane on the GPU
 #define PE_SCHED_FENCE() ((void)0)
+#define PE_ENTRY_BATCH(...) ((void)0)
+#define PE_ENTRY_NEED(anchor, ...) ((void)0)
 #define PE_SCHED_GROUP(mask, n) ((void)0)
 template <class T> inline T* pe_uniform_ptr(T* p) { return p; }
 // bounds-checked row load: element idx of a row of n floats, 0 outside [0, n)
@@ -145,6 +147,56 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // nothing is scheduled across this point: keeps a block of prefetch loads ahead of the MFMAs they overlap
 // with (the machine scheduler otherwise sinks each load next to its use to save registers)
 #define PE_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+// Kernel entry. The scalar cache is cold at every kernel start, so each wait for kernel arguments is one scalar-memory
+// round trip in front of the first vector loads, and the compiler requests a large by-value struct piecemeal: a group of
+// fields, a wait, the next group behind a branch, another wait. The small kernels therefore take the fields their first
+// loads need as LEADING SCALAR PARAMETERS (those arrive in SGPRs at wave launch: -amdgpu-kernarg-preload-count, Makefile;
+// at most 14 dwords) and copy them over the struct's fields, and name whatever else they read before the first vector
+// load here: every listed field (a wave-uniform lvalue) sits in an SGPR at this point, so all of them are requested
+// together and waited for ONCE. A kernel that needs lens[b] before its first loads reads it in front of the batch and lists
+// it as an operand (one wait for both: colchain4, lngemm4, mrf, conv_mfma); a kernel that needs it late leaves it out: the
+// compiler then requests it somewhere behind the batch's wait, and no wait stands between that and the operand loads.
+// Nothing but the assembly guarantees this placement -- a compiler may schedule the loads otherwise: scripts/entry_waits.py
+// is the check; tests/test_kernel_entry.py runs it for the front unit, profiles/kernel_entry.md holds its output for all three.
+#define PE_EB_1(C, a) C(a)
+#define PE_EB_2(C, a, ...) C(a), PE_EB_1(C, __VA_ARGS__)
+#define PE_EB_3(C, a, ...) C(a), PE_EB_2(C, __VA_ARGS__)
+#define PE_EB_4(C, a, ...) C(a), PE_EB_3(C, __VA_ARGS__)
+#define PE_EB_5(C, a, ...) C(a), PE_EB_4(C, __VA_ARGS__)
+#define PE_EB_6(C, a, ...) C(a), PE_EB_5(C, __VA_ARGS__)
+#define PE_EB_7(C, a, ...) C(a), PE_EB_6(C, __VA_ARGS__)
+#define PE_EB_8(C, a, ...) C(a), PE_EB_7(C, __VA_ARGS__)
+#define PE_EB_9(C, a, ...) C(a), PE_EB_8(C, __VA_ARGS__)
+#define PE_EB_10(C, a, ...) C(a), PE_EB_9(C, __VA_ARGS__)
+#define PE_EB_11(C, a, ...) C(a), PE_EB_10(C, __VA_ARGS__)
+#define PE_EB_12(C, a, ...) C(a), PE_EB_11(C, __VA_ARGS__)
+#define PE_EB_13(C, a, ...) C(a), PE_EB_12(C, __VA_ARGS__)
+#define PE_EB_14(C, a, ...) C(a), PE_EB_13(C, __VA_ARGS__)
+#define PE_EB_15(C, a, ...) C(a), PE_EB_14(C, __VA_ARGS__)
+#define PE_EB_16(C, a, ...) C(a), PE_EB_15(C, __VA_ARGS__)
+#define PE_EB_17(C, a, ...) C(a), PE_EB_16(C, __VA_ARGS__)
+#define PE_EB_18(C, a, ...) C(a), PE_EB_17(C, __VA_ARGS__)
+#define PE_EB_19(C, a, ...) C(a), PE_EB_18(C, __VA_ARGS__)
+#define PE_EB_20(C, a, ...) C(a), PE_EB_19(C, __VA_ARGS__)
+#define PE_EB_21(C, a, ...) C(a), PE_EB_20(C, __VA_ARGS__)
+#define PE_EB_22(C, a, ...) C(a), PE_EB_21(C, __VA_ARGS__)
+#define PE_EB_23(C, a, ...) C(a), PE_EB_22(C, __VA_ARGS__)
+#define PE_EB_24(C, a, ...) C(a), PE_EB_23(C, __VA_ARGS__)
+#define PE_EB_25(C, a, ...) C(a), PE_EB_24(C, __VA_ARGS__)
+#define PE_EB_26(C, a, ...) C(a), PE_EB_25(C, __VA_ARGS__)
+#define PE_EB_PICK(a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12, a13, a14, a15, a16, a17, a18, a19, a20, a21, a22, a23, a24, a25, a26, N, ...) N
+#define PE_EB_OPS(C, ...) \
+  PE_EB_PICK(__VA_ARGS__, PE_EB_26, PE_EB_25, PE_EB_24, PE_EB_23, PE_EB_22, PE_EB_21, PE_EB_20, PE_EB_19, PE_EB_18, \
+             PE_EB_17, PE_EB_16, PE_EB_15, PE_EB_14, PE_EB_13, PE_EB_12, PE_EB_11, PE_EB_10, PE_EB_9, \
+             PE_EB_8, PE_EB_7, PE_EB_6, PE_EB_5, PE_EB_4, PE_EB_3, PE_EB_2, PE_EB_1)(C, __VA_ARGS__)
+// (more than 26 operands do not compile: PE_EB_PICK then picks an operand instead of a list macro.)
+// The asm is NOT volatile and has no memory clobber: it is kept because its outputs are used, and it must not count as a
+// possible store -- behind an instruction that may write memory the compiler no longer proves a uniform load from global
+// memory (lens[b]) unclobbered and issues it as a vector load with a wait of its own.
+#define PE_ENTRY_BATCH(...) asm("" : PE_EB_OPS("+s", __VA_ARGS__))
+// the same for values that are only read (fields of a struct that stays in kernel-argument memory, reached by reference);
+// `anchor` = a wave-uniform int lvalue that everything behind this point depends on (the utterance index), which keeps the asm alive
+#define PE_ENTRY_NEED(anchor, ...) asm("" : "+s"(anchor) : PE_EB_OPS("s", __VA_ARGS__))
 // the next `n` instructions of class `mask` (LLVM SchedGroupMask: MFMA 0x8, VMEM read 0x20, DS read 0x100) of the
 // enclosing scheduling region, in the order these calls appear: a compile-time interleave of loads between MFMAs
 #define PE_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier((mask), (n), 0)
@@ -221,10 +273,11 @@ __device__ __forceinline__ int pe_xcd_tile(int id, int n, int P) {
 // moment cost more than eight L2s fetching them once each), and a column tile-major order for the tiled conv kernel
 // (+1 % at one utterance, +0.5 % / +6.5 % on the medium / high voice at 64). The planes of a 3-D grid are mapped one by
 // one: within a plane a residue class still sits on ONE XCD.
-__device__ __forceinline__ void pe_xcd_xy(int P, int& bx, int& by) {
+// (nx, ny) = the grid's x and y sizes, passed by the launcher: gridDim is a hidden kernel argument in a cache line of
+// its own, one more scalar round trip at kernel entry.
+__device__ __forceinline__ void pe_xcd_xy(int P, int nx, int ny, int& bx, int& by) {
   if (P <= 1) return;
-  const int nx = (int)gridDim.x;
-  const int t = pe_xcd_tile(by * nx + bx, nx * (int)gridDim.y, P);
+  const int t = pe_xcd_tile(by * nx + bx, nx * ny, P);
   by = t / nx;
   bx = t - by * nx;
 }
