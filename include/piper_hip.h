@@ -215,6 +215,39 @@ int pe_get_info(pe_engine* e, int32_t* sample_rate, int32_t* hop, int32_t* n_spe
 int pe_set_output_rate(pe_engine* e, int32_t native_rate, int32_t output_rate);
 int pe_get_output_rate(pe_engine* e, int32_t* native_rate, int32_t* output_rate, int32_t* half_width);
 
+/* The int16 level of stream chunks. By default every chunk of pe_stream_next, pe_stream_next_batch and pe_stream_pool_next is
+ * scaled by 32767 / max(0.01, its own peak), as the reference's streaming script does (infer_onnx_streaming.py:122): the
+ * level a listener hears moves at every chunk boundary, and a chunk that holds a pause is amplified by up to 100. Two
+ * stream-wide levels stand beside that rule, computed on the device between the chunk's peak and its conversion, with no host
+ * round trip. One stream = one pe_stream_begin utterance, one row of a batch stream, or one pool slot from join to its end.
+ * x[0 .. n) are the floats a chunk delivers for the stream (output samples when a rate is set; they never change), c = max |x|.
+ *   PE_GAIN_CHUNK    the default rule, bit for bit: g = 32767 / max(0.01, c); launches, graphs and buffers as without this call.
+ *   PE_GAIN_FIXED    g = 32767 / max(0.01, peak) for every sample of every chunk; no state. peak must be finite and > 0.
+ *   PE_GAIN_RUNNING  the stream carries an f32 running peak r = max(0.01, peak) at begin / join (peak 0: no prior; finite,
+ *                    >= 0). A chunk with n > 0: r' = max(r, c), g1 = 32767 / r', g0 = g1 on the stream's first delivered
+ *                    chunk and 32767 / r otherwise; with R = min(ramp_samples, n), sample i < R is scaled by
+ *                    g1 + (g0 - g1) * ((R - 1 - i) / R) and every later one by g1 (the last ramp sample carries exactly
+ *                    g1); then r = r'. A chunk with n == 0 delivers nothing and leaves r alone.
+ * Products are clamped to [-32768, 32767] and truncated as before. r never falls within a stream, so the gain never rises; a
+ * sample can reach the clamp only inside a ramp that contains the new peak (there the gain is still above 32767 / r'). Once
+ * the chunk with the utterance's peak has passed, every later sample has the gain pe_synthesize gives it. A pool slot's
+ * level is reset by the join that takes it -- a reused slot inherits nothing -- survives every other call on the handle like
+ * the slot's latent, and a failed join changes nothing.
+ * ramp_samples: 0 .. 65536 delivered samples. peak and ramp_samples are data the kernels read; only the mode picks launches,
+ * and every mode's graphs stay cached, so a steady server stops capturing in any mode. Errors that change nothing: an unknown
+ * mode, a peak or ramp out of range, and any call while a stream, a batch stream or a stream pool slot is live / occupied.
+ * pe_get_stream_gain reads the setting back (any pointer may be NULL). */
+enum { PE_GAIN_CHUNK = 0, PE_GAIN_RUNNING = 1, PE_GAIN_FIXED = 2 };
+int pe_set_stream_gain(pe_engine* e, int32_t mode, float peak, int32_t ramp_samples);
+int pe_get_stream_gain(pe_engine* e, int32_t* mode, float* peak, int32_t* ramp_samples);
+/* The last chunk call on the handle, of any of the three kinds: *n rows (1, batch or slots); gain[r] is the end-of-chunk gain
+ * g1 of row r and peak[r] the level it came from -- r' when running, max(0.01, c) in the default mode, max(0.01, peak) when
+ * fixed. A row that delivered nothing reports its stored state when running and 0 otherwise. gain / peak may be NULL (then
+ * only *n is written); capacity < *n is an error. In the default mode a batch stream's or pool's peaks stay on the device and
+ * are fetched by this call: ask before the next call that uploads inputs, which is an error ("no longer on the device")
+ * afterwards. */
+int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacity, int32_t* n);
+
 /* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
  * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them
  * counts as zero. out[b][0 .. count[b]) receives outputs n0[b] .. n0[b] + count[b] - 1 of that utterance (out_stride floats

@@ -78,6 +78,7 @@ void Engine::free_all() {
   if (sb_dev_) hipFree(sb_dev_);
   if (sb_pcm_) hipHostFree(sb_pcm_);
   if (sb_audio_) hipHostFree(sb_audio_);
+  gain_blocks_free(&sb_gctl_, &sb_gdev_);
   sb_host_ = sb_dev_ = nullptr; sb_pcm_ = nullptr; sb_audio_ = nullptr;
   sb_cap_ = 0; sb_pcm_cap_ = sb_audio_cap_ = 0; sb_active_ = false;
   stream_pool_free();
@@ -355,6 +356,7 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   if (!scales) throw std::runtime_error("null scales");
   PE_HIP(hipSetDevice(device_));
   sb_active_ = false;               // new inputs end a batch stream: its latent and its window state go with them
+  lg_dev_peaks_ = nullptr;          // (the next resampling launch clears the peak words a default-mode report would read)
   B_ = B;
   id_off_.assign(offsets, offsets + B + 1);
   tlens_h_.resize(B);
@@ -512,6 +514,7 @@ void Engine::drop_graphs() {
 #endif
   graphs_.clear();
   graph_of_.clear();
+  lg_dev_peaks_ = nullptr;          // (whoever drops the graphs is about to move the blocks they point into)
 }
 
 // Shape buckets (engine.h). Steps of 32 ids up to 512, then 8 per octave; steps of 64 frames up to 1024, then 16 per octave.
@@ -788,6 +791,8 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
   s_frames_ = Fmax_;
   s_pos_ = 0;
   s_active_ = true;
+  s_gain_r_ = std::max(0.01f, gain_peak_);
+  s_gain_first_ = true;
   sample_off_.assign(2, 0);
   return s_frames_;
 }
@@ -795,6 +800,12 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
 bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** pcm, int64_t* nsamples) {
   EntryLock entry_lock;
   if (!s_active_ || s_pos_ >= s_frames_) {
+    if (s_active_) {                                     // nothing delivered: the stored level when running, else zeros
+      const bool run = gain_mode_ == GAIN_RUNNING;
+      lg_n_ = 1; lg_dev_peaks_ = nullptr; lg_lazy_ = false;
+      lg_gain_.assign(1, run ? 32767.0f / s_gain_r_ : 0.f);
+      lg_peak_.assign(1, run ? s_gain_r_ : 0.f);
+    }
     s_active_ = false;
     if (nsamples) *nsamples = 0;
     return false;
@@ -823,16 +834,35 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
   PE_HIP(hipMemcpyAsync(h_audio_, rs_on_ ? raudio_ : audio_ + (size_t)(f0 - a) * hop_, n * sizeof(float), hipMemcpyDeviceToHost,
                         stream_));
   PE_HIP(hipStreamSynchronize(stream_));
-  // per-chunk peak normalisation, as the reference's streaming script does (infer_onnx_streaming.py:122)
+  // per-chunk peak normalisation, as the reference's streaming script does (infer_onnx_streaming.py:122) -- or one of the
+  // stream-wide levels, in the f32 arithmetic of stream_gain_kernel and chunk_pcm_gain_kernel (kernels/post.h)
   float peak = 0.01f;
   for (size_t i = 0; i < n; ++i) peak = std::max(peak, std::fabs(h_audio_[i]));
-  const float sc = 32767.0f / peak;
+  float g0 = 32767.0f / peak, sc = g0, level = peak;
+  size_t R = 0;
+  if (gain_mode_ == GAIN_FIXED) {
+    level = std::max(0.01f, gain_peak_);
+    g0 = sc = 32767.0f / level;
+  } else if (gain_mode_ == GAIN_RUNNING) {
+    const float r = s_gain_first_ ? std::max(0.01f, gain_peak_) : s_gain_r_;
+    level = std::max(r, peak);                           // (r >= 0.01, so the floor inside `peak` changes nothing)
+    sc = 32767.0f / level;
+    g0 = s_gain_first_ ? sc : 32767.0f / r;
+    R = std::min<size_t>((size_t)gain_ramp_, n);
+    s_gain_r_ = level;
+    s_gain_first_ = false;
+  }
+  const float dg = g0 - sc, Rf = (float)std::max<size_t>(R, 1);
   s_pcm_.resize(n);
   for (size_t i = 0; i < n; ++i) {
-    float v = h_audio_[i] * sc;
+    const float g = i < R ? std::fmaf(dg, (float)(int)(R - 1 - i) / Rf, sc) : sc;
+    float v = h_audio_[i] * g;
     v = std::min(std::max(v, -32768.0f), 32767.0f);
     s_pcm_[i] = (int16_t)v;
   }
+  lg_n_ = 1; lg_dev_peaks_ = nullptr; lg_lazy_ = false;
+  lg_gain_.assign(1, sc);
+  lg_peak_.assign(1, level);
   s_pos_ = f1;
   if (audio) *audio = h_audio_;
   if (pcm) *pcm = s_pcm_.data();
@@ -853,6 +883,7 @@ void Engine::ensure_stream_batch(int B) {
   drop_graphs();                                       // the blocks' addresses are kernel arguments inside the 'V' graphs
   if (sb_host_) { PE_HIP(hipHostFree(sb_host_)); sb_host_ = nullptr; }
   if (sb_dev_) { PE_HIP(hipFree(sb_dev_)); sb_dev_ = nullptr; }
+  gain_blocks_free(&sb_gctl_, &sb_gdev_);               // (they are sized by sb_cap_: the next chunk outside the default mode allocates them)
   sb_cap_ = 0;
   const size_t bytes = (size_t)sb_words(want) * sizeof(int);
   PE_HIP(hipHostMalloc((void**)&sb_host_, bytes));
@@ -899,6 +930,7 @@ const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const
   ensure_stream_batch(B);
   stream_front(B, 0);
   sb_pos_.assign(B, 0);
+  sb_gfirst_.assign(B, 1);
   sb_off_.assign(B + 1, 0);
   sample_off_.assign(B + 1, 0);
   sb_active_ = true;
@@ -944,7 +976,10 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   out.frames_done = sb_pos_.data();
   out.pcm = sb_pcm_;
   out.audio = nullptr;
-  if (total == 0) return;                              // every utterance is finished
+  if (total == 0) {                                    // every utterance is finished
+    gain_report_idle(sb_gctl_, cap, B);
+    return;
+  }
   if ((size_t)total > sb_pcm_cap_) {
     if (sb_pcm_) { PE_HIP(hipHostFree(sb_pcm_)); sb_pcm_ = nullptr; sb_pcm_cap_ = 0; }
     PE_HIP(hipHostMalloc((void**)&sb_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
@@ -960,9 +995,18 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   s_wg_ = std::min(rup(c + 2 * hf, 32), Fs_);
   if (s_wg_ < wmax) s_wg_ = std::min(rup(wmax, 32), Fs_);
   char key[96];
-  snprintf(key, sizeof(key), "V|%d|%d|%d", B, s_wg_, Fs_);
+  if (gain_mode_ == GAIN_CHUNK) {
+    snprintf(key, sizeof(key), "V|%d|%d|%d", B, s_wg_, Fs_);
+  } else {
+    if (!sb_gctl_) gain_blocks_alloc(cap, &sb_gctl_, &sb_gdev_);
+    if ((int)sb_gfirst_.size() < B) sb_gfirst_.assign(B, 1);
+    gain_prepare(sb_gctl_, cap, sb_gfirst_, B);
+    snprintf(key, sizeof(key), "V|%d|%d|%d|g%d", B, s_wg_, Fs_, gain_mode_);
+  }
   run_stage('V', key);
   PE_HIP(hipStreamSynchronize(stream_));
+  gain_collect(sb_gctl_, cap, B, sb_gfirst_, sb_off_.data(),
+               rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(sb_dev_) + sb_o_peak(cap));
   for (int b = 0; b < B; ++b) sb_pos_[b] = std::min(frames_h_[b], sb_pos_[b] + c);
   out.pcm = sb_pcm_;
   out.audio = want_audio ? sb_audio_ : nullptr;
@@ -984,6 +1028,8 @@ void Engine::stream_pool_free() {
   if (sp_join_) hipHostFree(sp_join_);
   if (sp_pcm_) hipHostFree(sp_pcm_);
   if (sp_audio_) hipHostFree(sp_audio_);
+  gain_blocks_free(&sp_gctl_, &sp_gdev_);
+  lg_dev_peaks_ = nullptr;                               // (a default-mode report not yet fetched pointed into sp_dev_)
   sp_z_ = sp_cond_ = nullptr; sp_dev_ = sp_host_ = sp_join_ = nullptr; sp_pcm_ = nullptr; sp_audio_ = nullptr;
   sp_pcm_cap_ = sp_audio_cap_ = 0;
   sp_slots_ = sp_cap_ = sp_fcap_ = sp_maxf_ = 0;
@@ -1021,6 +1067,7 @@ int Engine::stream_pool_open(int slots, int max_frames) {
     PE_HIP(hipMemset(sp_dev_, 0, sbytes));
     memset(sp_host_, 0, sbytes);
     memset(sp_join_, 0, jbytes);
+    gain_blocks_alloc(cap, &sp_gctl_, &sp_gdev_);
     PE_HIP(hipDeviceSynchronize());
   } catch (...) {
     stream_pool_free();
@@ -1030,6 +1077,7 @@ int Engine::stream_pool_open(int slots, int max_frames) {
   sp_frames_.assign(slots, 0);
   sp_pos_.assign(slots, 0);
   sp_live_.assign(slots, 0);
+  sp_gfirst_.assign(slots, 1);
   sp_off_.assign(slots + 1, 0);
   return decoder_halo_frames();
 }
@@ -1107,6 +1155,7 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
     sp_frames_[s] = frames_h_[j];
     sp_pos_[s] = 0;
     sp_live_[s] = 1;
+    sp_gfirst_[s] = 1;                                   // its first chunk resets the slot's level: nothing of the last tenant's stays
     if (slot_of) slot_of[j] = s;
     if (total_frames) total_frames[j] = frames_h_[j];
   }
@@ -1158,7 +1207,10 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   out.frames_done = sp_pos_.data();
   out.pcm = sp_pcm_;
   out.audio = nullptr;
-  if (total == 0) return;                              // no slot has frames left
+  if (total == 0) {                                    // no slot has frames left
+    gain_report_idle(sp_gctl_, cap, S);
+    return;
+  }
   if ((size_t)total > sp_pcm_cap_) {
     if (sp_pcm_) { PE_HIP(hipHostFree(sp_pcm_)); sp_pcm_ = nullptr; sp_pcm_cap_ = 0; }
     PE_HIP(hipHostMalloc((void**)&sp_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
@@ -1181,15 +1233,131 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   sp_wg_ = std::min(rup(cmax + 2 * hf, 32), Fs_);
   if (sp_wg_ < wmax) sp_wg_ = std::min(rup(wmax, 32), Fs_);
   char key[96];
-  snprintf(key, sizeof(key), "P|%d|%d|%d", S, sp_wg_, Fs_);
+  if (gain_mode_ == GAIN_CHUNK) {
+    snprintf(key, sizeof(key), "P|%d|%d|%d", S, sp_wg_, Fs_);
+  } else {
+    gain_prepare(sp_gctl_, cap, sp_gfirst_, S);
+    snprintf(key, sizeof(key), "P|%d|%d|%d|g%d", S, sp_wg_, Fs_, gain_mode_);
+  }
   run_stage('P', key);
   PE_HIP(hipStreamSynchronize(stream_));
+  gain_collect(sp_gctl_, cap, S, sp_gfirst_, sp_off_.data(),
+               rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(sp_dev_) + sb_o_peak(cap));
   for (int s = 0; s < S; ++s) {
     sp_pos_[s] = f1s[s];
     if (sp_live_[s] && sp_pos_[s] >= sp_frames_[s]) sp_live_[s] = 0;      // free from the next call on
   }
   out.pcm = sp_pcm_;
   out.audio = want_audio ? sp_audio_ : nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// stream-wide gain
+// ------------------------------------------------------------------------------------------------
+
+void Engine::set_stream_gain(int mode, float peak, int ramp_samples) {
+  EntryLock entry_lock;
+  if (mode != GAIN_CHUNK && mode != GAIN_RUNNING && mode != GAIN_FIXED)
+    throw std::runtime_error("unknown stream gain mode " + std::to_string(mode) + " (0 chunk, 1 running, 2 fixed)");
+  if (!std::isfinite(peak)) throw std::runtime_error("stream gain peak is not finite");
+  if (peak < 0.f) throw std::runtime_error("stream gain peak must not be negative");
+  if (mode == GAIN_FIXED && !(peak > 0.f)) throw std::runtime_error("a fixed stream gain needs a peak > 0");
+  if (ramp_samples < 0 || ramp_samples > GAIN_MAX_RAMP)
+    throw std::runtime_error("stream gain ramp_samples outside [0, " + std::to_string(GAIN_MAX_RAMP) + "]");
+  bool live = s_active_ && s_pos_ < s_frames_;
+  if (sb_active_)
+    for (int b = 0; b < B_ && b < (int)sb_pos_.size(); ++b) live = live || sb_pos_[b] < frames_h_[b];
+  bool pool = false;
+  for (int s = 0; s < sp_slots_; ++s) pool = pool || sp_live_[s] != 0;
+  if (live || pool)
+    throw std::runtime_error(std::string("the stream gain cannot change while a ") +
+                             (pool ? "stream pool slot is occupied" : "stream is live") + " on this handle");
+  // peak and ramp are data the kernels read from the control block; the mode picks the launches and is part of the window
+  // stages' graph keys, so nothing is dropped here: every mode's graphs stay cached side by side
+  gain_mode_ = mode; gain_peak_ = peak; gain_ramp_ = ramp_samples;
+}
+
+int Engine::stream_last_gains(float* gain, float* peak, int64_t capacity) {
+  EntryLock entry_lock;
+  if (lg_n_ < 0) throw std::runtime_error("no stream chunk delivered on this handle yet");
+  if ((gain || peak) && capacity < lg_n_) throw std::runtime_error("stream gains buffer too small");
+  if (lg_lazy_) {                                        // default mode, batch stream or pool: the peaks stayed on the device
+    if (!lg_dev_peaks_)
+      throw std::runtime_error("the last chunk's peaks are no longer on the device (another call ran since): ask right after the chunk");
+    PE_HIP(hipSetDevice(device_));
+    std::vector<unsigned> w((size_t)lg_n_);
+    PE_HIP(hipMemcpy(w.data(), lg_dev_peaks_, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int b = 0; b < lg_n_; ++b) {
+      float c;
+      memcpy(&c, &w[b], sizeof(float));
+      const float level = std::max(0.01f, c);
+      lg_peak_[b] = lg_got_[b] ? level : 0.f;
+      lg_gain_[b] = lg_got_[b] ? 32767.0f / level : 0.f;
+    }
+    lg_dev_peaks_ = nullptr;
+    lg_lazy_ = false;
+  }
+  for (int b = 0; b < lg_n_; ++b) {
+    if (gain) gain[b] = lg_gain_[b];
+    if (peak) peak[b] = lg_peak_[b];
+  }
+  return lg_n_;
+}
+
+void Engine::gain_blocks_alloc(int cap, int** ctl, int** dev) {
+  const size_t cbytes = (size_t)sg_words(cap) * sizeof(int), dbytes = (size_t)sgd_words(cap) * sizeof(int);
+  PE_HIP(hipHostMalloc((void**)ctl, cbytes));
+  memset(*ctl, 0, cbytes);
+  PE_HIP(hipMalloc((void**)dev, dbytes));
+  PE_HIP(hipMemset(*dev, 0, dbytes));
+  PE_HIP(hipDeviceSynchronize());
+}
+
+void Engine::gain_blocks_free(int** ctl, int** dev) {
+  if (*ctl) hipHostFree(*ctl);
+  if (*dev) hipFree(*dev);
+  *ctl = *dev = nullptr;
+}
+
+// The previous chunk ended with a synchronisation: nothing on the device reads or writes the control block any more.
+void Engine::gain_prepare(int* ctl, int cap, const std::vector<char>& first, int n) {
+  memcpy(ctl, &gain_peak_, sizeof(float));
+  ctl[1] = gain_ramp_;
+  for (int b = 0; b < n && b < cap; ++b) ctl[sg_o_first(cap) + b] = first[b] ? 1 : 0;
+}
+
+void Engine::gain_collect(const int* ctl, int cap, int n, std::vector<char>& first, const int64_t* off, const unsigned* peaks) {
+  lg_n_ = n;
+  lg_got_.resize(n);
+  for (int b = 0; b < n; ++b) lg_got_[b] = off[b + 1] > off[b];
+  if (gain_mode_ == GAIN_CHUNK) {
+    lg_gain_.assign(n, 0.f);
+    lg_peak_.assign(n, 0.f);
+    lg_dev_peaks_ = peaks;
+    lg_lazy_ = true;
+    return;
+  }
+  lg_dev_peaks_ = nullptr;
+  lg_lazy_ = false;
+  const float* cf = reinterpret_cast<const float*>(ctl);
+  lg_gain_.assign(cf + sg_o_rgain(cap), cf + sg_o_rgain(cap) + n);
+  lg_peak_.assign(cf + sg_o_rpeak(cap), cf + sg_o_rpeak(cap) + n);
+  for (int b = 0; b < n; ++b)
+    if (lg_got_[b]) first[b] = 0;
+}
+
+void Engine::gain_report_idle(const int* ctl, int cap, int n) {
+  lg_n_ = n;
+  lg_dev_peaks_ = nullptr;
+  lg_lazy_ = false;
+  lg_got_.assign(n, 0);
+  lg_gain_.assign(n, 0.f);
+  lg_peak_.assign(n, 0.f);
+  if (gain_mode_ != GAIN_RUNNING || !ctl) return;
+  // running: the report words still hold every row's stored state (the chunk that delivered a row's last samples wrote
+  // its final level; a row that delivered nothing since wrote its stored one)
+  const float* cf = reinterpret_cast<const float*>(ctl);
+  for (int b = 0; b < n && b < cap; ++b) { lg_gain_[b] = cf[sg_o_rgain(cap) + b]; lg_peak_[b] = cf[sg_o_rpeak(cap) + b]; }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -113,6 +113,21 @@ class Engine {
   void debug_resample(const float* x, int batch, int64_t stride, const int32_t* vlen, const int64_t* n0, const int32_t* count,
                       const int64_t* origin, float* out, int64_t out_stride);
 
+  // The int16 level of stream chunks (kernels/params.h: GAIN_*). GAIN_CHUNK, the default, is the
+  // reference's rule: every chunk scaled by 32767 / max(0.01, its own peak). GAIN_FIXED: 32767 / max(0.01, peak) for every
+  // sample. GAIN_RUNNING: every stream -- the one-utterance stream, a batch-stream row, a pool slot -- carries a running
+  // peak r that starts at max(0.01, peak) and only grows: a chunk with peak c is scaled by 32767 / max(r, c), reached from
+  // the previous chunk's gain over the chunk's first ramp_samples samples. The delivered floats are not touched. Throws,
+  // and changes nothing, for an unknown mode, a peak that is not finite (or < 0; fixed: <= 0), a ramp outside [0, 65536],
+  // or while a stream, a batch stream or a pool with an occupied slot is live. peak and ramp are data; the mode is part
+  // of the window stage's graph key.
+  void set_stream_gain(int mode, float peak, int ramp_samples);
+  int stream_gain_mode() const { return gain_mode_; }
+  float stream_gain_peak() const { return gain_peak_; }
+  int stream_gain_ramp() const { return gain_ramp_; }
+  // end-of-chunk gain and the level it came from, per row of the last chunk call of any kind; returns the rows
+  int stream_last_gains(float* gain, float* peak, int64_t capacity);
+
   // Streaming decode of a whole BATCH in lock step: stream_begin_batch is upload (one scales triple per utterance) + text
   // encoder + durations + flow for B utterances, once; the latent stays resident. Every stream_next_batch decodes the
   // next `chunk_frames` frames of every utterance that has frames left as ONE batched generator pass on exact-halo
@@ -488,12 +503,35 @@ class Engine {
   int16_t* sb_pcm_ = nullptr; float* sb_audio_ = nullptr;     // pinned host output of the current chunk
   size_t sb_pcm_cap_ = 0, sb_audio_cap_ = 0;
   void ensure_stream_batch(int B);
+  // stream-wide gain. The setting; the one-utterance stream's state (its conversion runs on the host); per batch stream and
+  // per pool a pinned control block and a device gain block (params.h: sg_*, sgd_*) at the state blocks' capacity -- the
+  // batch stream's allocated with its first chunk outside the default mode and freed with sb_dev_, the pool's allocated by
+  // stream_pool_open and freed by close, neither inside a workspace -- and the host's "nothing delivered yet" flags.
+  int gain_mode_ = GAIN_CHUNK, gain_ramp_ = 0;
+  float gain_peak_ = 0.f;
+  float s_gain_r_ = 0.01f; bool s_gain_first_ = true;
+  int* sb_gctl_ = nullptr; int* sb_gdev_ = nullptr;
+  int* sp_gctl_ = nullptr; int* sp_gdev_ = nullptr;
+  std::vector<char> sb_gfirst_, sp_gfirst_;
+  void gain_blocks_alloc(int cap, int** ctl, int** dev);
+  void gain_blocks_free(int** ctl, int** dev);
+  void gain_prepare(int* ctl, int cap, const std::vector<char>& first, int n);
+  // after a chunk call over n rows with sample offsets off[n + 1]: the report, and the flags of the rows that delivered.
+  // Default mode: the peaks stay on the device (`peaks`, one word per row) and are fetched when the report is asked for.
+  void gain_collect(const int* ctl, int cap, int n, std::vector<char>& first, const int64_t* off, const unsigned* peaks);
+  void gain_report_idle(const int* ctl, int cap, int n);   // a chunk call that ran nothing: stored state / zeros
+  std::vector<float> lg_gain_, lg_peak_;
+  std::vector<char> lg_got_;
+  int lg_n_ = -1;                                          // rows of the last chunk call (-1: none yet)
+  const unsigned* lg_dev_peaks_ = nullptr;                 // default mode: where the last chunk's peaks are, until other work runs
+  bool lg_lazy_ = false;                                   // the report is still to be fetched from there
   void issue_window_batch();
   // text encoder, durations and flow of the uploaded batch, the latent left in zp_ (front half of both batch streams);
   // max_frames > 0: an utterance with more frames is an error, raised before stage B is sized for it
   void stream_front(int B, int max_frames);
   // the window stage on B utterances: gather from `src` by the pinned state block `hst`, generator, chunk delivery
-  void issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg);
+  void issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg,
+                          int* gctl, int* gdev);
   // stream pool (see above). Resident: the latent [slots][C][sp_fcap_], the decoder conditioning rows [slots][cond_dec
   // rows] (multi-speaker voices), state blocks of its own in the sb_* layout at cap = sp_cap_ (slots rounded up to even),
   // the pinned join block (params.h: sj_*) and the pinned chunk output. All of them are allocations of their own: workspace

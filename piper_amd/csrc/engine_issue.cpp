@@ -436,7 +436,7 @@ void Engine::issue_resample(int B, const float* x, long x_bs, const int* hst, co
 // batch streaming: every utterance's window of z -> window buffer (the dead prior-noise buffer) -> generator on the
 // published window lengths -> per-chunk peak and int16 / float delivery into pinned host memory. One linear chain.
 void Engine::issue_window_batch() {
-  issue_window_stage(B_, sb_cap_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, s_wg_);
+  issue_window_stage(B_, sb_cap_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, s_wg_, sb_gctl_, sb_gdev_);
 }
 
 // stream pool: the same stage over all slots, reading the pool's resident rows and conditioning by the pool's state blocks.
@@ -449,10 +449,15 @@ void Engine::issue_window_pool() {
   B_ = sp_slots_;
   dec_cond_ = sp_cond_;
   dec_cond_bs_ = cond_dec_.rows;
-  issue_window_stage(sp_slots_, sp_cap_, sp_z_, (long)C_ * sp_fcap_, sp_fcap_, sp_host_, sp_dev_, sp_wg_);
+  issue_window_stage(sp_slots_, sp_cap_, sp_z_, (long)C_ * sp_fcap_, sp_fcap_, sp_host_, sp_dev_, sp_wg_, sp_gctl_, sp_gdev_);
 }
 
-void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg) {
+// gctl / gdev: the stream's gain blocks (params.h: sg_*, sgd_*), used in the modes running and fixed only -- one more launch
+// between the chunk's peak and its conversion; the default mode issues exactly the launches it always did.
+void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg,
+                                int* gctl, int* gdev) {
+  const int gm = gain_mode_;
+  if (gm != GAIN_CHUNK && (!gctl || !gdev || B > cap)) throw std::runtime_error("stream gain blocks are not sized for this call");
   PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * wg,
                launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, src, src_bs, src_cs, hst, dst, cap,
                                      noise_z_, (long)C_ * Fs_, Fs_, wg));
@@ -473,12 +478,26 @@ void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, i
     const long max_out = out_samples((long)wg * hop_) + 1;
     issue_resample(B, audio_, Ss_, rs_host_, nullptr, max_out, (double)B * wg * hop_);
     const int rsteps = std::max(1, (int)((max_out + CHUNK_SPB - 1) / CHUNK_SPB));
+    if (gm != GAIN_CHUNK) {
+      PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, rs_dev_, rs_cap_, So_));
+      PE_LAUNCH_KB("chunk_pcm_rs_gain_kernel", 10.0 * B * (double)max_out,
+                   launch::chunk_pcm_rs_gain(dim3(rsteps, B), stream_, raudio_, So_, rs_dev_, rs_cap_, dst, cap, gdev));
+      return;
+    }
     PE_LAUNCH_KB("chunk_pcm_rs_kernel", 10.0 * B * (double)max_out,
                  launch::chunk_pcm_rs(dim3(rsteps, B), stream_, raudio_, So_, rs_dev_, rs_cap_, dst, cap));
     return;
   }
   const int steps = std::max(1, (int)(((long)wg * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
-  PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
+  // (a fixed level needs no peak)
+  if (gm != GAIN_FIXED)
+    PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
+  if (gm != GAIN_CHUNK) {
+    PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, nullptr, 0, 0));
+    PE_LAUNCH_KB("chunk_pcm_gain_kernel", 10.0 * B * wg * hop_,
+                 launch::chunk_pcm_gain(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_, gdev));
+    return;
+  }
   PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * wg * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
 }
 

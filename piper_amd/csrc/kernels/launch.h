@@ -79,6 +79,12 @@ void window_gather(dim3 grid, hipStream_t stream, const float* z, long z_bs, int
 // ... and the chunk delivery: grid = (steps of CHUNK_SPB samples, utterances), peak first, conversion second
 void chunk_peak(dim3 grid, hipStream_t stream, const float* audio, long a_bs, int* st, int cap, int hop);
 void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop);
+// stream-wide gain (params.h: sg_*, sgd_*): one thread per row between the peak and the conversion; rows null: the chunk's
+// range and peak from the window state block `st`, else from the resampling row block. chunk_pcm_gain / chunk_pcm_rs_gain =
+// the conversions with the operands stream_gain wrote to `gq`
+void stream_gain(hipStream_t stream, int* ctl, int* gb, int cap, int B, int mode, const int* st, int hop, const int* rows,
+                 int rcap, long y_cap);
+void chunk_pcm_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop, const int* gq);
 // stream pool (params.h: sj_*): grid = (64-frame tiles of the newcomers' frame bucket, channels, newcomers)
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
                   int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots);
@@ -88,6 +94,8 @@ void resample_rows(hipStream_t stream, const int* hst, const int* lens, int len_
                    long y_cap, int L, int M);
 void resample(dim3 grid, hipStream_t stream, const RsP& p);
 void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap);
+void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
+                       const int* gq);
 
 }  // namespace launch
 }  // namespace pe

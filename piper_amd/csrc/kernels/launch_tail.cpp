@@ -64,6 +64,15 @@ void chunk_pcm(dim3 grid, hipStream_t stream, const float* audio, long a_bs, con
   PE_LAUNCH(chunk_pcm_kernel, grid, dim3(256), 0, stream, audio, a_bs, st, cap, hop);
 }
 
+void chunk_pcm_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* st, int cap, int hop, const int* gq) {
+  PE_LAUNCH(chunk_pcm_gain_kernel, grid, dim3(256), 0, stream, audio, a_bs, st, cap, hop, gq);
+}
+
+void stream_gain(hipStream_t stream, int* ctl, int* gb, int cap, int B, int mode, const int* st, int hop, const int* rows,
+                 int rcap, long y_cap) {
+  PE_LAUNCH(stream_gain_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, ctl, gb, cap, B, mode, st, hop, rows, rcap, y_cap);
+}
+
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
                   int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots) {
   PE_LAUNCH(stream_adopt_kernel, grid, dim3(64), 0, stream, z, z_bs, zs, cond, cond_bs, cond_rows, join, cap, pool, p_bs, ps,
@@ -81,6 +90,11 @@ void resample(dim3 grid, hipStream_t stream, const RsP& p) {
 
 void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap) {
   PE_LAUNCH(chunk_pcm_rs_kernel, grid, dim3(256), 0, stream, y, y_bs, rows, rcap, st, cap);
+}
+
+void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
+                       const int* gq) {
+  PE_LAUNCH(chunk_pcm_rs_gain_kernel, grid, dim3(256), 0, stream, y, y_bs, rows, rcap, st, cap, gq);
 }
 
 }  // namespace launch

@@ -245,6 +245,26 @@ static constexpr int sb_o_peak(int cap) { return 6 * cap + 4; }
 static constexpr int sb_words(int cap) { return 7 * cap + 4; }
 static constexpr int CHUNK_SPB = 1024;         // samples one workgroup of the delivery kernels covers per step
 
+// ---- stream-wide gain (post.h: stream_gain_kernel, chunk_pcm_gain_kernel; resample.h: chunk_pcm_rs_gain_kernel)
+// The int16 level of a stream outside the default per-chunk rule. The setting's numbers are DATA like the window state: a
+// pinned host control block for `cap` rows that the host fills before each chunk and stream_gain_kernel reads in place,
+// and into which the kernel writes what pe_stream_last_gains reports; the running peaks and the conversion's operands
+// live in a device block.
+//   control (pinned host)  P (float bits), R0, first[cap] (1: the row's stream has delivered nothing yet: its state is
+//                          reset to P), report gain[cap] (g1), report peak[cap] (the level g1 came from)
+//   gain (device)          r[cap] running peak (f32), then for the conversion g0[cap], g1[cap] (f32) and R[cap] (ramp
+//                          samples of this chunk: min(R0, chunk length))
+enum { GAIN_CHUNK = 0, GAIN_RUNNING = 1, GAIN_FIXED = 2 };
+static constexpr int GAIN_MAX_RAMP = 65536;
+static constexpr int sg_o_first(int cap) { (void)cap; return 2; }
+static constexpr int sg_o_rgain(int cap) { return 2 + cap; }
+static constexpr int sg_o_rpeak(int cap) { return 2 + 2 * cap; }
+static constexpr int sg_words(int cap) { return 2 + 3 * cap; }
+static constexpr int sgd_o_g0(int cap) { return cap; }
+static constexpr int sgd_o_g1(int cap) { return 2 * cap; }
+static constexpr int sgd_o_ramp(int cap) { return 3 * cap; }
+static constexpr int sgd_words(int cap) { return 4 * cap; }
+
 // ---- stream pool (post.h: stream_adopt_kernel). The join block, pinned host memory for `cap` newcomers that the kernel
 // reads in place: which slot every newcomer of a join takes and how many frames it has -- data, not kernel arguments.
 //   n, (pad)               newcomers of this join

@@ -178,8 +178,18 @@ __global__ __launch_bounds__(256) void chunk_peak_kernel(const float* audio, lon
 // 2. float -> int16 as pcm16_kernel, with the chunk's own peak (the reference's streaming script normalises every chunk
 //    by itself, infer_onnx_streaming.py:122), stored packed back to back into pinned host memory at the utterance's
 //    offset; the floats go next to them when the caller wants them.
-__global__ __launch_bounds__(256) void chunk_pcm_kernel(const float* audio, long a_bs, const int* st, int cap, int hop) {
-  PE_KTRACE(25);
+//    GAIN (chunk_pcm_gain_kernel, the stream-wide levels): the scale of sample i of the chunk is g1 behind the ramp and
+//    g1 + (g0 - g1) * ((R - 1 - i) / R) inside it (i < R), from the block stream_gain_kernel wrote (params.h: sgd_*). The
+//    default instantiation is the kernel as it was: nothing of the gain path is in it.
+template <bool GAIN>
+__device__ __forceinline__ float chunk_gain_at(float g1, float dg, int R, float Rf, long i) {
+  if constexpr (GAIN) {
+    if (i < R) return fmaf(dg, (float)(R - 1 - (int)i) / Rf, g1);
+  }
+  return g1;
+}
+template <bool GAIN>
+__device__ __forceinline__ void chunk_pcm_body(const float* audio, long a_bs, const int* st, int cap, int hop, const int* gq) {
   const int b = blockIdx.y;
   int first, count;
   chunk_range(st, cap, b, hop, first, count);
@@ -188,20 +198,95 @@ __global__ __launch_bounds__(256) void chunk_pcm_kernel(const float* audio, long
   const long off = reinterpret_cast<const long long*>(st + sb_o_off(cap))[b];
   short* pcm = reinterpret_cast<short* const*>(st + sb_o_ptrs(cap))[0] + off;
   float* fout = reinterpret_cast<float* const*>(st + sb_o_ptrs(cap))[1];
-  const float peak = fmaxf(0.01f, __uint_as_float(reinterpret_cast<const unsigned*>(st)[sb_o_peak(cap) + b]));
-  const float scale = 32767.0f / peak;
+  float scale, dg = 0.f, Rf = 1.f;
+  int R = 0;
+  if constexpr (GAIN) {
+    scale = __uint_as_float(reinterpret_cast<const unsigned*>(gq)[sgd_o_g1(cap) + b]);
+    dg = __uint_as_float(reinterpret_cast<const unsigned*>(gq)[sgd_o_g0(cap) + b]) - scale;
+    R = gq[sgd_o_ramp(cap) + b];
+    R = R < 0 ? 0 : (R > count ? count : R);
+    Rf = (float)(R > 0 ? R : 1);
+  } else {
+    const float peak = fmaxf(0.01f, __uint_as_float(reinterpret_cast<const unsigned*>(st)[sb_o_peak(cap) + b]));
+    scale = 32767.0f / peak;
+  }
   for (long base = (long)blockIdx.x * CHUNK_SPB; base < count; base += (long)gridDim.x * CHUNK_SPB)
 #pragma unroll
     for (int j = 0; j < CHUNK_SPB / 256; ++j) {
       const long i = base + j * 256 + threadIdx.x;
       if (i < count) {
         const float x = a[i];
-        float v = x * scale;
+        float v = x * chunk_gain_at<GAIN>(scale, dg, R, Rf, i);
         v = fminf(fmaxf(v, -32768.0f), 32767.0f);
         pcm[i] = (short)v;
         if (fout) fout[off + i] = x;
       }
     }
+}
+__global__ __launch_bounds__(256) void chunk_pcm_kernel(const float* audio, long a_bs, const int* st, int cap, int hop) {
+  PE_KTRACE(25);
+  chunk_pcm_body<false>(audio, a_bs, st, cap, hop, nullptr);
+}
+__global__ __launch_bounds__(256) void chunk_pcm_gain_kernel(const float* audio, long a_bs, const int* st, int cap, int hop,
+                                                             const int* gq) {
+  PE_KTRACE(30);
+  chunk_pcm_body<true>(audio, a_bs, st, cap, hop, gq);
+}
+
+// Stream-wide gain (pe_set_stream_gain, modes running and fixed), one thread per row, between the chunk's peak and its
+// conversion. Row b's chunk has n samples and peak c: of the window state block `st` at the native rate (chunk_range,
+// sb_o_peak), of the resampling row block `rows` when a rate is set (count cut to y_cap as the conversion cuts it). The
+// setting's numbers and the row's "nothing delivered yet" flag come from the pinned control block `ctl`, read in place;
+// the running peak r lives in the device block `gb` (params.h: sg_*, sgd_*).
+//   running: first -> r = max(0.01, P). n > 0: r' = max(r, c), g1 = 32767 / r', g0 = g1 on the first chunk, else 32767 / r;
+//            the chunk's ramp is R = min(R0, n) samples. n == 0: nothing moves. r never falls, so the gain never rises.
+//   fixed:   g0 = g1 = 32767 / max(0.01, P), no state.
+// {g0, g1, R} go to `gb` for the conversion, {g1, the level it came from} into the control block for pe_stream_last_gains
+// (rows with nothing delivered: the stored state when running, 0 when fixed). Every index is cut to its block.
+__global__ __launch_bounds__(64) void stream_gain_kernel(int* ctl, int* gb, int cap, int B, int mode, const int* st, int hop,
+                                                         const int* rows, int rcap, long y_cap) {
+  PE_KTRACE(29);
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || b >= cap) return;
+  int n = 0;
+  float c = 0.f;
+  if (rows) {
+    if (b >= rcap) return;
+    const long cnt = rows[rs_o_count(rcap) + b];
+    n = (int)(cnt < 0 ? 0 : (cnt > y_cap ? y_cap : cnt));
+    c = __uint_as_float(reinterpret_cast<const unsigned*>(rows)[rs_o_peak(rcap) + b]);
+  } else {
+    int first;
+    chunk_range(st, cap, b, hop, first, n);
+    c = __uint_as_float(reinterpret_cast<const unsigned*>(st)[sb_o_peak(cap) + b]);
+  }
+  const float P = __uint_as_float(reinterpret_cast<const unsigned*>(ctl)[0]);
+  int R0 = ctl[1];
+  R0 = R0 < 0 ? 0 : (R0 > GAIN_MAX_RAMP ? GAIN_MAX_RAMP : R0);
+  float* gf = reinterpret_cast<float*>(gb);
+  float* cf = reinterpret_cast<float*>(ctl);
+  float g0, g1, level;
+  int R = 0;
+  if (mode == GAIN_FIXED) {
+    level = fmaxf(0.01f, P);
+    g0 = g1 = 32767.0f / level;
+    cf[sg_o_rgain(cap) + b] = n > 0 ? g1 : 0.f;
+    cf[sg_o_rpeak(cap) + b] = n > 0 ? level : 0.f;
+  } else {
+    const bool first = ctl[sg_o_first(cap) + b] != 0;
+    float r = first ? fmaxf(0.01f, P) : gf[b];
+    if (!(r >= 0.01f)) r = 0.01f;                        // (a row that never began: the floor, not a division by zero)
+    level = n > 0 ? fmaxf(r, c) : r;
+    g1 = 32767.0f / level;
+    g0 = first ? g1 : 32767.0f / r;
+    R = R0 < n ? R0 : n;
+    gf[b] = level;
+    cf[sg_o_rgain(cap) + b] = g1;
+    cf[sg_o_rpeak(cap) + b] = level;
+  }
+  gf[sgd_o_g0(cap) + b] = g0;
+  gf[sgd_o_g1(cap) + b] = g1;
+  gb[sgd_o_ramp(cap) + b] = R;
 }
 
 // Stream pool (pe_stream_pool_join): the newcomers' latents move from the stage-B workspace, which the next upload

@@ -4,6 +4,7 @@
 #pragma once
 #include "../pe_rt.h"
 #include "params.h"
+#include "post.h"
 
 namespace pe {
 
@@ -114,9 +115,11 @@ __global__ __launch_bounds__(256) void resample_kernel(RsP p) {
 // Chunk delivery of a batch stream at a converted rate: chunk_pcm_kernel (post.h) on the resampled rows. The chunk is
 // y[b][0 .. count_b) of the row block, its peak the one resample_kernel folded; where it goes in the packed pinned host
 // output comes from the window state block `st` (params.h: sb_*), whose offsets the host wrote in output samples.
-__global__ __launch_bounds__(256) void chunk_pcm_rs_kernel(const float* y, long y_bs, const int* rows, int rcap, const int* st,
-                                                           int cap) {
-  PE_KTRACE(28);
+// GAIN (chunk_pcm_rs_gain_kernel): the stream-wide levels, as chunk_pcm_gain_kernel (post.h) -- the operands come from the
+// device gain block `gq` (params.h: sgd_*, at the window state's cap), the ramp counts in output samples.
+template <bool GAIN>
+__device__ __forceinline__ void chunk_pcm_rs_body(const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
+                                                  const int* gq) {
   const int b = blockIdx.y;
   int count = rows[rs_o_count(rcap) + b];
   count = count < 0 ? 0 : (count > y_bs ? (int)y_bs : count);
@@ -125,20 +128,40 @@ __global__ __launch_bounds__(256) void chunk_pcm_rs_kernel(const float* y, long 
   const long off = reinterpret_cast<const long long*>(st + sb_o_off(cap))[b];
   short* pcm = reinterpret_cast<short* const*>(st + sb_o_ptrs(cap))[0] + off;
   float* fout = reinterpret_cast<float* const*>(st + sb_o_ptrs(cap))[1];
-  const float peak = fmaxf(0.01f, __uint_as_float(reinterpret_cast<const unsigned*>(rows)[rs_o_peak(rcap) + b]));
-  const float scale = 32767.0f / peak;
+  float scale, dg = 0.f, Rf = 1.f;
+  int R = 0;
+  if constexpr (GAIN) {
+    scale = __uint_as_float(reinterpret_cast<const unsigned*>(gq)[sgd_o_g1(cap) + b]);
+    dg = __uint_as_float(reinterpret_cast<const unsigned*>(gq)[sgd_o_g0(cap) + b]) - scale;
+    R = gq[sgd_o_ramp(cap) + b];
+    R = R < 0 ? 0 : (R > count ? count : R);
+    Rf = (float)(R > 0 ? R : 1);
+  } else {
+    const float peak = fmaxf(0.01f, __uint_as_float(reinterpret_cast<const unsigned*>(rows)[rs_o_peak(rcap) + b]));
+    scale = 32767.0f / peak;
+  }
   for (long base = (long)blockIdx.x * CHUNK_SPB; base < count; base += (long)gridDim.x * CHUNK_SPB)
 #pragma unroll
     for (int j = 0; j < CHUNK_SPB / 256; ++j) {
       const long i = base + j * 256 + threadIdx.x;
       if (i < count) {
         const float x = a[i];
-        float v = x * scale;
+        float v = x * chunk_gain_at<GAIN>(scale, dg, R, Rf, i);
         v = fminf(fmaxf(v, -32768.0f), 32767.0f);
         pcm[i] = (short)v;
         if (fout) fout[off + i] = x;
       }
     }
+}
+__global__ __launch_bounds__(256) void chunk_pcm_rs_kernel(const float* y, long y_bs, const int* rows, int rcap, const int* st,
+                                                           int cap) {
+  PE_KTRACE(28);
+  chunk_pcm_rs_body<false>(y, y_bs, rows, rcap, st, cap, nullptr);
+}
+__global__ __launch_bounds__(256) void chunk_pcm_rs_gain_kernel(const float* y, long y_bs, const int* rows, int rcap,
+                                                                const int* st, int cap, const int* gq) {
+  PE_KTRACE(31);
+  chunk_pcm_rs_body<true>(y, y_bs, rows, rcap, st, cap, gq);
 }
 
 }  // namespace pe

@@ -386,6 +386,29 @@ int pe_get_output_rate(pe_engine* e, int32_t* native_rate, int32_t* output_rate,
   });
 }
 
+int pe_set_stream_gain(pe_engine* e, int32_t mode, float peak, int32_t ramp_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_stream_gain(mode, peak, ramp_samples);
+  });
+}
+
+int pe_get_stream_gain(pe_engine* e, int32_t* mode, float* peak, int32_t* ramp_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (mode) *mode = e->eng->stream_gain_mode();
+    if (peak) *peak = e->eng->stream_gain_peak();
+    if (ramp_samples) *ramp_samples = e->eng->stream_gain_ramp();
+  });
+}
+
+int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->stream_last_gains(gain, peak, capacity);
+  });
+}
+
 int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
                       const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
   return guard([&] {

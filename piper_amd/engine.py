@@ -219,7 +219,8 @@ class Engine:
     def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None):
         """Generator over (float_audio, int16_pcm) chunks of one utterance: encoder/flow once, then the
         vocoder on exact-halo windows of `chunk_frames` frames (reference default 45). Concatenating
-        the float chunks gives exactly the unchunked waveform; pcm is peak-normalised per chunk."""
+        the float chunks gives exactly the unchunked waveform; pcm is peak-normalised per chunk, or follows
+        the level set by ``set_stream_gain``."""
         ids_np = np.ascontiguousarray(ids, np.int64)
         sc = (C.c_float * 3)(*[float(s) for s in scales])
         keep: list = []
@@ -242,7 +243,8 @@ class Engine:
         """Generator over the chunks of B utterances streamed in lock step (pe_stream_begin_batch / pe_stream_next_batch):
         text encoder, durations and flow for the whole batch once, then one batched vocoder pass per chunk. Every item
         is a list of B ``(float chunk or None, int16 chunk)`` pairs -- empty arrays for utterances that are finished;
-        chunk k of utterance b is what ``stream`` yields for that utterance alone. ``chunk_frames``: an int, or a
+        chunk k of utterance b is what ``stream`` yields for that utterance alone, in every ``set_stream_gain`` mode (each
+        utterance carries its own level). ``chunk_frames``: an int, or a
         callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales`` as in
         ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
         B = len(id_lists)
@@ -298,6 +300,37 @@ class Engine:
         voice's header carries none (an .onnx: pass ``audio.sample_rate`` of its .onnx.json). ``rate`` None, 0 or the
         native rate: off. Sample counts are then in output samples; ``frames`` stays in native frames."""
         self._check(self._lib.pe_set_output_rate(self._h, int(native or 0), int(rate or 0)))
+
+    GAIN_MODES = ("chunk", "running", "fixed")
+
+    def set_stream_gain(self, mode: str = "chunk", peak: float = 0.0, ramp_ms: float = 5.0):
+        """The int16 level of the chunks of ``stream``, ``stream_batch`` and ``StreamPool`` (include/piper_hip.h:
+        pe_set_stream_gain). ``"chunk"``: every chunk normalised by its own peak, the default. ``"fixed"``: every sample
+        scaled by ``32767 / max(0.01, peak)``. ``"running"``: one gain per stream that follows the running maximum of the
+        chunk peaks (starting at ``peak``; 0 = no prior) and never rises, each change spread over the first ``ramp_ms``
+        milliseconds of the chunk that brings it. ``ramp_ms`` is converted to samples with the current ``output_rate``.
+        The float chunks are the same in every mode. Not while a stream is live."""
+        if mode not in self.GAIN_MODES:
+            raise ValueError(f"mode must be one of {self.GAIN_MODES}, got {mode!r}")
+        ramp = int(round(float(ramp_ms) * self.output_rate / 1000.0))
+        self._check(self._lib.pe_set_stream_gain(self._h, self.GAIN_MODES.index(mode), float(peak), ramp))
+
+    @property
+    def stream_gain(self):
+        """(mode, peak, ramp in samples) as set by ``set_stream_gain``."""
+        m, p, r = C.c_int32(), C.c_float(), C.c_int32()
+        self._check(self._lib.pe_get_stream_gain(self._h, C.byref(m), C.byref(p), C.byref(r)))
+        return self.GAIN_MODES[m.value], float(p.value), int(r.value)
+
+    def stream_last_gains(self):
+        """(gain, peak) float32 arrays of the last chunk call of any kind, one entry per utterance / slot: the gain at the
+        chunk's end and the level it came from (pe_stream_last_gains)."""
+        n = C.c_int32()
+        self._check(self._lib.pe_stream_last_gains(self._h, None, None, 0, C.byref(n)))
+        g, p = np.zeros(max(n.value, 1), np.float32), np.zeros(max(n.value, 1), np.float32)
+        self._check(self._lib.pe_stream_last_gains(self._h, g.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   p.ctypes.data_as(C.POINTER(C.c_float)), g.size, C.byref(n)))
+        return g[:n.value], p[:n.value]
 
     def _rates(self):
         nat, out, k = C.c_int32(), C.c_int32(), C.c_int32()
@@ -430,7 +463,8 @@ class StreamPool:
     resident in storage the pool owns, so every other call on the engine may run between two chunks. ``halo``: the
     generator's receptive half-width in frames. ``frames`` / ``frames_done``: per slot, the utterance's frame count and the
     frames delivered so far (a finished slot's stay readable until the slot is reused). ``free_slots``: the slots a join
-    may take, in the order it takes them."""
+    may take, in the order it takes them. The int16 level follows the engine's ``set_stream_gain``: in the running mode
+    every slot carries its own level, reset by the join that takes the slot."""
 
     def __init__(self, engine: Engine, slots: int, max_frames: int):
         self._eng, self.slots, self.max_frames, self._open = engine, int(slots), int(max_frames), False
