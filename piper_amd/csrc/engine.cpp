@@ -74,13 +74,8 @@ void Engine::free_all() {
   if (h_frames_) hipHostFree(h_frames_);
   if (h_in_) hipHostFree(h_in_);
   h_in_ = nullptr; h_in_cap_ = 0;
-  if (sb_host_) hipHostFree(sb_host_);
-  if (sb_dev_) hipFree(sb_dev_);
-  if (sb_pcm_) hipHostFree(sb_pcm_);
-  if (sb_audio_) hipHostFree(sb_audio_);
-  gain_blocks_free(&sb_gctl_, &sb_gdev_);
-  sb_host_ = sb_dev_ = nullptr; sb_pcm_ = nullptr; sb_audio_ = nullptr;
-  sb_cap_ = 0; sb_pcm_cap_ = sb_audio_cap_ = 0; sb_active_ = false;
+  rows_free(batch_rows_);
+  sb_active_ = false;
   stream_pool_free();
   rs_free();
   if (ev0_) hipEventDestroy(ev0_);
@@ -502,8 +497,8 @@ void Engine::dispatch_stage(char which) {
     case 'B': issue_stage_b(); break;
     case 'C': issue_stage_a(); issue_stage_b(); break;
     case 'F': issue_flow(); break;
-    case 'V': issue_window_batch(); break;
-    case 'P': issue_window_pool(); break;
+    case 'V': issue_window_rows(batch_rows_); break;
+    case 'P': issue_window_rows(pool_rows_); break;
     default: issue_window(); break;
   }
 }
@@ -713,19 +708,20 @@ bool Engine::finish_run() {
   return false;
 }
 
+// A pinned host buffer of at least n elements: grown with half as much again on top, its content not kept.
+template <typename T>
+static void grow_pinned(T*& p, size_t& cap, size_t n) {
+  if (n <= cap) return;
+  if (p) { PE_HIP(hipHostFree(p)); p = nullptr; cap = 0; }
+  PE_HIP(hipHostMalloc((void**)&p, (n + n / 2) * sizeof(T)));
+  cap = n + n / 2;
+}
+
 void Engine::download(bool want_audio, bool want_pcm) {
   EntryLock entry_lock;
   auto grow = [&](size_t total) {
-    if (want_audio && total > h_audio_cap_) {
-      if (h_audio_) PE_HIP(hipHostFree(h_audio_));
-      h_audio_cap_ = total + total / 2;
-      PE_HIP(hipHostMalloc((void**)&h_audio_, h_audio_cap_ * sizeof(float)));
-    }
-    if (want_pcm && total > h_pcm_cap_) {
-      if (h_pcm_) PE_HIP(hipHostFree(h_pcm_));
-      h_pcm_cap_ = total + total / 2;
-      PE_HIP(hipHostMalloc((void**)&h_pcm_, h_pcm_cap_ * sizeof(int16_t)));
-    }
+    if (want_audio) grow_pinned(h_audio_, h_audio_cap_, total);
+    if (want_pcm) grow_pinned(h_pcm_, h_pcm_cap_, total);
   };
   // pcm16_kernel already wrote the samples into pinned host memory (zero-copy), packed back to back: nothing to enqueue
   const bool zc = pol_.pcm_zc && h_pcm_zc_ != nullptr && h_pcm_zc_cap_ >= (size_t)B_ * (size_t)So_;
@@ -772,22 +768,7 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
   upload(ids, offs, 1, scales, sids, noise);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
-  Tg_ = std::min(id_bucket(Tmax_), Ts_);
-  char key[160];
-  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", 1, Tg_, Ts_, (int)have_noise_w_, Fs_);
-  run_stage('A', key);
-  ++call_;
-  PE_HIP(hipStreamSynchronize(stream_));
-  finish_stage_b_sizes();
-  ensure_stage_b(frame_bucket(Fmax_));
-  Fg_ = std::min(frame_bucket(Fmax_), Fs_);
-  lens_b_ = d_frames_;
-  if (have_noise_z_) {
-    issue_flow();
-  } else {
-    snprintf(key, sizeof(key), "F|%d|%d|%d|%d", 1, Fg_, Fs_, Ts_);
-    run_stage('F', key);
-  }
+  stream_front(1, 0);
   s_frames_ = Fmax_;
   s_pos_ = 0;
   s_active_ = true;
@@ -826,11 +807,7 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
   snprintf(key, sizeof(key), "W|%d|%d", s_wg_, Fs_);
   run_stage('W', key);
   const size_t n = (size_t)(o1 - o0);
-  if (n > h_audio_cap_) {
-    if (h_audio_) PE_HIP(hipHostFree(h_audio_));
-    h_audio_cap_ = n + n / 2;
-    PE_HIP(hipHostMalloc((void**)&h_audio_, h_audio_cap_ * sizeof(float)));
-  }
+  grow_pinned(h_audio_, h_audio_cap_, n);
   PE_HIP(hipMemcpyAsync(h_audio_, rs_on_ ? raudio_ : audio_ + (size_t)(f0 - a) * hop_, n * sizeof(float), hipMemcpyDeviceToHost,
                         stream_));
   PE_HIP(hipStreamSynchronize(stream_));
@@ -874,27 +851,36 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
 // batch streaming
 // ------------------------------------------------------------------------------------------------
 
-// The state blocks (kernels/params.h: sb_*), sized by the stage-A batch capacity so that they grow when that does -- which
-// drops every graph anyway -- and not from one batch to the next.
-void Engine::ensure_stream_batch(int B) {
-  const int want = (int)((std::max<size_t>(capA_B_, (size_t)B) + 1) & ~(size_t)1);
-  if (sb_host_ && sb_dev_ && sb_cap_ >= want) return;
-  PE_HIP(hipStreamSynchronize(stream_));
-  drop_graphs();                                       // the blocks' addresses are kernel arguments inside the 'V' graphs
-  if (sb_host_) { PE_HIP(hipHostFree(sb_host_)); sb_host_ = nullptr; }
-  if (sb_dev_) { PE_HIP(hipFree(sb_dev_)); sb_dev_ = nullptr; }
-  gain_blocks_free(&sb_gctl_, &sb_gdev_);               // (they are sized by sb_cap_: the next chunk outside the default mode allocates them)
-  sb_cap_ = 0;
-  const size_t bytes = (size_t)sb_words(want) * sizeof(int);
-  PE_HIP(hipHostMalloc((void**)&sb_host_, bytes));
-  PE_HIP(hipMalloc((void**)&sb_dev_, bytes));
-  memset(sb_host_, 0, bytes);
-  PE_HIP(hipMemset(sb_dev_, 0, bytes));
-  PE_HIP(hipDeviceSynchronize());
-  sb_cap_ = want;
+void Engine::rows_free(ChunkRows& r) {
+  if (r.host) hipHostFree(r.host);
+  if (r.dev) hipFree(r.dev);
+  if (r.pcm) hipHostFree(r.pcm);
+  if (r.audio) hipHostFree(r.audio);
+  gain_blocks_free(&r.gctl, &r.gdev);
+  lg_dev_peaks_ = nullptr;                               // (a default-mode report not yet fetched pointed into r.dev)
+  r.host = r.dev = nullptr; r.pcm = nullptr; r.audio = nullptr;
+  r.cap = 0; r.pcm_cap = r.audio_cap = 0;
 }
 
-// Front half of both batch streams, on the uploaded batch: text encoder and durations, the frame counts read back, the
+// The batch stream's blocks, sized by the stage-A batch capacity so that they grow when that does -- which drops every graph
+// anyway -- and not from one batch to the next.
+void Engine::ensure_stream_batch(int B) {
+  ChunkRows& r = batch_rows_;
+  const int want = (int)((std::max<size_t>(capA_B_, (size_t)B) + 1) & ~(size_t)1);
+  if (r.host && r.dev && r.cap >= want) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  drop_graphs();                                       // the blocks' addresses are kernel arguments inside the 'V' graphs
+  rows_free(r);                                        // (the gain blocks too: the next chunk outside the default mode allocates them)
+  const size_t bytes = (size_t)sb_words(want) * sizeof(int);
+  PE_HIP(hipHostMalloc((void**)&r.host, bytes));
+  PE_HIP(hipMalloc((void**)&r.dev, bytes));
+  memset(r.host, 0, bytes);
+  PE_HIP(hipMemset(r.dev, 0, bytes));
+  PE_HIP(hipDeviceSynchronize());
+  r.cap = want;
+}
+
+// Front half of every stream, on the uploaded batch: text encoder and durations, the frame counts read back, the
 // length regulator and the flow. The latent is left in zp_.
 void Engine::stream_front(int B, int max_frames) {
   Tg_ = std::min(id_bucket(Tmax_), Ts_);
@@ -929,9 +915,9 @@ const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
   ensure_stream_batch(B);
   stream_front(B, 0);
-  sb_pos_.assign(B, 0);
-  sb_gfirst_.assign(B, 1);
-  sb_off_.assign(B + 1, 0);
+  batch_rows_.pos.assign(B, 0);
+  batch_rows_.gfirst.assign(B, 1);
+  batch_rows_.off.assign(B + 1, 0);
   sample_off_.assign(B + 1, 0);
   sb_active_ = true;
   return frames_h_;
@@ -942,74 +928,81 @@ void Engine::stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& o
   if (!sb_active_) throw std::runtime_error("no batch stream begun on this handle (pe_stream_begin_batch)");
   if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
   PE_HIP(hipSetDevice(device_));
-  const int B = B_, cap = sb_cap_, c = std::min(chunk_frames, Fmax_), hf = decoder_halo_frames();
-  // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A finished
-  // utterance gets the one-frame window [0, 1) and no delivery range.
-  int* st = sb_host_;
+  ChunkRows& r = batch_rows_;
+  r.src = zp_; r.src_bs = (long)C_ * Fs_; r.src_cs = Fs_;      // (where the front half left the latent; conditioning: cond_)
+  rows_next(r, frames_h_.data(), nullptr, chunk_frames, nullptr, Fmax_, want_audio, out);
+}
+
+// One chunk of a row set. The previous chunk ended with a synchronisation: nothing on the device reads the pinned blocks
+// any more. A row with nothing to deliver -- finished, or not live -- gets the one-frame window [0, 1) of its own latent and
+// no delivery range.
+bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live, int chunk, const int32_t* per_row, int clamp,
+                       bool want_audio, StreamChunk& out) {
+  const int n = (int)r.pos.size(), cap = r.cap, hf = decoder_halo_frames();
+  int* st = r.host;
   long long* off = reinterpret_cast<long long*>(st + sb_o_off(cap));
-  int wmax = 1;
+  int wmax = 1, cmax = 1;
   int64_t total = 0;
-  for (int b = 0; b < B; ++b) {
-    const int F = frames_h_[b], f0 = sb_pos_[b], f1 = std::min(F, f0 + c);
+  for (int b = 0; b < n; ++b) {
+    const int F = frames[b], f0 = r.pos[b];
+    const int c = std::min(per_row && per_row[b] > 0 ? per_row[b] : chunk, clamp);
     int a = 0, e = 1, first = 0, count = 0;
     int64_t ocount = 0;
-    if (f0 < F) {
+    if ((!live || live[b]) && f0 < F) {
+      const int f1 = std::min(F, f0 + c);
       a = std::max(0, f0 - hf);
       e = std::min(F, f1 + hf);
       first = (f0 - a) * hop_;
       count = (f1 - f0) * hop_;
       ocount = out_samples((int64_t)f1 * hop_) - out_samples((int64_t)f0 * hop_);
+      cmax = std::max(cmax, c);
     }
     st[b] = a;
     st[sb_o_len(cap) + b] = e - a;
     st[sb_o_first(cap) + b] = first;
     st[sb_o_count(cap) + b] = count;
+    // (converted rate: the row of the resampling launch. The row block exists once the workspaces are sized, which the pool
+    // sees to before it comes here.)
     if (rs_on_) rs_host_row(b, out_samples((int64_t)f0 * hop_), (int64_t)a * hop_, (int)ocount, (e - a) * hop_);
     off[b] = (long long)total;
-    sb_off_[b] = total;
+    r.off[b] = total;
     total += ocount;
     wmax = std::max(wmax, e - a);
   }
-  sb_off_[B] = total;
-  out.batch = B;
-  out.sample_offsets = sb_off_.data();
-  out.frames_done = sb_pos_.data();
-  out.pcm = sb_pcm_;
+  r.off[n] = total;
+  out.batch = n;
+  out.sample_offsets = r.off.data();
+  out.frames_done = r.pos.data();
+  out.pcm = r.pcm;
   out.audio = nullptr;
-  if (total == 0) {                                    // every utterance is finished
-    gain_report_idle(sb_gctl_, cap, B);
-    return;
+  if (total == 0) {                                    // no row has frames left
+    gain_report_idle(r.gctl, cap, n);
+    return false;
   }
-  if ((size_t)total > sb_pcm_cap_) {
-    if (sb_pcm_) { PE_HIP(hipHostFree(sb_pcm_)); sb_pcm_ = nullptr; sb_pcm_cap_ = 0; }
-    PE_HIP(hipHostMalloc((void**)&sb_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
-    sb_pcm_cap_ = (size_t)total + (size_t)total / 2;
-  }
-  if (want_audio && (size_t)total > sb_audio_cap_) {
-    if (sb_audio_) { PE_HIP(hipHostFree(sb_audio_)); sb_audio_ = nullptr; sb_audio_cap_ = 0; }
-    PE_HIP(hipHostMalloc((void**)&sb_audio_, ((size_t)total + (size_t)total / 2) * sizeof(float)));
-    sb_audio_cap_ = (size_t)total + (size_t)total / 2;
-  }
-  void* ptrs[2] = {sb_pcm_, want_audio ? sb_audio_ : nullptr};
+  grow_pinned(r.pcm, r.pcm_cap, (size_t)total);
+  if (want_audio) grow_pinned(r.audio, r.audio_cap, (size_t)total);
+  void* ptrs[2] = {r.pcm, want_audio ? r.audio : nullptr};
   memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
-  s_wg_ = std::min(rup(c + 2 * hf, 32), Fs_);
-  if (s_wg_ < wmax) s_wg_ = std::min(rup(wmax, 32), Fs_);
+  // the window bucket: by the largest step among the rows that deliver
+  r.wg = std::min(rup(cmax + 2 * hf, 32), Fs_);
+  if (r.wg < wmax) r.wg = std::min(rup(wmax, 32), Fs_);
   char key[96];
   if (gain_mode_ == GAIN_CHUNK) {
-    snprintf(key, sizeof(key), "V|%d|%d|%d", B, s_wg_, Fs_);
+    snprintf(key, sizeof(key), "%c|%d|%d|%d", r.stage, n, r.wg, Fs_);
   } else {
-    if (!sb_gctl_) gain_blocks_alloc(cap, &sb_gctl_, &sb_gdev_);
-    if ((int)sb_gfirst_.size() < B) sb_gfirst_.assign(B, 1);
-    gain_prepare(sb_gctl_, cap, sb_gfirst_, B);
-    snprintf(key, sizeof(key), "V|%d|%d|%d|g%d", B, s_wg_, Fs_, gain_mode_);
+    if (!r.gctl) gain_blocks_alloc(cap, &r.gctl, &r.gdev);      // (the batch stream's: the pool's exist since open)
+    if ((int)r.gfirst.size() < n) r.gfirst.assign(n, 1);
+    gain_prepare(r.gctl, cap, r.gfirst, n);
+    snprintf(key, sizeof(key), "%c|%d|%d|%d|g%d", r.stage, n, r.wg, Fs_, gain_mode_);
   }
-  run_stage('V', key);
+  run_stage(r.stage, key);
   PE_HIP(hipStreamSynchronize(stream_));
-  gain_collect(sb_gctl_, cap, B, sb_gfirst_, sb_off_.data(),
-               rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(sb_dev_) + sb_o_peak(cap));
-  for (int b = 0; b < B; ++b) sb_pos_[b] = std::min(frames_h_[b], sb_pos_[b] + c);
-  out.pcm = sb_pcm_;
-  out.audio = want_audio ? sb_audio_ : nullptr;
+  gain_collect(r.gctl, cap, n, r.gfirst, r.off.data(),
+               rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(r.dev) + sb_o_peak(cap));
+  for (int b = 0; b < n; ++b) r.pos[b] += st[sb_o_count(cap) + b] / hop_;
+  out.pcm = r.pcm;
+  out.audio = want_audio ? r.audio : nullptr;
+  return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1023,16 +1016,10 @@ void Engine::stream_pool_require() const {
 void Engine::stream_pool_free() {
   if (sp_z_) hipFree(sp_z_);
   if (sp_cond_) hipFree(sp_cond_);
-  if (sp_dev_) hipFree(sp_dev_);
-  if (sp_host_) hipHostFree(sp_host_);
   if (sp_join_) hipHostFree(sp_join_);
-  if (sp_pcm_) hipHostFree(sp_pcm_);
-  if (sp_audio_) hipHostFree(sp_audio_);
-  gain_blocks_free(&sp_gctl_, &sp_gdev_);
-  lg_dev_peaks_ = nullptr;                               // (a default-mode report not yet fetched pointed into sp_dev_)
-  sp_z_ = sp_cond_ = nullptr; sp_dev_ = sp_host_ = sp_join_ = nullptr; sp_pcm_ = nullptr; sp_audio_ = nullptr;
-  sp_pcm_cap_ = sp_audio_cap_ = 0;
-  sp_slots_ = sp_cap_ = sp_fcap_ = sp_maxf_ = 0;
+  rows_free(pool_rows_);
+  sp_z_ = sp_cond_ = nullptr; sp_join_ = nullptr;
+  sp_slots_ = sp_fcap_ = sp_maxf_ = 0;
 }
 
 int Engine::stream_pool_open(int slots, int max_frames) {
@@ -1052,6 +1039,7 @@ int Engine::stream_pool_open(int slots, int max_frames) {
   const size_t zbytes = (size_t)slots * C_ * fcap * sizeof(float);
   const size_t cbytes = (size_t)slots * std::max(cond_dec_.rows, 1) * sizeof(float);
   const size_t sbytes = (size_t)sb_words(cap) * sizeof(int), jbytes = (size_t)sj_words(cap) * sizeof(int);
+  ChunkRows& r = pool_rows_;
   try {
     if (hipMalloc((void**)&sp_z_, zbytes) != hipSuccess) {
       (void)hipGetLastError();
@@ -1059,26 +1047,29 @@ int Engine::stream_pool_open(int slots, int max_frames) {
       throw std::runtime_error("out of device memory: " + std::to_string(zbytes >> 20) + " MiB of stream pool latents");
     }
     PE_HIP(hipMalloc((void**)&sp_cond_, cbytes));
-    PE_HIP(hipMalloc((void**)&sp_dev_, sbytes));
-    PE_HIP(hipHostMalloc((void**)&sp_host_, sbytes));
+    PE_HIP(hipMalloc((void**)&r.dev, sbytes));
+    PE_HIP(hipHostMalloc((void**)&r.host, sbytes));
     PE_HIP(hipHostMalloc((void**)&sp_join_, jbytes));
     PE_HIP(hipMemset(sp_z_, 0, zbytes));
     PE_HIP(hipMemset(sp_cond_, 0, cbytes));
-    PE_HIP(hipMemset(sp_dev_, 0, sbytes));
-    memset(sp_host_, 0, sbytes);
+    PE_HIP(hipMemset(r.dev, 0, sbytes));
+    memset(r.host, 0, sbytes);
     memset(sp_join_, 0, jbytes);
-    gain_blocks_alloc(cap, &sp_gctl_, &sp_gdev_);
+    gain_blocks_alloc(cap, &r.gctl, &r.gdev);
     PE_HIP(hipDeviceSynchronize());
   } catch (...) {
     stream_pool_free();
     throw;
   }
-  sp_slots_ = slots; sp_cap_ = cap; sp_fcap_ = fcap; sp_maxf_ = max_frames;
+  sp_slots_ = slots; sp_fcap_ = fcap; sp_maxf_ = max_frames;
   sp_frames_.assign(slots, 0);
-  sp_pos_.assign(slots, 0);
   sp_live_.assign(slots, 0);
-  sp_gfirst_.assign(slots, 1);
-  sp_off_.assign(slots + 1, 0);
+  r.cap = cap;
+  r.pos.assign(slots, 0);
+  r.gfirst.assign(slots, 1);
+  r.off.assign(slots + 1, 0);
+  r.src = sp_z_; r.src_bs = (long)C_ * fcap; r.src_cs = fcap;
+  r.cond = sp_cond_; r.cond_bs = cond_dec_.rows;
   return decoder_halo_frames();
 }
 
@@ -1103,7 +1094,7 @@ void Engine::stream_pool_close() {
 int Engine::stream_pool_state(int32_t* frames, int32_t* frames_done, int32_t* live) const {
   for (int s = 0; s < sp_slots_; ++s) {
     if (frames) frames[s] = sp_frames_[s];
-    if (frames_done) frames_done[s] = sp_pos_[s];
+    if (frames_done) frames_done[s] = pool_rows_.pos[s];
     if (live) live[s] = sp_live_[s];
   }
   return sp_slots_;
@@ -1138,7 +1129,7 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent)
   stream_front(n, sp_maxf_);
   // the previous join ended with a synchronisation: nothing on the device reads the pinned join block any more
-  const int cap = sp_cap_;
+  const int cap = pool_rows_.cap;
   sp_join_[0] = n;
   for (int j = 0; j < n; ++j) {
     sp_join_[sj_o_slot(cap) + j] = take[j];
@@ -1153,9 +1144,9 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
   for (int j = 0; j < n; ++j) {
     const int s = take[j];
     sp_frames_[s] = frames_h_[j];
-    sp_pos_[s] = 0;
+    pool_rows_.pos[s] = 0;
     sp_live_[s] = 1;
-    sp_gfirst_[s] = 1;                                   // its first chunk resets the slot's level: nothing of the last tenant's stays
+    pool_rows_.gfirst[s] = 1;                            // its first chunk resets the slot's level: nothing of the last tenant's stays
     if (slot_of) slot_of[j] = s;
     if (total_frames) total_frames[j] = frames_h_[j];
   }
@@ -1167,88 +1158,20 @@ void Engine::stream_pool_next(int chunk_frames, const int32_t* per_slot, bool wa
   if (chunk_frames < 1) throw std::runtime_error("chunk_frames must be >= 1");
   PE_HIP(hipSetDevice(device_));
   finish_run();                                        // (a speculative run still in flight settles its sizes first)
-  const int S = sp_slots_, cap = sp_cap_, hf = decoder_halo_frames();
-  std::vector<std::array<int64_t, 4>> rows;            // converted rate: every slot's row of the resampling launch
-  // The previous chunk ended with a synchronisation: nothing on the device reads the pinned block any more. A slot with
-  // nothing to deliver -- empty, finished, left -- gets the one-frame window [0, 1) of its own row and no delivery range.
-  int* st = sp_host_;
-  long long* off = reinterpret_cast<long long*>(st + sb_o_off(cap));
-  int wmax = 1, cmax = 1;
-  int64_t total = 0;
-  std::vector<int32_t> f1s(S);
-  for (int s = 0; s < S; ++s) {
-    const int F = sp_frames_[s], f0 = sp_pos_[s];
-    const int c = std::min(per_slot && per_slot[s] > 0 ? per_slot[s] : chunk_frames, sp_fcap_);
-    int a = 0, e = 1, first = 0, count = 0, f1 = f0;
-    int64_t ocount = 0;
-    if (sp_live_[s] && f0 < F) {
-      f1 = std::min(F, f0 + c);
-      a = std::max(0, f0 - hf);
-      e = std::min(F, f1 + hf);
-      first = (f0 - a) * hop_;
-      count = (f1 - f0) * hop_;
-      ocount = out_samples((int64_t)f1 * hop_) - out_samples((int64_t)f0 * hop_);
-      cmax = std::max(cmax, c);
-    }
-    f1s[s] = f1;
-    st[s] = a;
-    st[sb_o_len(cap) + s] = e - a;
-    st[sb_o_first(cap) + s] = first;
-    st[sb_o_count(cap) + s] = count;
-    rows.push_back({out_samples((int64_t)f0 * hop_), (int64_t)a * hop_, ocount, (int64_t)(e - a) * hop_});
-    off[s] = (long long)total;
-    sp_off_[s] = total;
-    total += ocount;
-    wmax = std::max(wmax, e - a);
+  const int S = sp_slots_;
+  ChunkRows& r = pool_rows_;
+  bool any = false;
+  for (int s = 0; s < S; ++s) any = any || (sp_live_[s] && r.pos[s] < sp_frames_[s]);
+  if (any) {
+    // the workspaces as open sized them, should another call have shrunk them since (an exact-size fallback under memory
+    // pressure): a no-op otherwise. Before the rows are written: the resampler's row block exists only then. (A call with
+    // nothing to deliver leaves the workspaces alone.)
+    if (capA_B_ < (size_t)S) ensure_stage_a(S, 1);
+    ensure_stage_b(sp_fcap_, S);
   }
-  sp_off_[S] = total;
-  out.batch = S;
-  out.sample_offsets = sp_off_.data();
-  out.frames_done = sp_pos_.data();
-  out.pcm = sp_pcm_;
-  out.audio = nullptr;
-  if (total == 0) {                                    // no slot has frames left
-    gain_report_idle(sp_gctl_, cap, S);
-    return;
-  }
-  if ((size_t)total > sp_pcm_cap_) {
-    if (sp_pcm_) { PE_HIP(hipHostFree(sp_pcm_)); sp_pcm_ = nullptr; sp_pcm_cap_ = 0; }
-    PE_HIP(hipHostMalloc((void**)&sp_pcm_, ((size_t)total + (size_t)total / 2) * sizeof(int16_t)));
-    sp_pcm_cap_ = (size_t)total + (size_t)total / 2;
-  }
-  if (want_audio && (size_t)total > sp_audio_cap_) {
-    if (sp_audio_) { PE_HIP(hipHostFree(sp_audio_)); sp_audio_ = nullptr; sp_audio_cap_ = 0; }
-    PE_HIP(hipHostMalloc((void**)&sp_audio_, ((size_t)total + (size_t)total / 2) * sizeof(float)));
-    sp_audio_cap_ = (size_t)total + (size_t)total / 2;
-  }
-  void* ptrs[2] = {sp_pcm_, want_audio ? sp_audio_ : nullptr};
-  memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
-  // the workspaces as open sized them, should another call have shrunk them since (an exact-size fallback under memory
-  // pressure): a no-op otherwise
-  if (capA_B_ < (size_t)S) ensure_stage_a(S, 1);
-  ensure_stage_b(sp_fcap_, S);
-  // (the row block exists once the workspaces are sized: the previous chunk's synchronisation freed it for writing)
-  if (rs_on_)
-    for (int s = 0; s < S; ++s) rs_host_row(s, rows[s][0], rows[s][1], (int)rows[s][2], (int)rows[s][3]);
-  sp_wg_ = std::min(rup(cmax + 2 * hf, 32), Fs_);
-  if (sp_wg_ < wmax) sp_wg_ = std::min(rup(wmax, 32), Fs_);
-  char key[96];
-  if (gain_mode_ == GAIN_CHUNK) {
-    snprintf(key, sizeof(key), "P|%d|%d|%d", S, sp_wg_, Fs_);
-  } else {
-    gain_prepare(sp_gctl_, cap, sp_gfirst_, S);
-    snprintf(key, sizeof(key), "P|%d|%d|%d|g%d", S, sp_wg_, Fs_, gain_mode_);
-  }
-  run_stage('P', key);
-  PE_HIP(hipStreamSynchronize(stream_));
-  gain_collect(sp_gctl_, cap, S, sp_gfirst_, sp_off_.data(),
-               rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(sp_dev_) + sb_o_peak(cap));
-  for (int s = 0; s < S; ++s) {
-    sp_pos_[s] = f1s[s];
-    if (sp_live_[s] && sp_pos_[s] >= sp_frames_[s]) sp_live_[s] = 0;      // free from the next call on
-  }
-  out.pcm = sp_pcm_;
-  out.audio = want_audio ? sp_audio_ : nullptr;
+  if (!rows_next(r, sp_frames_.data(), sp_live_.data(), chunk_frames, per_slot, sp_fcap_, want_audio, out)) return;
+  for (int s = 0; s < S; ++s)
+    if (sp_live_[s] && r.pos[s] >= sp_frames_[s]) sp_live_[s] = 0;      // free from the next call on
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1266,7 +1189,7 @@ void Engine::set_stream_gain(int mode, float peak, int ramp_samples) {
     throw std::runtime_error("stream gain ramp_samples outside [0, " + std::to_string(GAIN_MAX_RAMP) + "]");
   bool live = s_active_ && s_pos_ < s_frames_;
   if (sb_active_)
-    for (int b = 0; b < B_ && b < (int)sb_pos_.size(); ++b) live = live || sb_pos_[b] < frames_h_[b];
+    for (int b = 0; b < B_ && b < (int)batch_rows_.pos.size(); ++b) live = live || batch_rows_.pos[b] < frames_h_[b];
   bool pool = false;
   for (int s = 0; s < sp_slots_; ++s) pool = pool || sp_live_[s] != 0;
   if (live || pool)
@@ -1401,7 +1324,7 @@ void Engine::set_output_rate(int native, int output) {
   }
   bool live = s_active_ && s_pos_ < s_frames_;
   if (sb_active_)
-    for (int b = 0; b < B_ && b < (int)sb_pos_.size(); ++b) live = live || sb_pos_[b] < frames_h_[b];
+    for (int b = 0; b < B_ && b < (int)batch_rows_.pos.size(); ++b) live = live || batch_rows_.pos[b] < frames_h_[b];
   if (live || sp_slots_)
     throw std::runtime_error(std::string("the output rate cannot change while a ") +
                              (sp_slots_ ? "stream pool is open" : "stream is live") + " on this handle");

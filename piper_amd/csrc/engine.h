@@ -299,7 +299,9 @@ class Engine {
   void issue_window();
   // zero_absmax: a window pass (the peaks are cleared here, the PCM is not written to the zero-copy host buffer);
   // with_pcm16 = false additionally leaves out the whole-window pcm16_kernel (batch streaming delivers per chunk)
-  void issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16 = true);
+  // cond / cond_bs: the decoder's conditioning rows and their stride (null: this call's, in cond_)
+  void issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16 = true,
+                     const float* cond = nullptr, int cond_bs = 0);
   void run_stage(char which, const std::string& key);
   void dispatch_stage(char which);
   void drop_graphs();
@@ -490,29 +492,44 @@ class Engine {
   int halo_frames_ = 0, s_frames_ = 0, s_pos_ = 0, s_wg_ = 0;
   bool s_active_ = false;
   std::vector<int16_t> s_pcm_;
+  // Lock-step window stages. ChunkRows is everything such a stage owns for its set of rows -- the batch stream's utterances
+  // ('V' graphs), the pool's slots ('P' graphs). The per-chunk state block (kernels/params.h: sb_*) exists twice, pinned
+  // host and device; the gain blocks (params.h: sg_*, sgd_*) likewise. All are allocations of their own at `cap` rows,
+  // outside both workspaces; their addresses are kernel arguments inside the stage's graphs (growth drops the graphs), their
+  // CONTENT -- windows, delivery ranges, the output pointers -- is what changes from chunk to chunk.
+  struct ChunkRows {
+    char stage;                                    // dispatch_stage's letter, first character of the graph keys
+    int cap = 0;                                   // rows the blocks are sized for (even)
+    int* host = nullptr; int* dev = nullptr;       // state blocks
+    int* gctl = nullptr; int* gdev = nullptr;      // gain control (pinned) and gain state (device) blocks
+    std::vector<char> gfirst;                      // per row: nothing delivered yet (its level starts afresh)
+    std::vector<int32_t> pos;                      // frames delivered per row; its size is the number of rows
+    std::vector<int64_t> off;                      // sample offsets of the current chunk
+    int16_t* pcm = nullptr; float* audio = nullptr;     // pinned host output of the current chunk
+    size_t pcm_cap = 0, audio_cap = 0;
+    int wg = 0;                                    // window bucket of the current chunk
+    // what the stage reads the rows from: the latents [row][C][src_cs] and the decoder's conditioning rows (null: cond_)
+    const float* src = nullptr; long src_bs = 0; int src_cs = 0;
+    const float* cond = nullptr; int cond_bs = 0;
+  };
+  void rows_free(ChunkRows& r);
+  // one chunk of every row that has frames left (live: null = all rows are) and the positions advanced: row b goes on by
+  // per_row[b] where that is > 0, else by `chunk`, at most `clamp` frames. False, with nothing run, when no row delivers.
+  bool rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live, int chunk, const int32_t* per_row, int clamp,
+                 bool want_audio, StreamChunk& out);
+  // the window stage on the rows: gather from r.src by the pinned state block, generator, chunk delivery
+  void issue_window_rows(const ChunkRows& r);
   // batch streaming. The window buffer [B][C][Fs] is noise_z_: dead once regulate_kernel has run (debug_tensor refuses
-  // "noise_z" while a batch stream is live). The per-chunk state block (kernels/params.h: sb_*) exists twice, pinned host
-  // and device, both allocated on the first batch stream for the stage-A batch capacity; their addresses are kernel
-  // arguments inside the 'V' graphs (growth drops the graphs), their CONTENT -- windows, delivery ranges, the output
-  // pointers -- is what changes from chunk to chunk.
+  // "noise_z" while a batch stream is live). The blocks are allocated on the first batch stream for the stage-A batch
+  // capacity, the gain blocks with the first chunk outside the default mode; the rows are read from zp_.
   bool sb_active_ = false;
-  int sb_cap_ = 0;
-  int* sb_host_ = nullptr; int* sb_dev_ = nullptr;
-  std::vector<int32_t> sb_pos_;                  // frames delivered per utterance
-  std::vector<int64_t> sb_off_;                  // sample offsets of the current chunk
-  int16_t* sb_pcm_ = nullptr; float* sb_audio_ = nullptr;     // pinned host output of the current chunk
-  size_t sb_pcm_cap_ = 0, sb_audio_cap_ = 0;
+  ChunkRows batch_rows_{'V'};
   void ensure_stream_batch(int B);
-  // stream-wide gain. The setting; the one-utterance stream's state (its conversion runs on the host); per batch stream and
-  // per pool a pinned control block and a device gain block (params.h: sg_*, sgd_*) at the state blocks' capacity -- the
-  // batch stream's allocated with its first chunk outside the default mode and freed with sb_dev_, the pool's allocated by
-  // stream_pool_open and freed by close, neither inside a workspace -- and the host's "nothing delivered yet" flags.
+  // stream-wide gain. The setting; the one-utterance stream's state (its conversion runs on the host); the report of the
+  // last chunk call.
   int gain_mode_ = GAIN_CHUNK, gain_ramp_ = 0;
   float gain_peak_ = 0.f;
   float s_gain_r_ = 0.01f; bool s_gain_first_ = true;
-  int* sb_gctl_ = nullptr; int* sb_gdev_ = nullptr;
-  int* sp_gctl_ = nullptr; int* sp_gdev_ = nullptr;
-  std::vector<char> sb_gfirst_, sp_gfirst_;
   void gain_blocks_alloc(int cap, int** ctl, int** dev);
   void gain_blocks_free(int** ctl, int** dev);
   void gain_prepare(int* ctl, int cap, const std::vector<char>& first, int n);
@@ -525,27 +542,18 @@ class Engine {
   int lg_n_ = -1;                                          // rows of the last chunk call (-1: none yet)
   const unsigned* lg_dev_peaks_ = nullptr;                 // default mode: where the last chunk's peaks are, until other work runs
   bool lg_lazy_ = false;                                   // the report is still to be fetched from there
-  void issue_window_batch();
-  // text encoder, durations and flow of the uploaded batch, the latent left in zp_ (front half of both batch streams);
+  // text encoder, durations and flow of the uploaded batch, the latent left in zp_ (front half of every stream);
   // max_frames > 0: an utterance with more frames is an error, raised before stage B is sized for it
   void stream_front(int B, int max_frames);
-  // the window stage on B utterances: gather from `src` by the pinned state block `hst`, generator, chunk delivery
-  void issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg,
-                          int* gctl, int* gdev);
-  // stream pool (see above). Resident: the latent [slots][C][sp_fcap_], the decoder conditioning rows [slots][cond_dec
-  // rows] (multi-speaker voices), state blocks of its own in the sb_* layout at cap = sp_cap_ (slots rounded up to even),
-  // the pinned join block (params.h: sj_*) and the pinned chunk output. All of them are allocations of their own: workspace
-  // growth, which frees and poisons both workspaces and drops every graph, does not touch them. Their addresses are kernel
-  // arguments inside the 'P' graphs, which stream_pool_close destroys.
-  int sp_slots_ = 0, sp_cap_ = 0, sp_fcap_ = 0, sp_maxf_ = 0, sp_wg_ = 0;   // slots, block capacity, row width, max_frames, window bucket
+  // stream pool (see above). Resident, next to its rows' blocks (cap = slots rounded up to even, all allocated by open): the
+  // latent [slots][C][sp_fcap_], the decoder conditioning rows [slots][cond_dec rows] (multi-speaker voices) and the pinned
+  // join block (params.h: sj_*). Workspace growth, which frees and poisons both workspaces and drops every graph, does not
+  // touch them. stream_pool_close destroys the 'P' graphs.
+  int sp_slots_ = 0, sp_fcap_ = 0, sp_maxf_ = 0;           // slots, row width, max_frames
   float* sp_z_ = nullptr; float* sp_cond_ = nullptr;
-  int* sp_host_ = nullptr; int* sp_dev_ = nullptr; int* sp_join_ = nullptr;
-  std::vector<int32_t> sp_frames_, sp_pos_, sp_live_;
-  std::vector<int64_t> sp_off_;
-  int16_t* sp_pcm_ = nullptr; float* sp_audio_ = nullptr;
-  size_t sp_pcm_cap_ = 0, sp_audio_cap_ = 0;
-  const float* dec_cond_ = nullptr; int dec_cond_bs_ = 0;   // the decoder's conditioning rows while the pool's stage is issued (null: cond_)
-  void issue_window_pool();
+  int* sp_join_ = nullptr;
+  std::vector<int32_t> sp_frames_, sp_live_;
+  ChunkRows pool_rows_{'P'};
   void stream_pool_free();
   // output-rate conversion. The table, the resampled waveform [capB_B_][So_] with its int16 twin and the two row blocks
   // (pinned host + device, params.h: rs_*) are allocations of their own; their addresses are kernel arguments inside the

@@ -433,40 +433,29 @@ void Engine::issue_resample(int B, const float* x, long x_bs, const int* hst, co
                launch::resample(dim3((unsigned)((max_out + rs_tile_ - 1) / rs_tile_), B), stream_, p));
 }
 
-// batch streaming: every utterance's window of z -> window buffer (the dead prior-noise buffer) -> generator on the
-// published window lengths -> per-chunk peak and int16 / float delivery into pinned host memory. One linear chain.
-void Engine::issue_window_batch() {
-  issue_window_stage(B_, sb_cap_, zp_, (long)C_ * Fs_, Fs_, sb_host_, sb_dev_, s_wg_, sb_gctl_, sb_gdev_);
-}
-
-// stream pool: the same stage over all slots, reading the pool's resident rows and conditioning by the pool's state blocks.
-// The stage is issued as a call of `slots` utterances, whatever the handle's last upload was; that call's state comes back.
-void Engine::issue_window_pool() {
-  struct Restore {                                      // whichever way the stage is left
-    Engine* e; int B0;
-    ~Restore() { e->B_ = B0; e->dec_cond_ = nullptr; e->dec_cond_bs_ = 0; }
-  } restore{this, B_};
-  B_ = sp_slots_;
-  dec_cond_ = sp_cond_;
-  dec_cond_bs_ = cond_dec_.rows;
-  issue_window_stage(sp_slots_, sp_cap_, sp_z_, (long)C_ * sp_fcap_, sp_fcap_, sp_host_, sp_dev_, sp_wg_, sp_gctl_, sp_gdev_);
-}
-
-// gctl / gdev: the stream's gain blocks (params.h: sg_*, sgd_*), used in the modes running and fixed only -- one more launch
-// between the chunk's peak and its conversion; the default mode issues exactly the launches it always did.
-void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, int src_cs, const int* hst, int* dst, int wg,
-                                int* gctl, int* gdev) {
+// Lock-step window stage of a row set (the batch stream's utterances, the pool's slots): every row's window of its latent ->
+// window buffer (the dead prior-noise buffer) -> generator on the published window lengths -> per-chunk peak and int16 /
+// float delivery into pinned host memory. One linear chain. The rows' gain blocks (params.h: sg_*, sgd_*) are used in the
+// modes running and fixed only -- one more launch between the chunk's peak and its conversion; the default mode issues
+// exactly the launches it always did.
+void Engine::issue_window_rows(const ChunkRows& r) {
+  const int B = (int)r.pos.size(), cap = r.cap, wg = r.wg;
+  int *const dst = r.dev, *const gctl = r.gctl, *const gdev = r.gdev;
+  // the stage is issued as a call of B utterances, whatever the handle's last upload was (the pool's slots); that call's
+  // batch size comes back whichever way the stage is left
+  struct Restore { int& b; int b0; ~Restore() { b = b0; } } restore{B_, B_};
+  B_ = B;
   const int gm = gain_mode_;
   if (gm != GAIN_CHUNK && (!gctl || !gdev || B > cap)) throw std::runtime_error("stream gain blocks are not sized for this call");
   PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * wg,
-               launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, src, src_bs, src_cs, hst, dst, cap,
+               launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, r.src, r.src_bs, r.src_cs, r.host, dst, cap,
                                      noise_z_, (long)C_ * Fs_, Fs_, wg));
   // what the cost models see (window geometry of the stage kernels, profile rows): the window bucket for every utterance --
   // a function of the graph's key, whatever the utterances' real lengths are
   std::vector<int32_t> win((size_t)B, wg);
   frames_h_.swap(win);
   try {
-    issue_decoder(noise_z_, dst + sb_o_len(cap), wg, (double)B * wg, true, false);
+    issue_decoder(noise_z_, dst + sb_o_len(cap), wg, (double)B * wg, true, false, r.cond, r.cond_bs);
   } catch (...) {
     frames_h_.swap(win);
     throw;
@@ -503,12 +492,13 @@ void Engine::issue_window_stage(int B, int cap, const float* src, long src_bs, i
 
 // HiFiGAN generator + conv_post + int16 on z (already masked by its length semantics). `zsrc` is
 // [B][C][Fs_]; `lens` the per-utterance frame counts in device memory; Fmax the grid bound.
-void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16) {
+void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16,
+                           const float* cond, int cond_bs) {
   stage_tiled_ = false;
   const int B = B_, Fs = Fs_;
   const View none{nullptr, 0, 0};
-  const float* cb_dec = nspk_ > 1 ? (dec_cond_ ? dec_cond_ : cond_ + cond_off_dec_) : nullptr;
-  const int cb_dec_bs = dec_cond_ ? dec_cond_bs_ : cond_bs_;
+  const float* cb_dec = nspk_ > 1 ? (cond ? cond : cond_ + cond_off_dec_) : nullptr;
+  const int cb_dec_bs = cond ? cond_bs : cond_bs_;
   double fl = 0;
   bool tail_done = false;      // conv_post + tanh + peak computed inside the last stage's mrf_kernel
   // (zero_absmax marks the streaming window path; the whole-utterance path clears the peaks in regulate_kernel)
