@@ -104,6 +104,36 @@ int pe_synthesize_batch_scaled(pe_engine* e, const int64_t* ids, const int64_t* 
                                const float* scales, const int64_t* sids, const pe_noise* noise, pe_result* result);
 int pe_upload_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                      const int64_t* sids, const pe_noise* noise);
+
+/* Timing plan: when things are said (beyond the reference, whose only handle is one length_scale).
+ * Host pointers; any member, and the plan itself, may be NULL.
+ *   rate           [n_ids], concatenated like ids: multiplies that id's predicted duration; finite and > 0. NULL: all 1.
+ *   forced         [n_ids]: >= 0, that id lasts exactly so many frames (0 drops it from the audio); -1, predicted. In
+ *                  [-1, 60000]. NULL: all -1. The output of pe_get_durations fits here as it is.
+ *   target_frames  [batch]: > 0, the utterance lasts exactly so many frames; 0, no target. In [0, 60000]. NULL: all 0.
+ * With logw_i as before, w_i = (exp(logw_i) * length_scale) * rate_i in f32, in this order. Without a target a free id gets
+ * d_i = clamp(ceil(w_i), 0, 1e6) as ever and a forced one its value. With a target N the forced ids keep theirs; each of
+ * the n free ids gets one frame, and the R = N - sum(forced) - n frames that are left go by largest remainder on the integer
+ * weights q_i = w_i > 0 ? max(1, (int64)(min(w_i, 1e6) * 2^20)) : 1 -- a_i = q_i R / Q, r_i = q_i R % Q with Q = sum q_i; the
+ * R - sum a_i ids with the largest r_i, ties to the lower index, get one more -- so the frame count is N exactly.
+ * Refused, with a message that names the utterance and the id, before anything of the engine changes (a live stream goes on):
+ * a rate that is not finite or not > 0; a forced value or a target outside its range; a target below sum(forced) + n (every
+ * free id keeps a frame); with every id forced, a target that differs from the sum, or no target and a sum outside
+ * [1, 60000].
+ * The _timed entry points are the calls they are named after plus the plan; with a NULL plan exactly those calls. pe_run
+ * repeated on a timed upload keeps the plan; the next upload of any kind drops it. A timed call always reads the frame counts
+ * back between its two halves (it is never issued for a guessed frame bucket and leaves the guess's statistics alone). When
+ * every id of the call is forced the duration predictor does not run at all and no duration noise is drawn; the debug tensors
+ * logw and plan_w (w_i of the last timed call) are then not available. */
+typedef struct pe_timing {
+  const float* rate;
+  const int32_t* forced;
+  const int32_t* target_frames;
+} pe_timing;
+int pe_upload_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                    const int64_t* sids, const pe_noise* noise, const pe_timing* timing);
+int pe_synthesize_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                              const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing);
 int pe_run(pe_engine* e);
 int pe_fetch(pe_engine* e, int want_audio, int want_pcm, pe_result* result);
 
@@ -127,6 +157,11 @@ int pe_stream_next(pe_engine* e, int32_t chunk_frames, const float** audio, cons
  * NULL). total_frames[batch] receives every utterance's frame count, *halo_frames the generator's receptive half-width. */
 int pe_stream_begin_batch(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                           const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames);
+
+/* ... under a timing plan (pe_timing above) */
+int pe_stream_begin_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                const pe_timing* timing);
 
 typedef struct pe_stream_chunk {
   int32_t batch;
@@ -176,6 +211,10 @@ int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_
 int pe_stream_pool_open(pe_engine* e, int32_t slots, int32_t max_frames, int32_t* halo_frames);
 int pe_stream_pool_join(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
                         const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames);
+/* ... under a timing plan (pe_timing above); a target beyond max_frames is refused like an utterance that long */
+int pe_stream_pool_join_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                              const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                              const pe_timing* timing);
 int pe_stream_pool_next(pe_engine* e, int32_t chunk_frames, const int32_t* chunk_frames_per_slot, int want_audio,
                         pe_stream_chunk* out);
 int pe_stream_pool_leave(pe_engine* e, int32_t slot);
@@ -255,6 +294,12 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
 int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
                       const int32_t* count, const int64_t* origin, float* out, int64_t out_stride);
 
+/* Test hook: the timing-plan kernel alone on caller-supplied logw rows (concatenated, offsets[batch + 1]) with one scales
+ * triple per utterance and a plan (NULL: none). dur_out / w_out receive d_i and w_i, concatenated alike (w_out may be NULL),
+ * frames_out[batch] the frame counts. Plans of 8192 ids cost no synthesis this way. */
+int pe_debug_timing(pe_engine* e, const float* logw, const int64_t* offsets, int32_t batch, const float* scales,
+                    const pe_timing* timing, int32_t* dur_out, int32_t* frames_out, float* w_out);
+
 void pe_set_seed(pe_engine* e, uint64_t seed);
 
 /* Timing with HIP events on the engine's stream. level 1: one pair per pipeline stage (rows
@@ -273,7 +318,8 @@ int pe_profile_bytes(pe_engine* e, int row, double* bytes);
 void* pe_stream(pe_engine* e);
 
 /* Test hook: copy an internal per-stage tensor of utterance b: x_enc, stats (rows m_p then logs_p, models.py:208),
- * xg, logw, z_p (only with PIPER_HIP_DEBUG_KEEP=1 in the environment at pe_create), z, noise_w, noise_z, audio. */
+ * xg, logw, plan_w (w_i of a timed call), z_p (only with PIPER_HIP_DEBUG_KEEP=1 in the environment at pe_create), z, noise_w,
+ * noise_z, audio. */
 int pe_debug_tensor(pe_engine* e, const char* name, int32_t b, float* out, int64_t capacity, int32_t* rows,
                     int32_t* cols);
 

@@ -18,6 +18,7 @@ SYMBOLS = [
     "pe_stream_begin_batch", "pe_stream_next_batch",
     "pe_stream_pool_open", "pe_stream_pool_join", "pe_stream_pool_next", "pe_stream_pool_leave", "pe_stream_pool_close",
     "pe_stream_pool_state",
+    "pe_upload_timed", "pe_synthesize_batch_timed", "pe_stream_begin_batch_timed", "pe_stream_pool_join_timed", "pe_debug_timing",
     "pe_get_durations", "pe_get_info", "pe_set_output_rate", "pe_get_output_rate", "pe_debug_resample",
     "pe_set_stream_gain", "pe_get_stream_gain", "pe_stream_last_gains",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
@@ -32,6 +33,10 @@ SYMBOLS = [
 class PeNoise(C.Structure):
     _fields_ = [("noise_w", C.POINTER(C.c_float)), ("w_stride", C.c_int64),
                 ("noise_z", C.POINTER(C.c_float)), ("z_stride", C.c_int64)]
+
+
+class PeTiming(C.Structure):
+    _fields_ = [("rate", C.POINTER(C.c_float)), ("forced", C.POINTER(C.c_int32)), ("target_frames", C.POINTER(C.c_int32))]
 
 
 class PeResult(C.Structure):
@@ -70,14 +75,20 @@ def bind(path: str) -> C.CDLL:
     lib.pe_synthesize_batch_scaled.argtypes = lib.pe_synthesize_batch.argtypes
     lib.pe_upload.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise)]
     lib.pe_upload_scaled.argtypes = lib.pe_upload.argtypes
+    tp = C.POINTER(PeTiming)
+    lib.pe_upload_timed.argtypes = lib.pe_upload.argtypes + [tp]
+    lib.pe_synthesize_batch_timed.argtypes = lib.pe_synthesize_batch.argtypes + [tp]
     lib.pe_run.argtypes = [vp]
     lib.pe_fetch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PeResult)]
     lib.pe_stream_begin.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_next.argtypes = [vp, C.c_int32, C.POINTER(f32p), C.POINTER(C.POINTER(C.c_int16)), i64p]
     lib.pe_stream_begin_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
+    lib.pe_stream_begin_batch_timed.argtypes = lib.pe_stream_begin_batch.argtypes + [tp]
     lib.pe_stream_next_batch.argtypes = [vp, C.c_int32, C.c_int, C.POINTER(PeStreamChunk)]
     lib.pe_stream_pool_open.argtypes = [vp, C.c_int32, C.c_int32, i32p]
     lib.pe_stream_pool_join.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
+    lib.pe_stream_pool_join_timed.argtypes = lib.pe_stream_pool_join.argtypes + [tp]
+    lib.pe_debug_timing.argtypes = [vp, f32p, i64p, C.c_int32, f32p, tp, i32p, i32p, f32p]
     lib.pe_stream_pool_next.argtypes = [vp, C.c_int32, i32p, C.c_int, C.POINTER(PeStreamChunk)]
     lib.pe_stream_pool_leave.argtypes = [vp, C.c_int32]
     lib.pe_stream_pool_close.argtypes = [vp]

@@ -74,6 +74,8 @@ void Engine::free_all() {
   if (h_frames_) hipHostFree(h_frames_);
   if (h_in_) hipHostFree(h_in_);
   h_in_ = nullptr; h_in_cap_ = 0;
+  if (h_plan_) hipHostFree(h_plan_);
+  h_plan_ = nullptr; h_plan_cap_ = 0;
   rows_free(batch_rows_);
   sb_active_ = false;
   stream_pool_free();
@@ -191,6 +193,8 @@ void Engine::ensure_stage_a(int B, int Tmax) {
     logw_ = c.take<float>(Bc * T);
     noise_w_ = c.take<float>(Bc * 2 * T);
     cond_ = c.take<float>(Bc * (size_t)std::max(cond_bs_, 1));
+    plan_w_ = c.take<float>(Bc * T);               // timing plan (kernels/timing.h): w per id, and the plan block
+    d_plan_ = c.take<int>(plan_words(Bc, T));
     // utterances whose attention score slab does not fit LDS: [utterance][head][query block][32][SP] in global memory
     att_s_ = attn_scores_global((int)T) ? c.take<float>(Bc * nh_ * (size_t)rup((int)T, ATT_QB) * (rup((int)T, 64) + 1)) : nullptr;
     return c.off + 256;
@@ -345,10 +349,11 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
 // ------------------------------------------------------------------------------------------------
 
 void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                    const int64_t* sids, const NoiseIn* noise, bool per_utt) {
+                    const int64_t* sids, const NoiseIn* noise, bool per_utt, const TimingIn* timing) {
   EntryLock entry_lock;
   if (B <= 0 || B > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
   if (!scales) throw std::runtime_error("null scales");
+  const bool all_forced = timing ? check_timing(*timing, offsets, B) : false;      // (throws before anything changes)
   PE_HIP(hipSetDevice(device_));
   sb_active_ = false;               // new inputs end a batch stream: its latent and its window state go with them
   lg_dev_peaks_ = nullptr;          // (the next resampling launch clears the peak words a default-mode report would read)
@@ -418,6 +423,30 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   if (!ids_zc_)
     PE_HIP(hipMemcpyAsync(d_in_, h_in_, 32 + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int), hipMemcpyHostToDevice,
                           stream_));
+  plan_on_ = timing != nullptr;
+  plan_skip_ = all_forced;
+  if (timing) {
+    // the plan block through its own pinned staging block (the previous timed call's copy ended with that call's final
+    // synchronisation; an abandoned upload is waited for before its block is overwritten or freed)
+    const size_t words = plan_words(Bc, (size_t)Ts);
+    PE_HIP(hipStreamSynchronize(stream_));
+    if (h_plan_cap_ < words) {
+      if (h_plan_) { PE_HIP(hipHostFree(h_plan_)); h_plan_ = nullptr; h_plan_cap_ = 0; }
+      PE_HIP(hipHostMalloc((void**)&h_plan_, words * sizeof(int)));
+      h_plan_cap_ = words;
+    }
+    for (int b = 0; b < B; ++b) {
+      const int T = tlens_h_[b];
+      h_plan_[b] = timing->target ? timing->target[b] : 0;
+      float* hr_ = reinterpret_cast<float*>(h_plan_ + Bc + (size_t)b * 2 * Ts);
+      int* hf = h_plan_ + Bc + (size_t)b * 2 * Ts + Ts;
+      for (int t = 0; t < T; ++t) {
+        hr_[t] = timing->rate ? timing->rate[offsets[b] + t] : 1.0f;
+        hf[t] = timing->forced ? timing->forced[offsets[b] + t] : -1;
+      }
+    }
+    PE_HIP(hipMemcpyAsync(d_plan_, h_plan_, (Bc + (size_t)B * 2 * Ts) * sizeof(int), hipMemcpyHostToDevice, stream_));
+  }
   scales_[0] = scales[0]; scales_[1] = scales[1]; scales_[2] = scales[2];
   have_noise_w_ = noise && noise->noise_w;
   have_noise_z_ = noise && noise->noise_z;
@@ -588,6 +617,7 @@ void Engine::run() {
   run_launches_ = 0;
   // speculative sizing of stage B from the previous run's frames-per-id ratio (see engine.h)
   bool spec = pol_.speculate(B) && last_ratio_ > 0.f && !have_noise_z_ && use_graphs_ && !prof_on_;
+  if (plan_on_) spec = false;                 // a timed call: A, read-back, B -- and nothing of the speculation's state moves
   if (spec && spec_cooldown_ > 0) { --spec_cooldown_; spec = false; }
   int fguess = 0;
   if (spec) {
@@ -640,8 +670,7 @@ void Engine::run() {
     ++spec_runs_;
     return;
   }
-  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
-  run_stage('A', key);
+  run_stage('A', stage_a_key(B));
   ++call_;                                    // mirrors the device-side counter bump of this run
   PE_HIP(hipStreamSynchronize(stream_));      // the only data-dependent shape: F
   finish_stage_b_sizes();
@@ -656,6 +685,15 @@ void Engine::run() {
     snprintf(key, sizeof(key), "B|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
     run_stage('B', key);
   }
+}
+
+// The key of stage A's graph. An untimed call's is what it always was; a timed call's carries the plan's two flags -- a
+// plan is present, the duration predictor is left out -- and nothing of the plan's values.
+std::string Engine::stage_a_key(int B) const {
+  char key[200];
+  if (plan_on_) snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d|p%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_, (int)plan_skip_);
+  else snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
+  return key;
 }
 
 // Host view of the frame counts stage A produced (the stream is synchronised): frames, sample offsets, the ratio the
@@ -679,7 +717,8 @@ void Engine::finish_stage_b_sizes() {
   Fmax_ = Fmax;
   // decaying maximum: one long-winded utterance keeps the estimate up for a while, a lasting change of voice / scales
   // is followed within ~50 calls
-  last_ratio_ = std::max(ratio, last_ratio_ * 0.98f + ratio * 0.02f);
+  // (a timed call's frames per id say nothing about the voice: it leaves the estimate alone)
+  if (!plan_on_) last_ratio_ = std::max(ratio, last_ratio_ * 0.98f + ratio * 0.02f);
   sample_off_.assign(B + 1, 0);
   for (int b = 0; b < B; ++b) sample_off_[b + 1] = sample_off_[b] + out_samples((int64_t)frames_h_[b] * hop_);
 }
@@ -885,8 +924,7 @@ void Engine::ensure_stream_batch(int B) {
 void Engine::stream_front(int B, int max_frames) {
   Tg_ = std::min(id_bucket(Tmax_), Ts_);
   char key[160];
-  snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
-  run_stage('A', key);
+  run_stage('A', stage_a_key(B));
   ++call_;
   PE_HIP(hipStreamSynchronize(stream_));
   finish_stage_b_sizes();
@@ -907,9 +945,9 @@ void Engine::stream_front(int B, int max_frames) {
 }
 
 const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                                                       const int64_t* sids, const NoiseIn* noise) {
+                                                       const int64_t* sids, const NoiseIn* noise, const TimingIn* timing) {
   EntryLock entry_lock;
-  upload(ids, offsets, B, scales, sids, noise, true);
+  upload(ids, offsets, B, scales, sids, noise, true, timing);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
@@ -1109,7 +1147,7 @@ void Engine::stream_pool_leave(int slot) {
 }
 
 void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
-                              const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames) {
+                              const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing) {
   EntryLock entry_lock;
   stream_pool_require();
   if (n < 1) throw std::runtime_error("batch size must be in [1, 4096]");
@@ -1123,7 +1161,13 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
                              " utterances want to join");
   }
   // from here to the adopt launch nothing of the pool is touched: whatever fails, the pool is as it was
-  upload(ids, offsets, n, scales, sids, noise, true);
+  if (timing) check_timing(*timing, offsets, n);       // (before the pool's own check below, which reads the targets)
+  if (timing && timing->target)
+    for (int j = 0; j < n; ++j)
+      if (timing->target[j] > sp_maxf_)
+        throw std::runtime_error("utterance " + std::to_string(j) + " has a target of " + std::to_string(timing->target[j]) +
+                                 " frames, the stream pool holds at most " + std::to_string(sp_maxf_) + " (max_frames)");
+  upload(ids, offsets, n, scales, sids, noise, true, timing);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent)
@@ -1499,6 +1543,121 @@ void Engine::debug_resample(const float* x, int batch, int64_t stride, const int
   release();
 }
 
+// ------------------------------------------------------------------------------------------------
+// timing plan
+// ------------------------------------------------------------------------------------------------
+
+// The rules of include/piper_hip.h (pe_timing). Nothing of an engine is read: a refusal changes nothing.
+bool Engine::check_timing(const TimingIn& t, const int64_t* offsets, int B) {
+  bool all_forced = true;
+  for (int b = 0; b < B; ++b) {
+    const int64_t T = offsets[b + 1] - offsets[b];
+    if (T <= 0) throw std::runtime_error("empty phoneme id sequence");
+    if (T > 8192) throw std::runtime_error("phoneme id sequence longer than 8192");
+    const std::string utt = "utterance " + std::to_string(b);
+    long long sum = 0, nfree = 0;
+    for (int64_t i = 0; i < T; ++i) {
+      if (t.rate) {
+        const float r = t.rate[offsets[b] + i];
+        if (!std::isfinite(r) || !(r > 0.f))
+          throw std::runtime_error(utt + ", id " + std::to_string(i) + ": rate must be finite and > 0");
+      }
+      const int32_t f = t.forced ? t.forced[offsets[b] + i] : -1;
+      if (f < -1 || f > MAX_FRAMES)
+        throw std::runtime_error(utt + ", id " + std::to_string(i) + ": forced duration " + std::to_string(f) + " outside [-1, " +
+                                 std::to_string(MAX_FRAMES) + "]");
+      if (f >= 0) sum += f; else ++nfree;
+    }
+    const int32_t N = t.target ? t.target[b] : 0;
+    if (N < 0 || N > MAX_FRAMES)
+      throw std::runtime_error(utt + ": target_frames " + std::to_string(N) + " outside [0, " + std::to_string(MAX_FRAMES) + "]");
+    if (N > 0 && nfree > 0 && (long long)N < sum + nfree)
+      throw std::runtime_error(utt + ": target_frames " + std::to_string(N) + " is below the forced durations' sum " +
+                               std::to_string(sum) + " plus one frame for each of the " + std::to_string(nfree) + " free ids");
+    if (N > 0 && nfree == 0 && (long long)N != sum)
+      throw std::runtime_error(utt + ": every id is forced and the durations' sum " + std::to_string(sum) +
+                               " differs from target_frames " + std::to_string(N));
+    if (N == 0 && nfree == 0 && (sum < 1 || sum > MAX_FRAMES))
+      throw std::runtime_error(utt + ": every id is forced and the durations' sum " + std::to_string(sum) + " is outside [1, " +
+                               std::to_string(MAX_FRAMES) + "]");
+    all_forced = all_forced && nfree == 0;
+  }
+  return all_forced;
+}
+
+// duration_plan_kernel's parameters for the uploaded call on top of duration_kernel's
+void Engine::plan_params(PlanP& pp, const DurP& dp) const {
+  const size_t Bc = capA_B_;
+  pp.d = dp;
+  pp.target = d_plan_;
+  pp.rate = reinterpret_cast<const float*>(d_plan_ + Bc);
+  pp.forced = d_plan_ + Bc + Ts_;
+  pp.pl_bs = (long)2 * Ts_;
+  pp.w_out = plan_skip_ ? nullptr : plan_w_;
+}
+
+void Engine::debug_timing(const float* logw, const int64_t* offsets, int batch, const float* scales, const TimingIn* timing,
+                          int32_t* dur_out, int32_t* frames_out, float* w_out) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!logw || !offsets || !scales || !dur_out || !frames_out) throw std::runtime_error("null argument");
+  const TimingIn none;
+  const TimingIn& t = timing ? *timing : none;
+  check_timing(t, offsets, batch);
+  int Tmax = 1;
+  for (int b = 0; b < batch; ++b) Tmax = std::max(Tmax, (int)(offsets[b + 1] - offsets[b]));
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  // one host image, one device block: [lens B | frames B | clamped B | scales 3B | target B | per utterance: logw, rate,
+  // forced, dur, cum, w of Ts words each]
+  const size_t Ts = (size_t)rup(Tmax, 4), B = (size_t)batch, head = 7 * B, row = 6 * Ts, words = head + B * row;
+  std::vector<int> h(words, 0);
+  float* hf = reinterpret_cast<float*>(h.data());
+  for (size_t b = 0; b < B; ++b) {
+    const int T = (int)(offsets[b + 1] - offsets[b]);
+    h[b] = T;
+    for (int k = 0; k < 3; ++k) hf[3 * B + 3 * b + k] = scales[3 * b + k];
+    h[6 * B + b] = t.target ? t.target[b] : 0;
+    const size_t r0 = head + b * row;
+    for (int i = 0; i < T; ++i) {
+      hf[r0 + i] = logw[offsets[b] + i];
+      hf[r0 + Ts + i] = t.rate ? t.rate[offsets[b] + i] : 1.0f;
+      h[r0 + 2 * Ts + i] = t.forced ? t.forced[offsets[b] + i] : -1;
+    }
+  }
+  int* dv = nullptr;
+  PE_HIP(hipMalloc((void**)&dv, words * sizeof(int)));
+  try {
+    PE_HIP(hipMemcpyAsync(dv, h.data(), words * sizeof(int), hipMemcpyHostToDevice, stream_));
+    float* df = reinterpret_cast<float*>(dv);
+    PlanP pp{};
+    pp.d.z0 = df + head; pp.d.z_bs = (long)row; pp.d.m0 = 0.f; pp.d.es0 = 1.f; pp.d.scales = df + 3 * B;
+    pp.d.lens = dv; pp.d.dur = dv + head + 3 * Ts; pp.d.cum = dv + head + 4 * Ts; pp.d.d_bs = (int)row;
+    pp.d.frames = dv + B; pp.d.logw_out = nullptr; pp.d.frames_host = nullptr; pp.d.frames_clamped = dv + 2 * B;
+    pp.d.frame_cap = MAX_FRAMES + 1;
+    pp.target = dv + 6 * B;
+    pp.rate = df + head + Ts; pp.forced = dv + head + 2 * Ts; pp.pl_bs = (long)row;
+    pp.w_out = df + head + 5 * Ts;
+    launch::duration_plan(dim3(batch), stream_, pp);
+    PE_HIP(hipMemcpyAsync(h.data(), dv, words * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    hipFree(dv);
+    throw;
+  }
+  hipFree(dv);
+  for (size_t b = 0; b < B; ++b) {
+    const int T = (int)(offsets[b + 1] - offsets[b]);
+    const size_t r0 = head + b * row;
+    frames_out[b] = h[B + b];
+    for (int i = 0; i < T; ++i) {
+      dur_out[offsets[b] + i] = h[r0 + 3 * Ts + i];
+      if (w_out) w_out[offsets[b] + i] = hf[r0 + 5 * Ts + i];
+    }
+  }
+}
+
 const std::vector<int32_t>& Engine::durations_host() {
   EntryLock entry_lock;
   finish_run();
@@ -1532,7 +1691,7 @@ void Engine::debug_randn(int site, uint64_t call, int64_t row, int64_t n, float*
   hipFree(st);
 }
 
-// Per-stage tensors for parity debugging (tests only): name in {x_enc, stats (m_p | logs_p), xg, logw, z_p, z, noise_w,
+// Per-stage tensors for parity debugging (tests only): name in {x_enc, stats (m_p | logs_p), xg, logw, plan_w, z_p, z, noise_w,
 // noise_z, audio, pool_z, pool_cond}.
 void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& out, int* rows, int* cols) {
   EntryLock entry_lock;
@@ -1544,6 +1703,14 @@ void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& ou
   if (name == "x_enc") { src = stage_a_enc_out() + (size_t)b * H_ * Ts_; R = H_; Cn = tlens_h_[b]; stride = Ts_; }
   else if (name == "stats") { src = stats_ + (size_t)b * 2 * C_ * Ts_; R = 2 * C_; Cn = tlens_h_[b]; stride = Ts_; }
   else if (name == "xg") { src = xg_ + (size_t)b * H_ * Ts_; R = H_; Cn = tlens_h_[b]; stride = Ts_; }
+  else if (name == "logw" && plan_skip_)
+    throw std::runtime_error("logw is not available: every id of the call was forced, the duration predictor did not run");
+  else if (name == "plan_w") {
+    if (!plan_on_) throw std::runtime_error("plan_w is only available after a timed call");
+    if (plan_skip_)
+      throw std::runtime_error("plan_w is not available: every id of the call was forced, the duration predictor did not run");
+    src = plan_w_ + (size_t)b * Ts_; R = 1; Cn = tlens_h_[b]; stride = Ts_;
+  }
   else if (name == "logw") { src = logw_ + (size_t)b * Ts_; R = 1; Cn = tlens_h_[b]; stride = Ts_; }
   else if (name == "z") { src = zp_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_; }
   else if (name == "z_p") {

@@ -55,6 +55,14 @@ struct NoiseIn {            // optional injected N(0,1) draws (parity tests); ho
   int64_t z_stride = 0;
 };
 
+// A timing plan (include/piper_hip.h: pe_timing). Host pointers, any of them null: rate and forced per id,
+// concatenated like the ids; target per utterance.
+struct TimingIn {
+  const float* rate = nullptr;
+  const int32_t* forced = nullptr;
+  const int32_t* target = nullptr;
+};
+
 // Where the packed voice weights live. Default: one device allocation owned by the engine. A caller-provided arena
 // (multi-GPU: a device buffer the host framework can hand to RCCL) receives them instead; with `skeleton` the engine only
 // lays the arena out (same offsets as on the packing rank, derived from tensor shapes alone) and waits for its content
@@ -77,8 +85,15 @@ class Engine {
   // Phase 1: copy inputs to HBM. ids: concatenated phoneme ids, offsets[B+1]. scales: one {noise_scale, length_scale,
   // noise_w} triple for every utterance, or (per_utt) [B][3], one triple per utterance. The triples are call inputs in
   // device memory like the ids: no captured graph depends on their values.
+  // timing: the call's plan, checked before anything of the engine changes (a refused plan leaves a live stream alone). It
+  // stays with the uploaded inputs -- every run() on them follows it -- and goes with the next upload.
   void upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-              const int64_t* sids, const NoiseIn* noise, bool per_utt = false);
+              const int64_t* sids, const NoiseIn* noise, bool per_utt = false, const TimingIn* timing = nullptr);
+  bool timed() const { return plan_on_; }
+  // test hook: duration_plan_kernel alone on caller-given logw rows (concatenated like ids, offsets[batch + 1]) with one
+  // scales triple per utterance: the durations and w (concatenated) and the frame counts
+  void debug_timing(const float* logw, const int64_t* offsets, int batch, const float* scales, const TimingIn* timing,
+                    int32_t* dur_out, int32_t* frames_out, float* w_out);
   // Phase 2: the whole device pipeline (one host read-back of B frame counts in the middle).
   void run();
   // Phase 3: results to host (pinned buffers owned by the engine, valid until the next upload()).
@@ -143,7 +158,7 @@ class Engine {
     const int32_t* frames_done = nullptr;       // [batch]
   };
   const std::vector<int32_t>& stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                                                 const int64_t* sids, const NoiseIn* noise);
+                                                 const int64_t* sids, const NoiseIn* noise, const TimingIn* timing = nullptr);
   void stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out);
 
   // Stream pool: a fixed number of slots whose latents and decoder conditioning rows live in storage OWNED BY THE POOL,
@@ -158,7 +173,7 @@ class Engine {
   // A join that fails (too few free slots, an utterance over max_frames, an upload error) leaves the pool as it was.
   int stream_pool_open(int slots, int max_frames);                 // returns the halo in frames
   void stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
-                        const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames);
+                        const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing = nullptr);
   void stream_pool_next(int chunk_frames, const int32_t* per_slot, bool want_audio, StreamChunk& out);   // out.batch == slots
   void stream_pool_leave(int slot);
   void stream_pool_close();
@@ -442,6 +457,17 @@ class Engine {
   float spec_rel(int b) const { return (size_t)b < spec_rel_.size() ? spec_rel_[b] : 1.f; }
   bool have_noise_w_ = false, have_noise_z_ = false;
   bool drew_w_ = false;                       // this call's duration noise is drawn by embed_kernel (small calls), not randn_kernel
+  // Timing plan of the uploaded inputs. The plan block in the stage-A workspace (kernels/params.h: PlanP) is filled by one
+  // copy from a pinned staging block of its own -- not the input block embed_kernel may read in place -- so the plan's values
+  // are never kernel arguments: the 'A' graph of a timed call carries the two flags below in its key and nothing else of
+  // the plan. A timed call runs as A, frame-count read-back, B; it neither reads nor feeds the speculative sizing.
+  bool plan_on_ = false, plan_skip_ = false;      // skip: every id is forced, stage A leaves the duration predictor out
+  int* d_plan_ = nullptr; float* plan_w_ = nullptr;
+  int* h_plan_ = nullptr; size_t h_plan_cap_ = 0;
+  // throws the refusal; returns whether every id of the call is forced
+  static bool check_timing(const TimingIn& t, const int64_t* offsets, int B);
+  void plan_params(PlanP& pp, const DurP& dp) const;
+  std::string stage_a_key(int B) const;
   bool fold_dur_ = false;                  // the stage being issued is the one-graph form: regulate_kernel computes the durations
   DurP fold_dp_{};                         // ... from these fields (filled by issue_stage_a)
   std::vector<int64_t> id_off_;

@@ -64,7 +64,8 @@ void Engine::issue_stage_a() {
     }
     // small calls: the duration noise is drawn here too (one workgroup, <= 4 Philox blocks per thread), not by a launch of
     // its own in front of the first ConvFlow
-    drew_w_ = !have_noise_w_ && (long)B * 2 * ((T + 3) / 4) <= 256;
+    // (a call whose every duration is forced draws no duration noise at all)
+    drew_w_ = !have_noise_w_ && !plan_skip_ && (long)B * 2 * ((T + 3) / 4) <= 256;
     if (drew_w_) { ep.draw_out = noise_w_; ep.draw_stride = Ts; ep.draw_rows = B * 2; ep.draw_cols = T; }
     PE_LAUNCH_KB("embed_kernel", 4.0 * tsum * (1.0 + H_), launch::embed(dim3((T + 63) / 64, (H_ + 15) / 16, B), stream_, ep));
   }
@@ -229,6 +230,18 @@ void Engine::issue_stage_a() {
   // ================= stochastic duration predictor, reverse (models.py:63-71,108-117)
   prof_begin();
   fl = 0;
+  if (plan_skip_) {
+    // every duration of the call is forced: no duration predictor, no noise_w draw -- duration_plan_kernel runs from the
+    // plan alone
+    DurP dp{};
+    dp.scales = d_scales_; dp.lens = d_tlens_; dp.dur = d_dur_; dp.cum = d_cum_; dp.d_bs = Ts; dp.frames = d_frames_;
+    dp.frames_host = h_frames_; dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
+    PlanP pp{};
+    plan_params(pp, dp);
+    PE_LAUNCH_KB("duration_plan_kernel", 4.0 * 4.0 * tsum, launch::duration_plan(dim3(B), stream_, pp));
+    prof_end(1, fl);
+    return;
+  }
   if (!stacked &&
       !(chain_q && dp_pre16_ && conv1x1_col4(dp_pre16_, dp_pre_.bias, dp_pre_.rows, x, dy, d_tlens_, B, T, 2.0 * tsum * dp_pre_.macs_per_col,
                                              cb_dp, cond_bs_)))
@@ -285,7 +298,11 @@ void Engine::issue_stage_a() {
     dp.frames_host = h_frames_; dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
     // the whole utterance as one graph: regulate_kernel, first launch of stage B, computes the durations itself
     fold_dp_ = dp;
-    if (!fold_dur_) PE_LAUNCH_KB("duration_kernel", 4.0 * 4.0 * tsum, launch::duration(dim3(B), stream_, dp));
+    if (plan_on_) {
+      PlanP pp{};
+      plan_params(pp, dp);
+      PE_LAUNCH_KB("duration_plan_kernel", 4.0 * 6.0 * tsum, launch::duration_plan(dim3(B), stream_, pp));
+    } else if (!fold_dur_) PE_LAUNCH_KB("duration_kernel", 4.0 * 4.0 * tsum, launch::duration(dim3(B), stream_, dp));
   }
   prof_end(1, fl);
 }

@@ -56,6 +56,7 @@ void spline_inverse(dim3 grid, hipStream_t stream, const float* hproj, long h_bs
                     const int* lens, float inv_sqrt_h);
 void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, const float* s, long per_utt);
 void duration(dim3 grid, hipStream_t stream, const DurP& p);
+void duration_plan(dim3 grid, hipStream_t stream, const PlanP& p);      // duration_kernel's place under a timing plan (timing.h)
 void randn(hipStream_t stream, float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
            int site);
 void regulate(dim3 grid, hipStream_t stream, const RegP& p);

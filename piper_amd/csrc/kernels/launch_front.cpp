@@ -12,6 +12,7 @@
 #include "layernorm.h"
 #include "glue.h"
 #include "spline.h"
+#include "timing.h"
 
 namespace pe {
 namespace launch {
@@ -102,6 +103,8 @@ void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, c
 }
 
 void duration(dim3 grid, hipStream_t stream, const DurP& p) { PE_LAUNCH(duration_kernel, grid, dim3(256), 0, stream, p); }
+
+void duration_plan(dim3 grid, hipStream_t stream, const PlanP& p) { PE_LAUNCH(duration_plan_kernel, grid, dim3(256), 0, stream, p); }
 
 void randn(hipStream_t stream, float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
            int site) {

@@ -207,6 +207,15 @@ struct DurP {
   const int* lens; int* dur; int* cum; int d_bs; int* frames; float* logw_out;
   int* frames_host; int* frames_clamped; int frame_cap;
 };
+// ---- timing plan (timing.h). The plan block, device and pinned host alike: [target Bc | per utterance: rate T floats,
+// forced T ints], so that the rows of a call's B utterances are one contiguous piece behind the targets.
+struct PlanP {
+  DurP d;                                      // duration_kernel's fields; d.z0 null: every id is forced, no logw exists
+  const int* target;                           // [B]: > 0 the utterance's frame count, 0 none
+  const float* rate; const int* forced; long pl_bs;      // row b at + b * pl_bs: multiplier of the id's duration; >= 0 forced frames, -1 predicted
+  float* w_out;                                // [B][d.d_bs] w_i ("plan_w"), or null
+};
+static inline size_t plan_words(size_t Bc, size_t T) { return Bc + 2 * Bc * T; }
 static constexpr int RNG_PITCH = 65536;       // >= MAX_FRAMES and >= the longest id sequence
 static inline unsigned randn_blocks(long rows, int cols) { return (unsigned)(rows * ((cols + 1023) / 1024)); }
 struct RegP {

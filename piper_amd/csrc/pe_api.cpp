@@ -62,6 +62,12 @@ static void to_noise(const pe_noise* noise, pe::NoiseIn& n) {
   n.noise_z = noise->noise_z; n.z_stride = noise->z_stride;
 }
 
+static const pe::TimingIn* to_timing(const pe_timing* t, pe::TimingIn& out) {
+  if (!t) return nullptr;
+  out.rate = t->rate; out.forced = t->forced; out.target = t->target_frames;
+  return &out;
+}
+
 extern "C" {
 
 const char* pe_last_error(void) { return g_err.c_str(); }
@@ -179,6 +185,18 @@ int pe_upload_scaled(pe_engine* e, const int64_t* ids, const int64_t* offsets, i
   });
 }
 
+int pe_upload_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                    const int64_t* sids, const pe_noise* noise, const pe_timing* timing) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t));
+  });
+}
+
 int pe_run(pe_engine* e) {
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
@@ -221,6 +239,23 @@ int pe_synthesize_batch_scaled(pe_engine* e, const int64_t* ids, const int64_t* 
     to_noise(noise, n);
     const auto t0 = std::chrono::steady_clock::now();
     e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true);
+    e->eng->run();
+    e->eng->download(true, true);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fill_result(e, result, secs);
+  });
+}
+
+int pe_synthesize_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                              const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    const auto t0 = std::chrono::steady_clock::now();
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t));
     e->eng->run();
     e->eng->download(true, true);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -274,6 +309,22 @@ int pe_stream_begin_batch(pe_engine* e, const int64_t* ids, const int64_t* offse
   });
 }
 
+int pe_stream_begin_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                const pe_timing* timing) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    const std::vector<int32_t>& f =
+        e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr, to_timing(timing, t));
+    if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
 int pe_stream_next_batch(pe_engine* e, int32_t chunk_frames, int want_audio, pe_stream_chunk* out) {
   return guard([&] {
     if (!e || !out) throw std::runtime_error("null argument");
@@ -305,6 +356,21 @@ int pe_stream_pool_join(pe_engine* e, const int64_t* ids, const int64_t* offsets
     pe::NoiseIn nz;
     to_noise(noise, nz);
     e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames);
+  });
+}
+
+int pe_stream_pool_join_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                              const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                              const pe_timing* timing) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_require();
+    if (!ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, n, 4096);
+    pe::NoiseIn nz;
+    to_noise(noise, nz);
+    pe::TimingIn t;
+    e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames, to_timing(timing, t));
   });
 }
 
@@ -414,6 +480,16 @@ int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t strid
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
     e->eng->debug_resample(x, batch, stride, valid, n0, count, origin, out, out_stride);
+  });
+}
+
+int pe_debug_timing(pe_engine* e, const float* logw, const int64_t* offsets, int32_t batch, const float* scales,
+                    const pe_timing* timing, int32_t* dur_out, int32_t* frames_out, float* w_out) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    check_scales(scales, batch, 4096);
+    pe::TimingIn t;
+    e->eng->debug_timing(logw, offsets, batch, scales, to_timing(timing, t), dur_out, frames_out, w_out);
   });
 }
 

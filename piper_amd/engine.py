@@ -40,6 +40,56 @@ def per_utterance_scales(scales, batch: int):
     return np.ascontiguousarray(a)
 
 
+class Timing:
+    """A timing plan (include/piper_hip.h: pe_timing) as per-utterance lists. ``rate``: one array of per-id multipliers of
+    the predicted durations per utterance (an entry None: all 1). ``durations``: one int array per utterance, >= 0 = that id
+    lasts exactly so many frames, -1 = predicted (an entry None: all predicted). ``target_frames``: one int per utterance,
+    0 = no target. Any of the three may be None."""
+
+    def __init__(self, rate=None, durations=None, target_frames=None):
+        self.rate, self.durations, self.target_frames = rate, durations, target_frames
+
+    def pack(self, id_lists, keep: list):
+        """The C struct for ``id_lists`` (by reference); the arrays it points to are appended to ``keep``."""
+        lens = [len(s) for s in id_lists]
+        t = L.PeTiming()
+
+        def rows(per, dtype, fill, what):
+            if len(per) != len(lens):
+                raise ValueError(f"{what}: {len(per)} entries for {len(lens)} utterances")
+            out = []
+            for b, (r, n) in enumerate(zip(per, lens)):
+                a = np.full(n, fill, dtype) if r is None else np.asarray(r, dtype).reshape(-1)
+                if a.size != n:
+                    raise ValueError(f"{what} of utterance {b}: {a.size} values for {n} ids")
+                out.append(a)
+            return np.ascontiguousarray(np.concatenate(out)) if out else np.zeros(0, dtype)
+
+        if self.rate is not None:
+            a = rows(self.rate, np.float32, 1.0, "rate")
+            keep.append(a)
+            t.rate = a.ctypes.data_as(C.POINTER(C.c_float))
+        if self.durations is not None:
+            a = rows(self.durations, np.int32, -1, "durations")
+            keep.append(a)
+            t.forced = a.ctypes.data_as(C.POINTER(C.c_int32))
+        if self.target_frames is not None:
+            a = np.ascontiguousarray(self.target_frames, np.int32).reshape(-1)
+            if a.size != len(lens):
+                raise ValueError(f"target_frames: {a.size} entries for {len(lens)} utterances")
+            keep.append(a)
+            t.target_frames = a.ctypes.data_as(C.POINTER(C.c_int32))
+        keep.append(t)
+        return C.byref(t)
+
+
+def _tiled_scales(scales, batch: int):
+    per = per_utterance_scales(scales, batch)
+    if per is None:
+        per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (max(batch, 1), 1)))
+    return per
+
+
 class Engine:
     def __init__(self, *, onnx_path: Optional[str] = None, blob: Optional[bytes] = None, device: int = 0,
                  lib: Optional[C.CDLL] = None, arena=None, skeleton: bool = False):
@@ -145,14 +195,18 @@ class Engine:
         return Synthesis(audio, pcm, frames, res.infer_seconds)
 
     # ---- API
-    def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None) -> Synthesis:
+    def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
+                         timing: Optional[Timing] = None) -> Synthesis:
         """``scales``: one (noise_scale, length_scale, noise_w) triple for every utterance, or a (B, 3) array with one
-        triple per utterance (pe_synthesize_batch_scaled)."""
+        triple per utterance (pe_synthesize_batch_scaled). ``timing``: a ``Timing`` plan (pe_synthesize_batch_timed)."""
         ids, offs = self._pack(id_lists)
-        per = per_utterance_scales(scales, len(id_lists))
+        per = per_utterance_scales(scales, len(id_lists)) if timing is None else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_synthesize_batch if per is None else self._lib.pe_synthesize_batch_scaled
         keep: list = [per]
+        extra = ()
+        if timing is not None:
+            entry, extra = self._lib.pe_synthesize_batch_timed, (timing.pack(id_lists, keep),)
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -162,7 +216,7 @@ class Engine:
         res = L.PeResult()
         self._check(entry(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)),
-            len(id_lists), sc, sid_arr, nz, C.byref(res)))
+            len(id_lists), sc, sid_arr, nz, C.byref(res), *extra))
         return self._collect(res)
 
     def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid=None, noise_w=None, noise_z=None) -> Synthesis:
@@ -170,13 +224,18 @@ class Engine:
         nz = None if noise_z is None else np.asarray(noise_z, np.float32)[None]
         return self.synthesize_batch([ids], scales, None if sid is None else [sid], nw, nz)
 
-    def upload(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None):
-        """``scales``: one triple, or a (B, 3) array of per-utterance triples (pe_upload_scaled)."""
+    def upload(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
+               timing: Optional[Timing] = None):
+        """``scales``: one triple, or a (B, 3) array of per-utterance triples (pe_upload_scaled). ``timing``: a ``Timing``
+        plan (pe_upload_timed); every ``run()`` on the upload follows it."""
         ids, offs = self._pack(id_lists)
-        per = per_utterance_scales(scales, len(id_lists))
+        per = per_utterance_scales(scales, len(id_lists)) if timing is None else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_upload if per is None else self._lib.pe_upload_scaled
         keep: list = [per]
+        extra = ()
+        if timing is not None:
+            entry, extra = self._lib.pe_upload_timed, (timing.pack(id_lists, keep),)
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -185,13 +244,20 @@ class Engine:
             sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
         self._keep = keep          # noise_z is read during run()
         self._check(entry(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                          offs.ctypes.data_as(C.POINTER(C.c_int64)), len(id_lists), sc, sid_arr, nz))
+                          offs.ctypes.data_as(C.POINTER(C.c_int64)), len(id_lists), sc, sid_arr, nz, *extra))
 
-    def pack_host(self, id_lists, scales=(0.667, 1.0, 0.8)):
+    def pack_host(self, id_lists, scales=(0.667, 1.0, 0.8), timing: Optional[Timing] = None):
         """The host-side inputs of a call as the C ABI takes them -- int64 ids, prefix offsets, float scales in host
         memory, what piper::synthesize wraps as Ort tensors (reference piper.cpp:342-365) -- built once, for callers that
-        time whole calls (bench.py) without Python's list handling inside the timed region."""
+        time whole calls (bench.py) without Python's list handling inside the timed region. With ``timing`` the plan is
+        packed as well and ``upload_host`` goes through pe_upload_timed."""
         ids, offs = self._pack(id_lists)
+        if timing is not None:
+            per = _tiled_scales(scales, len(id_lists))
+            keep: list = [per]
+            tref = timing.pack(id_lists, keep)
+            return (ids, offs, per.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                    offs.ctypes.data_as(C.POINTER(C.c_int64)), len(id_lists), tref, keep)
         sc = (C.c_float * 3)(*[float(s) for s in scales])
         return (ids, offs, sc, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)),
                 len(id_lists))
@@ -199,6 +265,9 @@ class Engine:
     def upload_host(self, packed):
         """pe_upload of inputs prepared by pack_host: host ids -> device, the engine draws both noise sites."""
         self._keep = []
+        if len(packed) > 6:
+            self._check(self._lib.pe_upload_timed(self._h, packed[3], packed[4], packed[5], packed[2], None, None, packed[6]))
+            return
         self._check(self._lib.pe_upload(self._h, packed[3], packed[4], packed[5], packed[2], None, None))
 
     def run(self):
@@ -239,13 +308,13 @@ class Engine:
             yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
 
     def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
-                     want_audio: bool = True):
+                     want_audio: bool = True, timing: Optional[Timing] = None):
         """Generator over the chunks of B utterances streamed in lock step (pe_stream_begin_batch / pe_stream_next_batch):
         text encoder, durations and flow for the whole batch once, then one batched vocoder pass per chunk. Every item
         is a list of B ``(float chunk or None, int16 chunk)`` pairs -- empty arrays for utterances that are finished;
         chunk k of utterance b is what ``stream`` yields for that utterance alone, in every ``set_stream_gain`` mode (each
         utterance carries its own level). ``chunk_frames``: an int, or a
-        callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales`` as in
+        callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales`` and ``timing`` as in
         ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
         B = len(id_lists)
         ids, offs = self._pack(id_lists)
@@ -260,10 +329,13 @@ class Engine:
             keep.append(sid_np)
             sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
         frames, halo = np.zeros(max(B, 1), np.int32), C.c_int32()
-        self._check(self._lib.pe_stream_begin_batch(
+        entry, extra = self._lib.pe_stream_begin_batch, ()
+        if timing is not None:
+            entry, extra = self._lib.pe_stream_begin_batch_timed, (timing.pack(id_lists, keep),)
+        self._check(entry(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, frames.ctypes.data_as(C.POINTER(C.c_int32)),
-            C.byref(halo)))
+            C.byref(halo), *extra))
         self.stream_frames, self.stream_halo = frames[:B].copy(), halo.value
         self.stream_frames_done = np.zeros(B, np.int32)
         k = 0
@@ -373,6 +445,27 @@ class Engine:
             n0_a.ctypes.data_as(C.POINTER(C.c_int64)), cnt_a.ctypes.data_as(C.POINTER(C.c_int32)),
             org_a.ctypes.data_as(C.POINTER(C.c_int64)), y.ctypes.data_as(C.POINTER(C.c_float)), ostride))
         return [y[b, :cnt_a[b]].copy() for b in range(B)]
+
+    def debug_timing(self, logw_rows, scales=(0.667, 1.0, 0.8), timing: Optional[Timing] = None):
+        """Test hook (pe_debug_timing): the timing-plan kernel alone on ``logw_rows``, a list of 1-D float arrays of logw,
+        with ``scales`` (one triple or a (B, 3) array) and a ``Timing`` plan. Returns (durations, frames, w): per-utterance
+        int32 arrays, an int32 array of B, per-utterance float32 arrays."""
+        B = len(logw_rows)
+        rows = [np.asarray(r, np.float32).reshape(-1) for r in logw_rows]
+        offs = np.zeros(B + 1, np.int64)
+        offs[1:] = np.cumsum([r.size for r in rows])
+        lw = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, np.float32)
+        per = _tiled_scales(scales, B)
+        keep: list = []
+        tref = None if timing is None else timing.pack(rows, keep)
+        n = max(int(offs[-1]), 1)
+        dur, frames, w = np.zeros(n, np.int32), np.zeros(max(B, 1), np.int32), np.zeros(n, np.float32)
+        self._check(self._lib.pe_debug_timing(
+            self._h, lw.ctypes.data_as(C.POINTER(C.c_float)), offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
+            per.ctypes.data_as(C.POINTER(C.c_float)), tref, dur.ctypes.data_as(C.POINTER(C.c_int32)),
+            frames.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))))
+        sl = [slice(int(offs[b]), int(offs[b + 1])) for b in range(B)]
+        return [dur[s].copy() for s in sl], frames[:B].copy(), [w[s].copy() for s in sl]
 
     def set_seed(self, seed: int):
         self._lib.pe_set_seed(self._h, int(seed))
@@ -505,10 +598,12 @@ class StreamPool:
     def free_slots(self) -> list:
         return [int(s) for s in np.flatnonzero(self._state()[2] == 0)]
 
-    def join(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None) -> list:
+    def join(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
+             timing: Optional[Timing] = None) -> list:
         """Begin the utterances of ``id_lists`` and give each a free slot, lowest first, in input order; returns the slots.
         ``scales``: one triple, or a (B, 3) array of per-utterance triples. Fails as a whole, the pool unchanged, when
-        there are too few free slots or an utterance has more than ``max_frames`` frames."""
+        there are too few free slots or an utterance has more than ``max_frames`` frames. ``timing``: a ``Timing`` plan
+        (pe_stream_pool_join_timed)."""
         eng, n = self._eng, len(id_lists)
         ids, offs = eng._pack(id_lists)
         per = per_utterance_scales(scales, n)
@@ -522,10 +617,13 @@ class StreamPool:
             keep.append(sid_np)
             sid_arr = sid_np.ctypes.data_as(C.POINTER(C.c_int64))
         slot_of, frames = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        eng._check(eng._lib.pe_stream_pool_join(
+        entry, extra = eng._lib.pe_stream_pool_join, ()
+        if timing is not None:
+            entry, extra = eng._lib.pe_stream_pool_join_timed, (timing.pack(id_lists, keep),)
+        eng._check(entry(
             eng._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, slot_of.ctypes.data_as(C.POINTER(C.c_int32)),
-            frames.ctypes.data_as(C.POINTER(C.c_int32))))
+            frames.ctypes.data_as(C.POINTER(C.c_int32)), *extra))
         return [int(s) for s in slot_of[:n]]
 
     def next(self, chunk_frames: int = 45, per_slot=None, want_audio: bool = True) -> dict:

@@ -5,7 +5,10 @@ per stdin line with ``phoneme_ids`` (and optionally ``speaker_id``), one ``<line
 ``--batch N`` (new) groups N consecutive lines into one batched GPU call. A line may carry its own ``length_scale``,
 ``noise_scale`` and / or ``noise_w`` (new): they override the command-line values for that utterance alone, and the group
 it belongs to still runs as one call (one scale triple per utterance). ``--output-rate R`` (new) delivers the audio at R Hz,
-resampled on the GPU from ``--sample-rate`` (the voice's own rate); the WAV headers then say R.
+resampled on the GPU from ``--sample-rate`` (the voice's own rate); the WAV headers then say R. A line may also carry
+``durations`` (one int per id: >= 0 that id's frames, -1 predicted), ``rate`` (one multiplier per id) and / or
+``target_seconds`` (the utterance's exact length, converted to frames with ``--sample-rate`` and the voice's hop) (new): a
+group with such a line runs as one timed call; a group without is the call it always was.
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -20,7 +23,7 @@ import wave
 from pathlib import Path
 from typing import Iterable, List, Optional, Tuple
 
-from .engine import Engine
+from .engine import Engine, Timing
 
 _LOGGER = logging.getLogger("piper_amd.infer")
 
@@ -55,6 +58,31 @@ def read_scales(lines: Iterable[str], default: Tuple[float, float, float]) -> Li
             continue
         out.append(tuple(float(obj[k]) if k in obj else float(d) for k, d in zip(SCALE_KEYS, default)))
     return out
+
+
+TIMING_KEYS = ("durations", "rate", "target_seconds")
+
+
+def read_timing(lines: Iterable[str]) -> List[Optional[dict]]:
+    """Per non-empty line (the order of read_utterances): its timing keys as a dict, or None when it has none of them."""
+    out: List[Optional[dict]] = []
+    for line in lines:
+        line = line.strip()
+        if not line:
+            continue
+        obj = json.loads(line)
+        out.append({k: obj[k] for k in TIMING_KEYS if k in obj} or None)
+    return out
+
+
+def group_timing(own: List[Optional[dict]], native_rate: int, hop: int) -> Optional[Timing]:
+    """The plan of a group of lines, or None when no line of it carries a timing key."""
+    if all(t is None for t in own):
+        return None
+    get = lambda t, k: None if t is None else t.get(k)      # noqa: E731
+    secs = [get(t, "target_seconds") for t in own]
+    return Timing(rate=[get(t, "rate") for t in own], durations=[get(t, "durations") for t in own],
+                  target_frames=[0 if s is None else int(round(float(s) * native_rate / hop)) for s in secs])
 
 
 def write_wav(path: Path, sample_rate: int, pcm) -> None:
@@ -95,6 +123,7 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     lines = list(stdin if stdin is not None else sys.stdin)
     utts = read_utterances(lines)
     line_scales = read_scales(lines, scales)
+    line_timing = read_timing(lines)
     step = max(1, args.batch)
     for k in range(0, len(utts), step):
         group = utts[k:k + step]
@@ -103,8 +132,10 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
         # lines without scale keys: the command-line triple; any line with its own: one triple per utterance
         call_scales = scales if all(s is None for s in own) else [scales if s is None else s for s in own]
         t0 = time.perf_counter()
+        timing = group_timing(line_timing[k:k + step], args.sample_rate, engine.hop)
+        extra = {} if timing is None else {"timing": timing}
         res = engine.synthesize_batch([u[1] for u in group], call_scales,
-                                      sids=None if all(s is None for s in sids) else [s or 0 for s in sids])
+                                      sids=None if all(s is None for s in sids) else [s or 0 for s in sids], **extra)
         infer_sec = time.perf_counter() - t0
         audio_sec = sum(p.shape[-1] for p in res.pcm) / wav_rate
         _LOGGER.debug("Real-time factor for %s..%s: %0.4f (infer=%0.4f sec, audio=%0.2f sec)", group[0][0] + 1,

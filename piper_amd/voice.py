@@ -20,7 +20,7 @@ from pathlib import Path
 from typing import Iterable, List, Optional, Union
 
 from .config import PhonemeType, PiperConfig
-from .engine import Engine
+from .engine import Engine, Timing
 
 PAD = "_"  # padding (0)        -- reference const.py
 BOS = "^"  # beginning of sentence
@@ -143,20 +143,48 @@ class PiperVoice:
             return None
         return 0 if speaker_id is None else speaker_id
 
+    def target_frames(self, seconds: Optional[float]) -> int:
+        """A length in seconds as spectrogram frames of this voice: round(seconds * native rate / hop) with the
+        config's sample rate as the native one; None: 0, no target."""
+        if seconds is None:
+            return 0
+        return int(round(float(seconds) * int(self.config.sample_rate) / self.session.hop))
+
+    def _timing(self, durations, rate, target_seconds) -> Optional[Timing]:
+        """The plan of a call from per-utterance lists (None: nothing of that kind), or None for an untimed call."""
+        if durations is None and rate is None and target_seconds is None:
+            return None
+        return Timing(rate=rate, durations=durations,
+                      target_frames=None if target_seconds is None else [self.target_frames(s) for s in target_seconds])
+
     def synthesize_ids_to_raw(self, phoneme_ids: List[int], speaker_id: Optional[int] = None,
                               length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
-                              noise_w: Optional[float] = None) -> bytes:
-        """Synthesize raw 16-bit mono audio from phoneme ids (voice.py:140-185)."""
-        r = self.session.synthesize(phoneme_ids, self._scales(length_scale, noise_scale, noise_w),
-                                    sid=self._speaker(speaker_id))
+                              noise_w: Optional[float] = None, durations=None, rate=None,
+                              target_seconds: Optional[float] = None) -> bytes:
+        """Synthesize raw 16-bit mono audio from phoneme ids (voice.py:140-185). New, all optional (Engine's ``Timing``):
+        ``durations`` -- one int per id, >= 0 = that id lasts exactly so many frames, -1 = predicted; ``rate`` -- one
+        multiplier of the predicted duration per id; ``target_seconds`` -- the utterance lasts
+        round(seconds * native rate / hop) frames exactly (the byte count follows from the output rate)."""
+        timing = self._timing(None if durations is None else [durations], None if rate is None else [rate],
+                              None if target_seconds is None else [target_seconds])
+        if timing is None:
+            r = self.session.synthesize(phoneme_ids, self._scales(length_scale, noise_scale, noise_w),
+                                        sid=self._speaker(speaker_id))
+        else:
+            sid = self._speaker(speaker_id)
+            r = self.session.synthesize_batch([phoneme_ids], self._scales(length_scale, noise_scale, noise_w),
+                                              sids=None if sid is None else [sid], timing=timing)
         return r.pcm[0].tobytes()
 
     def synthesize_ids_batch_to_raw(self, phoneme_id_lists: List[List[int]], speaker_ids=None,
                                     length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
-                                    noise_w: Optional[float] = None) -> List[bytes]:
+                                    noise_w: Optional[float] = None, durations=None, rate=None,
+                                    target_seconds=None) -> List[bytes]:
         """Batched extension: several utterances in one GPU call, each identical to its own
         synthesize_ids_to_raw() (same noise stream aside). ``length_scale`` / ``noise_scale`` / ``noise_w`` may each be
-        one value for every utterance or a list with one value per utterance (None entries: the voice's default)."""
+        one value for every utterance or a list with one value per utterance (None entries: the voice's default).
+        ``durations`` / ``rate`` / ``target_seconds``: lists with one entry per utterance as in synthesize_ids_to_raw
+        (None entries: nothing of that kind for that utterance)."""
         sids = None
         n = len(phoneme_id_lists)
         if self.config.num_speakers > 1:
@@ -172,5 +200,9 @@ class PiperVoice:
             scales = [self._scales(*(at(v, i) for v in knobs)) for i in range(n)]
         else:
             scales = self._scales(length_scale, noise_scale, noise_w)
-        r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
+        timing = self._timing(durations, rate, target_seconds)
+        if timing is None:
+            r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
+        else:
+            r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids, timing=timing)
         return [p.tobytes() for p in r.pcm]
