@@ -30,14 +30,15 @@ $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $(OBJ) -o $@
 
 emu: $(EMULIB)
-build/emu/%.o: $(CSRC)/%.cpp $(HDRS) tests/emu/hip_emu.h
+build/emu/%.o: $(CSRC)/%.cpp $(HDRS) $(wildcard tests/emu/*.h)
 	@mkdir -p $(dir $@)
 	$(CXX_EMU) $(EMUFLAGS) -c $< -o $@
 build/emu/hip_emu.o: tests/emu/hip_emu.cpp tests/emu/hip_emu.h
 	@mkdir -p $(dir $@)
 	$(CXX_EMU) $(EMUFLAGS) -c $< -o $@
+# (linked beside the target and moved into place: tests that find no library run `make emu` themselves, several at once)
 $(EMULIB): $(OBJ_EMU)
-	$(CXX_EMU) -shared -fPIC $(OBJ_EMU) -o $@
+	$(CXX_EMU) -shared -fPIC $(OBJ_EMU) -o $(@D)/tmp$$$$.$(@F) && mv -f $(@D)/tmp$$$$.$(@F) $@
 
 # tuning build: the same library with phase timestamps in the small kernels (scripts/stamps.py); never shipped
 stamps: piper_amd/libpiper_hip_stamps.so

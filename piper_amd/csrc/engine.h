@@ -236,28 +236,31 @@ class Engine {
 
   // ---- launches
   struct View { float* p; long bs; int cs; };
-  void conv(const PackedConv& pc, View x, View out, const int* lens, int len_mul, int Lmax, int epi,
-            float in_slope = 1.f, int act = 0, View res = View{nullptr, 0, 0},
-            View out2 = View{nullptr, 0, 0}, int mode = 0, float alpha = 1.f, const float* bias2 = nullptr,
-            int bias2_bs = 0);
+  // what a conv launch may set beyond its operands: input leaky-relu slope, output activation, residual, second output
+  // (WN skip rows), accumulate mode and scale of the MRF epilogues, a per-utterance bias (speaker conditioning)
+  struct ConvOpt {
+    float in_slope = 1.f; int act = 0; View res{nullptr, 0, 0}; View out2{nullptr, 0, 0}; int mode = 0; float alpha = 1.f;
+    const float* bias2 = nullptr; int bias2_bs = 0;
+  };
+  void conv(const PackedConv& pc, View x, View out, const int* lens, int len_mul, int Lmax, int epi, const ConvOpt& o);
+  void conv(const PackedConv& pc, View x, View out, const int* lens, int len_mul, int Lmax, int epi) { conv(pc, x, out, lens, len_mul, Lmax, epi, ConvOpt()); }
+  // One conv launch decided once (engine_internal.h: ConvPlan): kernel form, grid, LDS, whether it may ride in a grouped
+  // launch. A pure function of the packed conv, the column bound, the epilogue, B_, the policy and the matrix mode.
+  struct ConvPlan plan_conv(const PackedConv& pc, int Lmax, int epi, bool stage_tiled) const;
   // Grouped launches (conv_splitk_group_kernel): between group_begin() and group_end() conv() records the launch instead
   // of issuing it; group_end() issues all of them (<= 3 independent convs of one launch shape) as one launch.
   bool grouping_ = false;
-  bool stage_tiled_ = false;            // the MRF stage being issued takes the tiled kernel for every conv (a single utterance's stage past policy.h: group_maxb)
+  bool stage_tiled_ = false;            // the stage being issued keeps the tiled kernel (set for the stage's scope by issue_decoder from its schedule)
   bool group_tiled_ = false;            // the open group goes to the TILED kernel (conv_mfma_group_kernel), cfg = group_cfg_
   int group_cfg_ = 0;
   std::vector<struct ConvP> group_;
   double group_flops_ = 0, group_bytes_ = 0;
   int group_ncols_ = 0;
-  bool can_group(const PackedConv& pc, int ncols) const;
-  bool can_group_tiled(const PackedConv& pc, int ncols) const;
   void group_begin(bool tiled = false);
   void group_end();
   // the recorded convs as ONE GEMM over their concatenated K, summed: out = (sum_j (res_j + conv_j)) * alpha
   bool can_group_sum() const;
   void group_end_sum(View out, const float* bias_sum, float alpha);
-  enum { ROUTE_TILE = 0, ROUTE_SPLITK = 1, ROUTE_SPLITK16 = 2 };
-  int route(const PackedConv& pc, int ncols, int epi) const;
   void layer_norm(View in, View out, const float* g, const float* b, int C, const int* lens, int Lmax);
   // options of one DDSConv run: ConvFlow.pre folded into the first layer, a 1x1 conv (+ spline) fused after the last
   struct DdsOpt {
@@ -406,6 +409,11 @@ class Engine {
   bool mrf_geo(const UpStage& st, int len_mul, bool tail, MrfGeo& best) const;      // window geometry by the cost model
   void build_mrf(UpStage& st);
   void mrf(const UpStage& st, View x, View out, const int* lens, int len_mul, int Lmax, bool tail = false);
+  // How a generator stage's resblocks are issued (engine_launch.cpp, next to the grouping code): one fused launch, sibling
+  // convs grouped on the split-K or the tiled kernel, or conv by conv; `tiled`: every conv of the stage keeps the tiled kernel
+  enum StageForm { STAGE_FUSED, STAGE_GROUP_SPLITK, STAGE_GROUP_TILED, STAGE_CHAIN };
+  struct StageSchedule { StageForm form; bool tiled; };
+  StageSchedule stage_schedule(const UpStage& st, int Lmax, double fsum, bool buffers_fit) const;
   // Opt-in split-operand matrix modes PIPER_HIP_MATRIX = bf16x3 | f16x3 | bf16x6 (read at engine creation): the tiled conv
   // GEMMs of the coupling flow and the generator -- and, in the two-term modes, the fused MRF stages -- run on the 16-bit matrix
   // pipe with both f32 operands split into 16-bit terms (kernels/conv_bf3.h, mrf_split.h; 16 / 22 / 24 significand bits per

@@ -42,4 +42,25 @@ enum { CFG_A = 0, CFG_B = 1, CFG_C = 2, CFG_S = 3, CFG_G = 4, CFG_C2 = 5, CFG_B2
 static const int CFG_BM[] = {128, 64, 32, 64, 128, 32, 64};
 static const int CFG_BN[] = {128, 128, 128, 64, 64, 256, 256};
 
+// Workgroups of a launch on BM x BN tiles over `ncols` columns, `row_tiles` packed 32-row tiles and B utterances: the count
+// every policy threshold is asked with.
+static inline long tile_workgroups(int BM, int BN, int ncols, int row_tiles, int B) {
+  return (long)((ncols + BN - 1) / BN) * (row_tiles * 32 / BM) * B;
+}
+
+// One conv launch, decided once by Engine::plan_conv and carried out by Engine::conv (or recorded into the open group).
+enum ConvForm { CONV_TILE, CONV_SPLIT, CONV_1X1, CONV_SPLITK, CONV_SPLITK16, CONV_GATE12 };
+struct ConvPlan {
+  ConvForm form = CONV_TILE;  // tiled, split-operand tiled, one-tap direct, split-K, 16-column split-K, 12-column gate
+  int ncols = 0;              // grid bound in columns (one more for a ConvTranspose)
+  long blocks = 0;            // tile workgroups of the PACKED configuration: what the split-K / grouping thresholds were asked with
+  int cfg = 0, halo = 64;     // launched tile configuration (CFG_*; split-operand: 0 / 1 / 2) and x-slab halo (64 / 128)
+  int nw = 0, MT = 1, tgroups = 1, tpb = 1, nbuf = 2, up_vec = 0;      // split-K waves and row tiles per wave; ConvP fields
+  bool half = false;          // 16-column gate form on half a channel group per workgroup
+  dim3 grid;
+  size_t smem = 0;
+  bool group_splitk = false, group_tiled = false;      // may ride in a grouped split-K / grouped tiled launch ...
+  int group_cfg = CFG_S;                               // ... the latter on this tile configuration (CFG_C or CFG_S)
+};
+
 }  // namespace pe

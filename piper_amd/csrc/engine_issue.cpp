@@ -30,7 +30,6 @@ float* Engine::stage_a_enc_out() const { return (stage_a_ffn_fused() && (enc_.si
 // Grids are sized by the bucketed maximum length Tg_; kernels bound themselves by the device-side
 // per-utterance lengths, so the same captured graph serves every batch of that bucket.
 void Engine::issue_stage_a() {
-  stage_tiled_ = false;         // (a call that threw inside a generator stage must not leave it set)
   const int B = B_, Ts = Ts_, T = Tg_;
   const long bsH = (long)H_ * Ts;
   auto V = [&](float* p, int ch) { return View{p, (long)ch * Ts, Ts}; };
@@ -38,7 +37,6 @@ void Engine::issue_stage_a() {
   const View qkv = V(qkv_, 3 * H_), att = V(att_, H_), ffh = V(ffh_, FC_),
              stats = V(stats_, 2 * C_), xg = V(xg_, H_), dh = V(dh_, H_), dy = V(dy_, H_), dy2 = V(dy2_, H_),
              hproj = V(hproj_, 32);
-  const View none{nullptr, 0, 0};
   (void)bsH;
   double tsum = 0;
   for (int b = 0; b < B; ++b) tsum += tlens_h_[b];
@@ -180,7 +178,7 @@ void Engine::issue_stage_a() {
       cp.lens = d_tlens_;
       colchain(cp, B, T, 2.0 * tsum * e.o.macs_per_col);
     } else {
-      conv(e.o, att, y, d_tlens_, 1, T, EPI_RESADD, 1.f, ACT_NONE, x);
+      conv(e.o, att, y, d_tlens_, 1, T, EPI_RESADD, {.res = x});
     }
     if (!chain_o) layer_norm(y, x, e.g1, e.b1, H_, d_tlens_, T);
     }      // !attno
@@ -199,8 +197,8 @@ void Engine::issue_stage_a() {
       kend(khf);
       pend_bias = e.f2.bias;
     } else {
-      conv(e.f1, x, ffh, d_tlens_, 1, T, EPI_STORE, 1.f, ACT_RELU);
-      conv(e.f2, ffh, y, d_tlens_, 1, T, EPI_RESADD, 1.f, ACT_NONE, x);
+      conv(e.f1, x, ffh, d_tlens_, 1, T, EPI_STORE, {.act = ACT_RELU});
+      conv(e.f2, ffh, y, d_tlens_, 1, T, EPI_RESADD, {.res = x});
     }
     if (chain_q) { pg = e.g2; pb = e.b2; }
     else layer_norm(y, x, e.g2, e.b2, H_, d_tlens_, T);
@@ -245,7 +243,7 @@ void Engine::issue_stage_a() {
   if (!stacked &&
       !(chain_q && dp_pre16_ && conv1x1_col4(dp_pre16_, dp_pre_.bias, dp_pre_.rows, x, dy, d_tlens_, B, T, 2.0 * tsum * dp_pre_.macs_per_col,
                                              cb_dp, cond_bs_)))
-    conv(dp_pre_, x, dy, d_tlens_, 1, T, EPI_STORE, 1.f, ACT_NONE, none, none, 0, 1.f, cb_dp, cond_bs_);
+    conv(dp_pre_, x, dy, d_tlens_, 1, T, EPI_STORE, {.bias2 = cb_dp, .bias2_bs = cond_bs_});
   if (pol_.fuse_dp) {
     DdsOpt o;                      // dp.proj fused after the last DDSConv layer (models.py:65)
     o.post_w16 = dp_proj16_; o.post_bias = dp_proj_.bias; o.post_rows = dp_proj_.rows; o.post_out = xg;
@@ -311,7 +309,6 @@ void Engine::issue_stage_a() {
 // maximum frame count Fg_.
 void Engine::issue_flow() {
   const int B = B_, Ts = Ts_, Fmax = Fg_, Fs = Fs_;
-  const View none{nullptr, 0, 0};
   double fsum = 0;
   for (int b = 0; b < B; ++b) fsum += frames_h_[b];
   cols_frames_ = fsum;
@@ -366,7 +363,7 @@ void Engine::issue_flow() {
                           (ri + 1 >= rcls_.size() || (rcls_[ri + 1].pre.rows <= 192 && w4_of(rcls_[ri + 1].pre16)));
     for (int i = 0; i < nl; ++i) {
       const float* b2 = nspk_ > 1 ? cond_ + cond_off_wn_[ri] + (long)i * 2 * H_ : nullptr;
-      conv(r.in[i], fh, facts, lens_b_, 1, Fmax, EPI_GATE, 1.f, ACT_NONE, none, none, 0, 1.f, b2, cond_bs_);
+      conv(r.in[i], fh, facts, lens_b_, 1, Fmax, EPI_GATE, {.bias2 = b2, .bias2_bs = cond_bs_});
       if (rs_front && i == nl - 1) {
         fl += 2.0 * fsum * (r.in[i].macs_per_col + r.rs[i].macs_per_col);
         continue;
@@ -386,7 +383,7 @@ void Engine::issue_flow() {
         launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem(), stream_, cp);
         kend(kh4);
       } else {
-        conv(r.rs[i], facts, fh, lens_b_, 1, Fmax, EPI_WNRS, 1.f, ACT_NONE, none, fskip, i == 0 ? 1 : 0);
+        conv(r.rs[i], facts, fh, lens_b_, 1, Fmax, EPI_WNRS, {.out2 = fskip, .mode = i == 0 ? 1 : 0});
       }
       fl += 2.0 * fsum * (r.in[i].macs_per_col + r.rs[i].macs_per_col);
     }
@@ -511,9 +508,7 @@ void Engine::issue_window_rows(const ChunkRows& r) {
 // [B][C][Fs_]; `lens` the per-utterance frame counts in device memory; Fmax the grid bound.
 void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double fsum, bool zero_absmax, bool with_pcm16,
                            const float* cond, int cond_bs) {
-  stage_tiled_ = false;
   const int B = B_, Fs = Fs_;
-  const View none{nullptr, 0, 0};
   const float* cb_dec = nspk_ > 1 ? (cond ? cond : cond_ + cond_off_dec_) : nullptr;
   const int cb_dec_bs = cond ? cond_bs : cond_bs_;
   double fl = 0;
@@ -525,8 +520,7 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
   fl = 0;
   {
     View cur{hb_[0], (long)U_ * Fs, Fs};
-    conv(dec_pre_, View{const_cast<float*>(zsrc), (long)C_ * Fs, Fs}, cur, lens, 1, Fmax, EPI_STORE, 1.f, ACT_NONE, none, none, 0, 1.f,
-         cb_dec, cb_dec_bs);
+    conv(dec_pre_, View{const_cast<float*>(zsrc), (long)C_ * Fs, Fs}, cur, lens, 1, Fmax, EPI_STORE, {.bias2 = cb_dec, .bias2_bs = cb_dec_bs});
     fl += 2.0 * fsum * dec_pre_.macs_per_col;
     int mult = 1;
     int cur_buf = 0;
@@ -543,21 +537,19 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
       auto VS = [&](int bi) { return View{hb_[bi], (long)st.ch * Ls, (int)Ls}; };
       const View u = VS(ids[0]), ta = VS(ids[1]), tb = VS(ids[2]), tc = VS(ids[3]);
       const int Lmax = Fmax * mult;
-      // One launch per stage (mrf_kernel). Measured (profiles/r03_notes.md): ResBlock2 stages (medium / x-low) win at every
-      // batch size (B=1 -3 %, B=16 / 64 +4.5 % end to end over the conv-by-conv schedule); ResBlock1 stages (high) tie at
-      // one utterance and lose at batch (its 64-channel stage: 86 vs ~110 TFLOP/s for the conv GEMM kernel on K = 64 * 11
-      // convs), so those are fused for one or two utterances and on 32 channels only.
-      // (split matrix modes: the two-term modes run the fused stage on the 16-bit pipe, mrf_split_kernel; mode bf16x6 keeps the f32
-      // fused kernel for a few utterances and goes conv by conv on the 16-bit pipe from PIPER_HIP_BF3_MINF frames up)
-      const bool fuse = pol_.mrf_stage(st.mrf_ok, st.mrf_rb1, st.mrf_cp, fsum, matrix_bf3_,
-                                       matrix_bf3_ && pol_.mrf_split && st.mrf_wsplit != nullptr);
+      // fused, grouped or conv by conv (stage_schedule, engine_launch.cpp, with the measurements behind each)
+      const StageSchedule sched = stage_schedule(st, Lmax, fsum, (size_t)B * st.ch * Ls <= side_floats_);
+      const bool fuse = sched.form == STAGE_FUSED, grp_t = sched.form == STAGE_GROUP_TILED;
       // the last stage also runs the generator tail (conv_post, tanh, peak) on its MRF mean while it is still on chip
       const bool tail = fuse && pol_.mrf_tail && &st == &ups_.back() && st.mrf_cp == 32 && st.ch == post_cin_ && mult == hop_;
       // leaky_relu(0.1) -> ConvTranspose1d
       // (folding the up-conv into the stage kernel's prologue was built and measured: the window GEMM with its halo
       // recompute on the 209 workgroups of a single round costs what the launch costs -- profiles/r04_notes.md)
-      conv(st.up, cur, u, lens, Lin, Fmax * Lin, EPI_CONVT, 0.1f);
+      conv(st.up, cur, u, lens, Lin, Fmax * Lin, EPI_CONVT, {.in_slope = 0.1f});
       fl += 2.0 * fsum * Lin * st.up.macs_per_col;
+      // the resblock convs are planned with the schedule's choice of kernel (the up-conv is not), however the stage is left
+      struct Scope { bool& f; ~Scope() { f = false; } } scope{stage_tiled_};
+      stage_tiled_ = sched.tiled;
       // xs accumulates into the buffer that held the stage input (free once the up-conv is done)
       const View xs{hb_[cur_buf], (long)st.ch * Ls, (int)Ls};
       // One resblock chain, accumulated into xs with the MRF mode. `t` = {c1 output, ping, pong}.
@@ -569,13 +561,13 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
           // ResBlock1 (modules.py:301-314): x = x + c2(lrelu(c1(lrelu(x)))) per dilation
           const int np = (int)cv.size() / 2;
           for (int d = 0; d < np; ++d) {
-            conv(cv[2 * d], xin, t[0], lens, mult, Lmax, EPI_STORE, 0.1f);
+            conv(cv[2 * d], xin, t[0], lens, mult, Lmax, EPI_STORE, {.in_slope = 0.1f});
             if (d < np - 1) {
               const View nxt = (d & 1) ? t[2] : t[1];
-              conv(cv[2 * d + 1], t[0], nxt, lens, mult, Lmax, EPI_RESADD, 0.1f, ACT_NONE, xin);
+              conv(cv[2 * d + 1], t[0], nxt, lens, mult, Lmax, EPI_RESADD, {.in_slope = 0.1f, .res = xin});
               xin = nxt;
             } else {
-              conv(cv[2 * d + 1], t[0], dst, lens, mult, Lmax, last_epi, 0.1f, ACT_NONE, xin, none, accmode, inv_nk);
+              conv(cv[2 * d + 1], t[0], dst, lens, mult, Lmax, last_epi, {.in_slope = 0.1f, .res = xin, .mode = accmode, .alpha = inv_nk});
             }
             fl += 2.0 * fsum * mult * (cv[2 * d].macs_per_col + cv[2 * d + 1].macs_per_col);
           }
@@ -585,38 +577,15 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
           for (int d = 0; d < nc; ++d) {
             if (d < nc - 1) {
               const View nxt = (d & 1) ? t[2] : t[1];
-              conv(cv[d], xin, nxt, lens, mult, Lmax, EPI_RESADD, 0.1f, ACT_NONE, xin);
+              conv(cv[d], xin, nxt, lens, mult, Lmax, EPI_RESADD, {.in_slope = 0.1f, .res = xin});
               xin = nxt;
             } else {
-              conv(cv[d], xin, dst, lens, mult, Lmax, last_epi, 0.1f, ACT_NONE, xin, none, accmode, inv_nk);
+              conv(cv[d], xin, dst, lens, mult, Lmax, last_epi, {.in_slope = 0.1f, .res = xin, .mode = accmode, .alpha = inv_nk});
             }
             fl += 2.0 * fsum * mult * cv[d].macs_per_col;
           }
         }
       };
-      const size_t need = (size_t)B * st.ch * Ls;
-      const long blocks64 = (long)((Lmax + 63) / 64) * ((st.ch + 63) / 64) * B;
-      // grouped sibling launches are a single-utterance latency measure: measured -24 us (medium) / -4 % (high) at
-      // B=1, but +1..2 % at B=2 and B=4, where every conv already fills the chip on its own
-      stage_tiled_ = !fuse && pol_.stage_all_tiled(B, nk, blocks64);
-      bool grp = pol_.group_stage(B, nk, blocks64, need <= side_floats_);
-      for (auto& cv : st.rb) {
-        if (cv.size() != st.rb[0].size()) grp = false;
-        for (auto& c : cv) grp = grp && can_group(c, Lmax);
-      }
-      // the same schedule through the TILED kernel where one conv of the stage is only a few tiles per CU (the high voice's
-      // 128- / 64-channel stages of a single utterance: 834 tiles = 3.26 per CU)
-      bool grp_t = false;
-      if (!fuse && !grp) {
-        const PackedConv& c0 = st.rb[0][0];
-        const long tblocks = (long)((Lmax + CFG_BN[c0.cfg == CFG_C ? CFG_C : CFG_S] - 1) / CFG_BN[c0.cfg == CFG_C ? CFG_C : CFG_S]) *
-                             ((c0.rows + CFG_BM[c0.cfg == CFG_C ? CFG_C : CFG_S] - 1) / CFG_BM[c0.cfg == CFG_C ? CFG_C : CFG_S]) * B;
-        grp_t = pol_.group_stage_tiled(nk, tblocks, need <= side_floats_);
-        for (auto& cv : st.rb) {
-          if (cv.size() != st.rb[0].size()) grp_t = false;
-          for (auto& c : cv) grp_t = grp_t && can_group_tiled(c, Lmax) && (c.cfg == CFG_C) == (c0.cfg == CFG_C);
-        }
-      }
       if (fuse) {
         mrf(st, u, xs, lens, mult, Lmax, tail);
         for (auto& cv : st.rb)
@@ -625,7 +594,7 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
           tail_done = true;
           fl += 2.0 * fsum * hop_ * post_cin_ * POST_K;
         }
-      } else if (grp || grp_t) {
+      } else if (sched.form != STAGE_CHAIN) {
         // step d of every resblock in one grouped launch; each resblock keeps its own buffers, one pass sums them
         auto SV = [&](int k) { return View{side_[k], (long)st.ch * Ls, (int)Ls}; };
         View xin[3] = {u, u, u};
@@ -639,11 +608,11 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
             const View t0 = j == 0 ? tb : SV(4 * (j - 1)), t1 = j == 0 ? ta : SV(4 * (j - 1) + 1),
                        t2 = j == 0 ? tc : SV(4 * (j - 1) + 2), dst = j == 0 ? SV(8) : SV(4 * (j - 1) + 3);
             if (rb1 && !(d & 1)) {
-              conv(cv[d], xin[j], t0, lens, mult, Lmax, EPI_STORE, 0.1f);
+              conv(cv[d], xin[j], t0, lens, mult, Lmax, EPI_STORE, {.in_slope = 0.1f});
             } else {
               const int dd = rb1 ? d / 2 : d, nd = rb1 ? nsteps / 2 : nsteps;
               const View o = dd < nd - 1 ? ((dd & 1) ? t2 : t1) : dst;
-              conv(cv[d], rb1 ? t0 : xin[j], o, lens, mult, Lmax, EPI_RESADD, 0.1f, ACT_NONE, xin[j]);
+              conv(cv[d], rb1 ? t0 : xin[j], o, lens, mult, Lmax, EPI_RESADD, {.in_slope = 0.1f, .res = xin[j]});
               xin[j] = o;
             }
             fl += 2.0 * fsum * mult * cv[d].macs_per_col;
@@ -665,7 +634,6 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
           chain(j, t, xs, accmode);
         }
       }
-      stage_tiled_ = false;
       cur = xs;      // same buffer index cur_buf, new shape
     }
     prof_end(3, fl);

@@ -1,5 +1,5 @@
 // One launcher per kernel family: parameter structs, grids, shared-memory sizes, profile rows; which form a launch takes is
-// asked of the launch policy (policy.h).
+// asked of the launch policy (policy.h) -- for the convs once per launch, in plan_conv.
 #include "engine_internal.h"
 
 namespace pe {
@@ -8,19 +8,173 @@ namespace pe {
 // launch helpers
 // ------------------------------------------------------------------------------------------------
 
-// A conv that may ride in a grouped split-K launch: few enough column tiles that the launch is latency- rather than
-// throughput-bound, and a halo the 128-column slab covers.
-bool Engine::can_group(const PackedConv& pc, int ncols) const {
-  if (stage_tiled_) return false;
-  const long blocks = (long)((ncols + CFG_BN[pc.cfg] - 1) / CFG_BN[pc.cfg]) * (pc.mtiles * 32 / CFG_BM[pc.cfg]) * B_;
-  return pol_.groupable(pc.gate, pc.up != 0, blocks, (pc.ntaps - 1) * pc.dil, pc.Cin);
-}
-// The tiled kernel's grouped form: a plain conv (no gate, no ConvTranspose) that takes the tiled route anyway.
-bool Engine::can_group_tiled(const PackedConv& pc, int ncols) const {
-  return !pc.gate && pc.up == 0 && route(pc, ncols, EPI_STORE) == ROUTE_TILE && !(matrix_bf3_ && pc.wpb) &&
-         !pol_.one_tap_direct(pc.gate, false, pc.ntaps, pc.Cin) && (pc.ntaps - 1) * pc.dil <= 128;
-}
 static int tile_cfg_of(int cfg) { return cfg == CFG_C ? CFG_C : CFG_S; }      // non-gate configurations: 32 x 128 or 64 x 64 tiles
+static int slab_halo(int xhalo) { return xhalo <= 64 ? 64 : 128; }
+// dynamic LDS: the tiled kernels' nbuf slabs of KC channels x (BN + halo) columns; the split-K kernels' KC x xw slab per wave, or the waves' partial tiles
+static size_t tile_smem(int nbuf, int BN, int halo) { return (size_t)nbuf * KC * ((BN + halo + 63) / 64 * 64) * sizeof(float); }
+static size_t splitk_smem(int nw, int MT, int xw) { return std::max<size_t>((size_t)nw * KC * xw, (size_t)nw * MT * 16 * 64) * sizeof(float); }
+
+// Where a conv launch is decided: policy.h answers the questions, this function asks them once.
+ConvPlan Engine::plan_conv(const PackedConv& pc, int Lmax, int epi, bool stage_tiled) const {
+  ConvPlan pl;
+  const bool convt = epi == EPI_CONVT;
+  const int ncols = pl.ncols = convt ? Lmax + 1 : Lmax;
+  const int xhalo = (pc.ntaps - 1) * pc.dil, units = pc.nchunks * pc.ntaps;
+  // (the thresholds are asked with the PACKED configuration's tile count, whatever configuration is launched below)
+  pl.blocks = tile_workgroups(CFG_BM[pc.cfg], CFG_BN[pc.cfg], ncols, pc.mtiles, B_);
+  pl.halo = slab_halo(xhalo);
+  const bool to_splitk = !stage_tiled && pol_.splitk(pl.blocks, xhalo, pc.Cin);
+  const bool direct = pol_.one_tap_direct(pc.gate, convt, pc.ntaps, pc.Cin);
+  // A conv that may ride in a grouped split-K launch: few enough column tiles that the launch is latency- rather than
+  // throughput-bound, and a halo the 128-column slab covers. The tiled kernel's grouped form: a plain conv (no gate, no
+  // ConvTranspose) that takes the tiled route anyway.
+  pl.group_splitk = !stage_tiled && !convt && pol_.groupable(pc.gate, pc.up != 0, pl.blocks, xhalo, pc.Cin);
+  pl.group_tiled = !pc.gate && pc.up == 0 && !convt && !to_splitk && !(matrix_bf3_ && pc.wpb) && !direct && xhalo <= 128;
+  pl.group_cfg = tile_cfg_of(pc.cfg);
+  if (to_splitk && epi == EPI_GATE &&
+      pol_.gate_12col(pc.gate, pc.wpg4 != nullptr && pc.Cin == 192, pc.ntaps, pc.dil, tile_workgroups(32, 12, ncols, pc.split / 32, B_))) {
+    // the WN gate conv of a short call: 64 rows x 12 columns per workgroup on the 4x4x1 MFMA (kernels/gate4.h)
+    pl.form = CONV_GATE12;
+    pl.grid = dim3((ncols + 11) / 12, pc.split / 32, B_);
+    pl.smem = ((size_t)16 * 196 + (size_t)12 * 64 * 12) * sizeof(float);
+    return pl;
+  }
+  if (to_splitk) {
+    // few columns (one utterance through encoder / duration predictor / flow): split K across the waves
+    // waves per workgroup: 4 / 8 take whole chunks; the WN gate conv (6 chunks x 5 taps, two M tiles per wave)
+    // goes to 12 waves whose two halves split the taps: 15.8 -> 14.2 us per launch at B=1. Measured and not used:
+    // the same 12 waves for conv_pre (6 x 7) and FFN conv_2 (24 chunks) are slower than 8.
+    pl.form = CONV_SPLITK;
+    pl.MT = pc.gate ? 2 : 1;
+    pl.nw = pc.nchunks >= 5 ? 8 : 4;
+    if (pol_.splitk_12wave(pc.gate, units, pc.nchunks, pc.ntaps)) {
+      pl.nw = 12;
+      pl.tgroups = pc.nchunks <= 6 ? 2 : 1;
+    }
+    pl.grid = dim3((ncols + 31) / 32, pc.mtiles / pl.MT, B_);
+    pl.smem = splitk_smem(pl.nw, pl.MT, 64);
+    // MFMA-pipe bound inside the workgroup (>= 24 chunk-tap units) although most CUs idle: 16 output columns
+    if (pol_.splitk_16col(pc.wp16 != nullptr, convt, pc.gate, units)) {
+      pl.form = CONV_SPLITK16;
+      pl.grid.x = (ncols + 15) / 16;
+      // the gate conv of a SHORT utterance (<= 128 workgroups of 12 waves: half the CUs idle): half a channel group per
+      // workgroup on 6 waves (one chunk and every tap each, all five weight steps in flight at entry) is twice the
+      // workgroups with half the matrix time each -- 64 ids: 9.64 -> 8.37 us per launch; beyond one workgroup per CU it
+      // loses (128 ids, 324 workgroups: 9.77 -> 12.6 us; profiles/r04_notes.md, call 32)
+      pl.half = pol_.gate_half_groups(pc.gate, pc.nchunks, pc.ntaps, tile_workgroups(32 * pl.MT, 16, ncols, pc.mtiles, B_));
+      if (pl.half) pl.grid.y *= 2;
+      pl.nw = pc.gate ? (pl.half ? 6 : 12) : 8;
+      pl.tgroups = pc.gate ? (pl.half ? 1 : (pc.nchunks <= 6 ? 2 : 1)) : 1;
+      pl.smem = (size_t)pl.nw * KC * 64 * sizeof(float);
+    }
+    return pl;
+  }
+  // polyphase up-conv: a lane's four accumulator rows are consecutive output samples of one channel (stride a multiple of
+  // 4) or both phases of two channels (stride 2): stored as 16- / 8-byte pieces straight from the accumulators (the 32x32
+  // result layout of the tiled f32 kernel and of the split-operand kernel is the same). Measured against one 4-byte store
+  // per phase and against the tile transposed through LDS (profiles/r04_notes.md, calls 7 / 11).
+  pl.up_vec = (convt && pol_.convt_vec) ? (pc.up % 4 == 0 ? 4 : (pc.up == 2 ? 2 : 0)) : 0;
+  if (matrix_bf3_ && pc.wpb && xhalo <= 128) {
+    // split matrix modes (bf16x3 / f16x3 / bf16x6): 128 x 128 / 64 x 128 / 32 x 256 tiles (two 32x32 MFMA tiles per wave at least: the bf16 pipe
+    // is fast enough that operand traffic per MFMA matters more than workgroup count)
+    static const int BF3_BM[] = {128, 64, 32}, BF3_BN[] = {128, 128, 256};
+    const int bc = pl.cfg = pc.cfg == CFG_A ? 0 : (pc.cfg == CFG_B ? 1 : 2);
+    if (pc.gate && bc == 2) throw std::runtime_error("internal: gate conv packed for 32-row blocks");
+    pl.form = CONV_SPLIT;
+    pl.nbuf = pc.nchunks == 1 ? 1 : 2;
+    const int nterm = matrix_sm_ == 2 ? 3 : 2;
+    pl.smem = (size_t)pl.nbuf * nterm * 64 * ((BF3_BN[bc] + pl.halo + 63) / 64 * 64);       // [terms][4 k groups][XS] x 16 B
+    pl.grid = dim3((ncols + BF3_BN[bc] - 1) / BF3_BN[bc], pc.mtiles * 32 / BF3_BM[bc], B_);
+    return pl;
+  }
+  if (direct) {
+    // one tap: nothing to share between the MFMA's k rows, so the B operand skips LDS (kernels/conv1x1.h)
+    pl.form = CONV_1X1;
+    pl.grid = dim3((ncols + 63) / 64, (pc.mtiles + 1) / 2, B_);
+    return pl;
+  }
+  // 32x32 wave tiles everywhere (64x64 / 32x128 workgroup tiles; the gate form pairs two row tiles per wave): measured in
+  // rounds 1-3 against 128x128, 64x128 and 256-column tiles at every batch size -- latency here is hidden across
+  // workgroups, occupancy beats register reuse (profiles/r01_ablation.txt, r02_notes.md); the larger instantiations are gone
+  pl.cfg = pc.cfg == CFG_A ? (pc.gate ? CFG_G : CFG_S) : ((pc.cfg == CFG_B && !pc.gate) ? CFG_S : pc.cfg);
+  const int BM = CFG_BM[pl.cfg], BN = CFG_BN[pl.cfg];
+  // Column tiles walked by one workgroup. Measured on MI355X (profiles/r01_tpb_sweep.txt): with 2-3
+  // workgroups resident per CU, one tile per workgroup (latency hidden across workgroups) beats walking
+  // several tiles with the in-kernel prefetch pipeline at every batch size, so the default is 1; the
+  // multi-tile path stays available through PIPER_HIP_TPB.
+  pl.tpb = pol_.tiles_per_workgroup();
+  pl.grid = dim3(((ncols + BN - 1) / BN + pl.tpb - 1) / pl.tpb, pc.mtiles * 32 / BM, B_);
+  if (xhalo > 128) throw std::runtime_error("conv halo (kernel-1)*dilation > 128 is not supported");
+  // one x slab when the workgroup only ever stages one (single chunk, single tile): more workgroups per CU
+  pl.nbuf = (pl.tpb == 1 && pc.nchunks == 1) ? 1 : 2;
+  pl.smem = tile_smem(pl.nbuf, BN, pl.halo);
+  return pl;
+}
+
+// The level-2 profile row of a planned launch: the instantiation exactly as rocprofv3 prints it (minus spaces), as
+// kernels/launch_conv.cpp / launch_bf3.cpp pick it from the same plan (tests/test_launch_plan_emu.py holds the two together).
+// PIPER_HIP_PROF_SITES=1 (tuning aid): one row per conv SHAPE of the tiled and one-tap kernels instead.
+static std::string conv_row_name(const ConvPlan& pl, const PackedConv& pc, int sm, bool sites, int epi, int len_mul) {
+  static const char* knames[] = {"2,2,2,2,8", "1,4,2,1,16", "1,4,1,1,16", "2,2,1,1,16", "2,2,2,1,16", "1,4,1,2,16", "1,4,2,2,8"};
+  static const char* bnames[] = {"2,2,2,2", "2,2,1,2", "1,4,1,2"};
+  const char* g = pc.gate ? "true" : "false";
+  char nm[96];
+  int n = 0;
+  switch (pl.form) {
+    case CONV_GATE12: return "gate4_kernel";
+    case CONV_SPLITK:
+      snprintf(nm, sizeof(nm), "conv_splitk_kernel<%d,%s,%d,%d>", pl.MT, g, pl.nw, pc.gate ? (pl.nw == 12 ? 2 : 3) : 4);
+      break;
+    case CONV_SPLITK16:      // (the default GT = 4 included)
+      snprintf(nm, sizeof(nm), "conv_splitk16_kernel<%s>", pc.gate ? (pl.half ? "true,6,5,2" : "true,12,2,4") : "false,8,4,4");
+      break;
+    case CONV_SPLIT:
+      snprintf(nm, sizeof(nm), "conv_split_kernel<%d,%s,%s,%d>", sm, (pc.gate && pl.cfg == 1) ? "1,4,2,1" : bnames[pl.cfg], g, pl.halo);
+      break;
+    case CONV_1X1:
+      n = snprintf(nm, sizeof(nm), "conv1x1_kernel<1>");
+      if (sites) snprintf(nm + n, sizeof(nm) - n, "|%dx%dx%d e%d L%d", pc.rows, pc.Cin, pc.ntaps, epi, len_mul);
+      break;
+    case CONV_TILE:
+      n = snprintf(nm, sizeof(nm), "conv_mfma_kernel<%s,%s,%d>", knames[pl.cfg], g, pl.halo);
+      if (sites) snprintf(nm + n, sizeof(nm) - n, "|%dx%dx%d d%d e%d L%d", pc.rows, pc.Cin, pc.ntaps, pc.dil, epi, len_mul);
+      break;
+  }
+  return nm;
+}
+
+// How the resblocks of a generator stage are issued, and the only place that decides whether the stage keeps the tiled
+// kernel. One launch per stage (mrf_kernel). Measured (profiles/r03_notes.md): ResBlock2 stages (medium / x-low) win at every
+// batch size (B=1 -3 %, B=16 / 64 +4.5 % end to end over the conv-by-conv schedule); ResBlock1 stages (high) tie at
+// one utterance and lose at batch (its 64-channel stage: 86 vs ~110 TFLOP/s for the conv GEMM kernel on K = 64 * 11
+// convs), so those are fused for one or two utterances and on 32 channels only.
+// (split matrix modes: the two-term modes run the fused stage on the 16-bit pipe, mrf_split_kernel; mode bf16x6 keeps the f32
+// fused kernel for a few utterances and goes conv by conv on the 16-bit pipe from PIPER_HIP_BF3_MINF frames up)
+// Grouped sibling launches are a single-utterance latency measure: measured -24 us (medium) / -4 % (high) at B=1, but
+// +1..2 % at B=2 and B=4, where every conv already fills the chip on its own; the same schedule goes through the TILED
+// kernel where one conv of the stage is only a few tiles per CU (the high voice's 128- / 64-channel stages of a single
+// utterance: 834 tiles = 3.26 per CU).
+Engine::StageSchedule Engine::stage_schedule(const UpStage& st, int Lmax, double fsum, bool buffers_fit) const {
+  if (pol_.mrf_stage(st.mrf_ok, st.mrf_rb1, st.mrf_cp, fsum, matrix_bf3_, matrix_bf3_ && pol_.mrf_split && st.mrf_wsplit != nullptr))
+    return {STAGE_FUSED, false};
+  const int nk = arch_[A_NRB];
+  const long blocks64 = tile_workgroups(64, 64, Lmax, rup(st.ch, 64) / 32, B_);
+  const bool tiled = pol_.stage_all_tiled(B_, nk, blocks64);
+  const PackedConv& c0 = st.rb[0][0];
+  const int tc = tile_cfg_of(c0.cfg);
+  bool grp = pol_.group_stage(B_, nk, blocks64, buffers_fit);
+  bool grp_t = pol_.group_stage_tiled(nk, tile_workgroups(CFG_BM[tc], CFG_BN[tc], Lmax, rup(c0.rows, CFG_BM[tc]) / 32, B_), buffers_fit);
+  for (auto& cv : st.rb) {
+    if (cv.size() != st.rb[0].size()) grp = grp_t = false;
+    for (auto& c : cv) {
+      const ConvPlan pl = plan_conv(c, Lmax, EPI_STORE, tiled);
+      grp = grp && pl.group_splitk;
+      grp_t = grp_t && pl.group_tiled && pl.group_cfg == tc;
+    }
+  }
+  return {grp ? STAGE_GROUP_SPLITK : (grp_t ? STAGE_GROUP_TILED : STAGE_CHAIN), tiled};
+}
+
 void Engine::group_begin(bool tiled) {
   grouping_ = true;
   group_tiled_ = tiled;
@@ -45,8 +199,7 @@ void Engine::group_end() {
     g.n = n;
     g.B = B_;
     const int cfg = group_cfg_, BM = CFG_BM[cfg], BN = CFG_BN[cfg];
-    const int HALO = xhalo <= 64 ? 64 : 128;
-    const size_t smem = (size_t)2 * KC * ((BN + HALO + 63) / 64 * 64) * sizeof(float);
+    const int HALO = slab_halo(xhalo);
     const dim3 grid((group_ncols_ + BN - 1) / BN, (rows + BM - 1) / BM, n * B_);
     int kh = -1;
     if (prof_level_ >= 2) {
@@ -54,7 +207,7 @@ void Engine::group_end() {
       snprintf(nm, sizeof(nm), "conv_mfma_group_kernel<%s,%d>", cfg == CFG_C ? "1,4,1,1,16" : "2,2,1,1,16", HALO);
       kh = kbegin(krow(std::string(nm)), group_flops_, group_bytes_);
     }
-    launch::conv_tile_group(cfg, HALO, grid, smem, ls_, g);
+    launch::conv_tile_group(cfg, HALO, grid, tile_smem(2, BN, HALO), ls_, g);
     kend(kh);
     group_.clear();
     return;
@@ -77,13 +230,11 @@ void Engine::group_end() {
     if (!n) continue;
     g.n = n;
     g.B = B_;
-    const int XW = wide ? 128 : 64;
-    const size_t smem = std::max<size_t>((size_t)NW * KC * XW, (size_t)NW * 16 * 64) * sizeof(float);
     const dim3 grid((group_ncols_ + 31) / 32, mt, n * B_);
     const double share = (double)n / (double)group_.size();
     const int kh = kbegin(prof_level_ >= 2 ? krow(wide ? "conv_splitk_group_kernel<4,2,128>" : "conv_splitk_group_kernel<4,2,64>") : 0,
                           group_flops_ * share, group_bytes_ * share);
-    launch::conv_group(wide != 0, grid, smem, ls_, g);
+    launch::conv_group(wide != 0, grid, splitk_smem(NW, 1, wide ? 128 : 64), ls_, g);
     kend(kh);
   }
   group_.clear();
@@ -113,220 +264,71 @@ void Engine::group_end_sum(View out, const float* bias_sum, float alpha) {
   q.out = out.p; q.o_bs = out.bs; q.o_cs = out.cs;
   q.epi = EPI_ACCUM; q.mode = 3; q.alpha = alpha;      // (acc + bias + residuals) * alpha, nothing read back
   q.tgroups = 1;
-  constexpr int NW = 4;
-  const size_t smem = std::max<size_t>((size_t)NW * KC * 128, (size_t)NW * 16 * 64) * sizeof(float);
   const dim3 grid((group_ncols_ + 31) / 32, (q.rows + 31) / 32, B_);
   // (a 4-deep weight ring measured slower than 2: hifigan stage 0.345 vs 0.338 ms)
   // (a 16-deep ring -- a wave's whole K range in flight at entry, 256 registers, one workgroup per CU -- measured 59 us
   // against 30: profiles/r04_notes.md)
   const int kh = kbegin(prof_level_ >= 2 ? krow("conv_splitk_sum_kernel<4,2>") : 0, group_flops_, group_bytes_);
-  launch::conv_group_sum(grid, smem, ls_, q);
+  launch::conv_group_sum(grid, splitk_smem(4, 1, 128), ls_, q);
   kend(kh);
   group_.clear();
 }
 
-// Which kernel family a conv launch goes to (the policy conv() applies).
-int Engine::route(const PackedConv& pc, int ncols, int epi) const {
-  const int cfg = pc.cfg;
-  const long blocks = (long)((ncols + CFG_BN[cfg] - 1) / CFG_BN[cfg]) * (pc.mtiles * 32 / CFG_BM[cfg]) * B_;
-  if (stage_tiled_ || !pol_.splitk(blocks, (pc.ntaps - 1) * pc.dil, pc.Cin)) return ROUTE_TILE;
-  return pol_.splitk_16col(pc.wp16 != nullptr, epi == EPI_CONVT, pc.gate, pc.nchunks * pc.ntaps) ? ROUTE_SPLITK16 : ROUTE_SPLITK;
+// algorithmic FLOPs of a conv launch over `cols` valid columns: 2 * MACs per output column; algorithmic bytes: every input
+// channel and every output row once per column, residual / read-modify-write operands once more each, the weights once
+static void conv_cost(const PackedConv& pc, int epi, int mode, double cols, double& flops, double& bytes) {
+  const bool rd_res = epi == EPI_RESADD || epi == EPI_ACCUM;
+  const bool rd_old = epi == EPI_SUBFROM || epi == EPI_WNRS || (epi == EPI_ACCUM && (mode == 1 || mode == 2));
+  const double out_rows = epi == EPI_GATE ? pc.split : pc.rows;
+  flops = 2.0 * pc.macs_per_col * cols;
+  bytes = 4.0 * (cols * (pc.Cin + out_rows * (1 + (rd_res ? 1 : 0) + (rd_old ? 1 : 0))) + (double)pc.rows * pc.Cin * pc.ntaps);
 }
-void Engine::conv(const PackedConv& pc, View x, View out, const int* lens, int len_mul, int Lmax, int epi,
-                  float in_slope, int act, View res, View out2, int mode, float alpha, const float* bias2,
-                  int bias2_bs) {
+
+void Engine::conv(const PackedConv& pc, View x, View out, const int* lens, int len_mul, int Lmax, int epi, const ConvOpt& o) {
+  if ((epi == EPI_GATE) != pc.gate) throw std::runtime_error("internal: gate epilogue/packing mismatch");
   ConvP p;
   p.x = x.p; p.x_bs = x.bs; p.x_cs = x.cs;
   p.wp = pc.wp; p.wp16 = pc.wp16; p.wpb = pc.wpb; p.wunscale = pc.wunscale; p.wpg4 = nullptr; p.bias = pc.bias;
-  p.bias2 = bias2; p.bias2_bs = bias2_bs;
+  p.bias2 = o.bias2; p.bias2_bs = o.bias2_bs;
   p.out = out.p; p.o_bs = out.bs; p.o_cs = out.cs;
-  p.res = res.p; p.r_bs = res.bs; p.r_cs = res.cs;
-  p.out2 = out2.p; p.o2_bs = out2.bs; p.o2_cs = out2.cs;
+  p.res = o.res.p; p.r_bs = o.res.bs; p.r_cs = o.res.cs;
+  p.out2 = o.out2.p; p.o2_bs = o.out2.bs; p.o2_cs = o.out2.cs;
   p.lens = lens; p.len_mul = len_mul;
   p.Cin = pc.Cin; p.rows = pc.rows; p.nchunks = pc.nchunks;
-  p.ntaps = pc.ntaps; p.dil = pc.dil; p.padl = pc.padl;
-  p.xhalo = (pc.ntaps - 1) * pc.dil;
-  p.in_slope = in_slope;
-  p.epi = epi; p.act = act;
+  p.ntaps = pc.ntaps; p.dil = pc.dil; p.padl = pc.padl; p.xhalo = (pc.ntaps - 1) * pc.dil;
+  p.in_slope = o.in_slope; p.epi = epi; p.act = o.act; p.mode = o.mode; p.alpha = o.alpha;
   p.split = (epi == EPI_GATE) ? pc.split : (epi == EPI_WNRS ? (pc.rows > H_ ? H_ : 0) : 0);
-  p.up = pc.up; p.padT = pc.padT;
-  p.up_magic = pc.up ? (unsigned)((0x100000000ULL + pc.up - 1) / pc.up) : 0u;
-  p.up_vec = 0;
-  p.mode = mode; p.alpha = alpha;
-  p.tpb = 1;
-  p.tgroups = 1;
-  if ((epi == EPI_GATE) != pc.gate) throw std::runtime_error("internal: gate epilogue/packing mismatch");
-
-  const int ncols = (epi == EPI_CONVT) ? Lmax + 1 : Lmax;
-  int cfg = pc.cfg;
+  p.up = pc.up; p.padT = pc.padT; p.up_magic = pc.up ? (unsigned)((0x100000000ULL + pc.up - 1) / pc.up) : 0u;
+  p.up_vec = 0; p.tpb = 1; p.tgroups = 1;      // (what a grouped launch runs with; a launch of its own takes the plan's)
   double kflops = 0, kbytes = 0;
   if (prof_level_ >= 2) {
-    // algorithmic FLOPs of this launch: 2 * MACs per output column * valid columns over the batch
     const std::vector<int32_t>& lh = (lens == d_tlens_) ? tlens_h_ : frames_h_;
     double cols = 0;
-    for (int b = 0; b < B_; ++b) cols += (double)lh[b] * len_mul;
-    kflops = 2.0 * pc.macs_per_col * cols;
-    // algorithmic bytes: every input channel and every output row once per column, residual / read-modify-write
-    // operands once more each, the weights once per launch
-    const bool rd_res = epi == EPI_RESADD || epi == EPI_ACCUM;
-    const bool rd_old = epi == EPI_SUBFROM || epi == EPI_WNRS || (epi == EPI_ACCUM && (mode == 1 || mode == 2));
-    const double out_rows = epi == EPI_GATE ? pc.split : pc.rows;
-    kbytes = 4.0 * (cols * (pc.Cin + out_rows * (1 + (rd_res ? 1 : 0) + (rd_old ? 1 : 0))) +
-                    (double)pc.rows * pc.Cin * pc.ntaps);
+    for (int b = 0; b < B_; ++b) cols += (double)lh[b] * len_mul;      // valid columns over the batch
+    conv_cost(pc, epi, o.mode, cols, kflops, kbytes);
   }
-  const long blocks = (long)((ncols + CFG_BN[cfg] - 1) / CFG_BN[cfg]) * (pc.mtiles * 32 / CFG_BM[cfg]) * B_;
-  if (grouping_ && group_tiled_) {
-    const int tc = tile_cfg_of(cfg);
-    if (!can_group_tiled(pc, ncols) || epi == EPI_CONVT || epi == EPI_GATE || group_.size() >= 3 ||
-        (!group_.empty() && (group_ncols_ != ncols || group_cfg_ != tc)))
-      throw std::runtime_error("internal: conv does not fit a grouped tiled launch");
-    group_cfg_ = tc;
-    p.tpb = 1;
-    group_.push_back(p);
-    group_ncols_ = ncols;
-    group_flops_ += kflops;
-    group_bytes_ += kbytes;
-    return;
-  }
+  const ConvPlan pl = plan_conv(pc, Lmax, epi, stage_tiled_);
   if (grouping_) {
-    if (!can_group(pc, ncols) || epi == EPI_CONVT || epi == EPI_GATE || group_.size() >= 3 ||
-        (!group_.empty() && group_ncols_ != ncols))
-      throw std::runtime_error("internal: conv does not fit a grouped launch");
-    p.tgroups = 1;
+    if (!(group_tiled_ ? pl.group_tiled : pl.group_splitk) || group_.size() >= 3 ||
+        (!group_.empty() && (group_ncols_ != pl.ncols || (group_tiled_ && group_cfg_ != pl.group_cfg))))
+      throw std::runtime_error(group_tiled_ ? "internal: conv does not fit a grouped tiled launch" : "internal: conv does not fit a grouped launch");
+    group_cfg_ = pl.group_cfg;
     group_.push_back(p);
-    group_ncols_ = ncols;
-    group_flops_ += kflops;
-    group_bytes_ += kbytes;
+    group_ncols_ = pl.ncols;
+    group_flops_ += kflops; group_bytes_ += kbytes;
     return;
   }
-  const bool to_splitk = !stage_tiled_ && pol_.splitk(blocks, p.xhalo, pc.Cin);
-  if (to_splitk && epi == EPI_GATE &&
-      pol_.gate_12col(pc.gate, pc.wpg4 != nullptr && pc.Cin == 192, pc.ntaps, pc.dil, (long)((ncols + 11) / 12) * (pc.split / 32) * B_)) {
-    // the WN gate conv of a short call: 64 rows x 12 columns per workgroup on the 4x4x1 MFMA (kernels/gate4.h)
-    p.wpg4 = pc.wpg4;
-    const dim3 grid((ncols + 11) / 12, pc.split / 32, B_);
-    const size_t smem = ((size_t)16 * 196 + (size_t)12 * 64 * 12) * sizeof(float);
-    const int kh = kbegin(prof_level_ >= 2 ? krow("gate4_kernel") : 0, kflops, kbytes);
-    launch::gate4(grid, smem, ls_, p);
-    kend(kh);
-    return;
+  p.up_vec = pl.up_vec; p.tpb = pl.tpb; p.tgroups = pl.tgroups;
+  if (pl.form == CONV_GATE12) p.wpg4 = pc.wpg4;
+  const int kh = prof_level_ >= 2 ? kbegin(krow(conv_row_name(pl, pc, matrix_sm_, pol_.prof_sites != 0, epi, len_mul)), kflops, kbytes) : -1;
+  switch (pl.form) {
+    case CONV_GATE12: launch::gate4(pl.grid, pl.smem, ls_, p); break;
+    case CONV_SPLITK: launch::conv_splitk(pc.gate, pl.nw, pl.grid, pl.smem, ls_, p); break;
+    case CONV_SPLITK16: launch::conv_splitk16(pc.gate, pl.grid, pl.smem, ls_, p, pl.half); break;
+    case CONV_SPLIT: launch::conv_bf3(matrix_sm_, pl.cfg, pc.gate, pl.halo, pl.grid, pl.smem, ls_, p); break;
+    case CONV_1X1: launch::conv1x1(pl.grid, ls_, p); break;
+    case CONV_TILE: launch::conv_tile(pl.cfg, pc.gate, pl.halo, pl.grid, pl.smem, ls_, p); break;
   }
-  if (to_splitk) {
-    // few columns (one utterance through encoder / duration predictor / flow): split K across the waves
-    const int MT = pc.gate ? 2 : 1;
-    // waves per workgroup: 4 / 8 take whole chunks; the WN gate conv (6 chunks x 5 taps, two M tiles per wave)
-    // goes to 12 waves whose two halves split the taps: 15.8 -> 14.2 us per launch at B=1. Measured and not used:
-    // the same 12 waves for conv_pre (6 x 7) and FFN conv_2 (24 chunks) are slower than 8.
-    const int units = pc.nchunks * pc.ntaps;
-    int NW = pc.nchunks >= 5 ? 8 : 4;
-    p.tgroups = 1;
-    if (pol_.splitk_12wave(pc.gate, units, pc.nchunks, pc.ntaps)) {
-      NW = 12;
-      p.tgroups = pc.nchunks <= 6 ? 2 : 1;
-    }
-    dim3 grid((ncols + 31) / 32, pc.mtiles / MT, B_);
-    const size_t smem = std::max<size_t>((size_t)NW * KC * 64, (size_t)NW * MT * 16 * 64) * sizeof(float);
-    const bool k16 = pol_.splitk_16col(pc.wp16 != nullptr, epi == EPI_CONVT, pc.gate, units);
-    // profile rows carry the instantiation exactly as rocprofv3 prints it (minus spaces)
-    int kh = -1;
-    if (prof_level_ >= 2) {
-      char nm[96];
-      if (k16) snprintf(nm, sizeof(nm), "conv_splitk16_kernel<%s>", pc.gate ? (pol_.gate_half_groups(true, pc.nchunks, pc.ntaps, (long)((ncols + 15) / 16) * (pc.mtiles / MT) * B_) ? "true,6,5,2" : "true,12,2,4") : "false,8,4,4");      // (as rocprofv3 prints them: the default GT = 4 included)
-      else snprintf(nm, sizeof(nm), "conv_splitk_kernel<%d,%s,%d,%d>", MT, pc.gate ? "true" : "false", NW,
-                    pc.gate ? (NW == 12 ? 2 : 3) : 4);
-      kh = kbegin(krow(std::string(nm)), kflops, kbytes);
-    }
-    // MFMA-pipe bound inside the workgroup (>= 24 chunk-tap units) although most CUs idle: 16 output columns
-    if (k16) {
-      dim3 grid16((ncols + 15) / 16, pc.mtiles / MT, B_);
-      // the gate conv of a SHORT utterance (<= 128 workgroups of 12 waves: half the CUs idle): half a channel group per
-      // workgroup on 6 waves (one chunk and every tap each, all five weight steps in flight at entry) is twice the
-      // workgroups with half the matrix time each -- 64 ids: 9.64 -> 8.37 us per launch; beyond one workgroup per CU it
-      // loses (128 ids, 324 workgroups: 9.77 -> 12.6 us; profiles/r04_notes.md, call 32)
-      const bool half = pol_.gate_half_groups(pc.gate, pc.nchunks, pc.ntaps, (long)grid16.x * grid16.y * grid16.z);
-      if (half) grid16.y *= 2;
-      const int nw = pc.gate ? (half ? 6 : 12) : 8;
-      p.tgroups = pc.gate ? (half ? 1 : (pc.nchunks <= 6 ? 2 : 1)) : 1;
-      launch::conv_splitk16(pc.gate, grid16, (size_t)nw * KC * 64 * sizeof(float), ls_, p, half);
-      kend(kh);
-      return;
-    }
-    launch::conv_splitk(pc.gate, NW, grid, smem, ls_, p);
-    kend(kh);
-    return;
-  }
-  // polyphase up-conv: a lane's four accumulator rows are consecutive output samples of one channel (stride a multiple of
-  // 4) or both phases of two channels (stride 2): stored as 16- / 8-byte pieces straight from the accumulators (the 32x32
-  // result layout of the tiled f32 kernel and of the split-operand kernel is the same). Measured against one 4-byte store
-  // per phase and against the tile transposed through LDS (profiles/r04_notes.md, calls 7 / 11).
-  p.up_vec = (epi == EPI_CONVT && pol_.convt_vec) ? (pc.up % 4 == 0 ? 4 : (pc.up == 2 ? 2 : 0)) : 0;
-  if (matrix_bf3_ && pc.wpb && p.xhalo <= 128) {
-    // split matrix modes (bf16x3 / f16x3 / bf16x6): 128 x 128 / 64 x 128 / 32 x 256 tiles (two 32x32 MFMA tiles per wave at least: the bf16 pipe
-    // is fast enough that operand traffic per MFMA matters more than workgroup count)
-    static const int BF3_BM[] = {128, 64, 32}, BF3_BN[] = {128, 128, 256};
-    static const char* bnames[] = {"2,2,2,2", "2,2,1,2", "1,4,1,2"};
-    const int bc = cfg == CFG_A ? 0 : (cfg == CFG_B ? 1 : 2);
-    if (pc.gate && bc == 2) throw std::runtime_error("internal: gate conv packed for 32-row blocks");
-    const int BM = BF3_BM[bc], BN = BF3_BN[bc];
-    const int HALO = p.xhalo <= 64 ? 64 : 128;
-    const int nbuf = pc.nchunks == 1 ? 1 : 2;
-    const int nterm = matrix_sm_ == 2 ? 3 : 2;
-    const size_t smem = (size_t)nbuf * nterm * 64 * ((BN + HALO + 63) / 64 * 64);       // [terms][4 k groups][XS] x 16 B
-    dim3 grid((ncols + BN - 1) / BN, pc.mtiles * 32 / BM, B_);
-    int kh = -1;
-    if (prof_level_ >= 2) {
-      char nm[96];
-      snprintf(nm, sizeof(nm), "conv_split_kernel<%d,%s,%s,%d>", matrix_sm_, (pc.gate && bc == 1) ? "1,4,2,1" : bnames[bc],
-               pc.gate ? "true" : "false", HALO);
-      kh = kbegin(krow(std::string(nm)), kflops, kbytes);
-    }
-    launch::conv_bf3(matrix_sm_, bc, pc.gate, HALO, grid, smem, ls_, p);
-    kend(kh);
-    return;
-  }
-  if (pol_.one_tap_direct(pc.gate, epi == EPI_CONVT, pc.ntaps, pc.Cin)) {
-    // one tap: nothing to share between the MFMA's k rows, so the B operand skips LDS (kernels/conv1x1.h)
-    const dim3 grid((ncols + 63) / 64, (pc.mtiles + 1) / 2, B_);
-    int kh = -1;
-    if (prof_level_ >= 2) {
-      char nm[96];
-      int n = snprintf(nm, sizeof(nm), "conv1x1_kernel<1>");
-      if (pol_.prof_sites) snprintf(nm + n, sizeof(nm) - n, "|%dx%dx%d e%d L%d", pc.rows, pc.Cin, pc.ntaps, epi, len_mul);
-      kh = kbegin(krow(std::string(nm)), kflops, kbytes);
-    }
-    launch::conv1x1(grid, ls_, p);
-    kend(kh);
-    return;
-  }
-  // 32x32 wave tiles everywhere (64x64 / 32x128 workgroup tiles; the gate form pairs two row tiles per wave): measured in
-  // rounds 1-3 against 128x128, 64x128 and 256-column tiles at every batch size -- latency here is hidden across
-  // workgroups, occupancy beats register reuse (profiles/r01_ablation.txt, r02_notes.md); the larger instantiations are gone
-  if (cfg == CFG_A) cfg = pc.gate ? CFG_G : CFG_S;
-  else if (cfg == CFG_B && !pc.gate) cfg = CFG_S;
-  const int BM = CFG_BM[cfg], BN = CFG_BN[cfg];
-  const int ntile = (ncols + BN - 1) / BN, mblocks = pc.mtiles * 32 / BM;
-  // Column tiles walked by one workgroup. Measured on MI355X (profiles/r01_tpb_sweep.txt): with 2-3
-  // workgroups resident per CU, one tile per workgroup (latency hidden across workgroups) beats walking
-  // several tiles with the in-kernel prefetch pipeline at every batch size, so the default is 1; the
-  // multi-tile path stays available through PIPER_HIP_TPB.
-  const int tpb = pol_.tiles_per_workgroup();
-  p.tpb = tpb;
-  dim3 grid((ntile + tpb - 1) / tpb, mblocks, B_);
-  if (p.xhalo > 128) throw std::runtime_error("conv halo (kernel-1)*dilation > 128 is not supported");
-  // one x slab when the workgroup only ever stages one (single chunk, single tile): more workgroups per CU
-  const int nbuf = (tpb == 1 && pc.nchunks == 1) ? 1 : 2;
-  const int HALO = p.xhalo <= 64 ? 64 : 128;
-  const size_t smem = (size_t)nbuf * KC * ((BN + HALO + 63) / 64 * 64) * sizeof(float);
-  static const char* knames[] = {"2,2,2,2,8", "1,4,2,1,16", "1,4,1,1,16", "2,2,1,1,16", "2,2,2,1,16", "1,4,1,2,16", "1,4,2,2,8"};
-  int kh = -1;
-  if (prof_level_ >= 2) {
-    char nm[96];
-    int n = snprintf(nm, sizeof(nm), "conv_mfma_kernel<%s,%s,%d>", knames[cfg], pc.gate ? "true" : "false", HALO);
-    // tuning aid (PIPER_HIP_PROF_SITES=1): one profile row per conv SHAPE instead of per instantiation
-    if (pol_.prof_sites) snprintf(nm + n, sizeof(nm) - n, "|%dx%dx%d d%d e%d L%d", pc.rows, pc.Cin, pc.ntaps, pc.dil, epi, len_mul);
-    kh = kbegin(krow(std::string(nm)), kflops, kbytes);
-  }
-  launch::conv_tile(cfg, pc.gate, HALO, grid, smem, ls_, p);
   kend(kh);
 }
 

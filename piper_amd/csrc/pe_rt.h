@@ -6,9 +6,10 @@
 namespace pe { extern thread_local long g_launches; }   // kernel launches issued by this thread (captured launches count once)
 #ifdef PE_EMU
 namespace pe { inline const char* g_emu_kernel = ""; }   // the kernel the emulator is running (diagnostics)
-#include "hip_emu.h"
-#define PE_LAUNCH(kernel, grid, block, smem, stream, ...) \
-  (++pe::g_launches, pe::g_emu_kernel = #kernel, emu::launch((grid), (block), (smem), [=]() { kernel(__VA_ARGS__); }))
+#include "plan_trace.h"      // hip_emu.h + the launch record (EMU_PLAN_TRACE)
+#define PE_LAUNCH(kernel, grid, block, smem, stream, ...)                                               \
+  (++pe::g_launches, pe::g_emu_kernel = #kernel, emu::plan_trace(#kernel, (grid), (block), (smem)), \
+   emu::launch((grid), (block), (smem), [=]() { kernel(__VA_ARGS__); }))
 #define PE_DYN_SMEM(type, name) type* name = reinterpret_cast<type*>(emu::dyn_smem)
 #define PE_STAMP(k, i) ((void)0)
 #define PE_KTRACE(id) ((void)0)
