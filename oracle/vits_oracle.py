@@ -457,6 +457,66 @@ def decode(w, cfg, z_p, sid: Optional[int] = None, dtype=torch.float64) -> np.nd
     return generator(w, cfg, z * y_mask, g=g)[0, 0].numpy()
 
 
+@torch.no_grad()
+def stage_truths(w, cfg, ids, scales, noise_w, noise_z, given, sid: Optional[int] = None, dtype=torch.float64,
+                 stages: str = "EDRFG") -> Dict[str, np.ndarray]:
+    """Every stage of ``infer_one`` computed from a GIVEN input to that stage (one utterance), in `dtype`: an error of one
+    stage can then neither hide in the next nor be blamed on it, and a flipped ceil cannot make two runs incomparable. A
+    test hands it the engine's own tensors in `given`; weights are converted to `dtype` (f32 -> f64 exactly, as in
+    ``decode``), and with dtype=float32 the same call is the oracle's own f32 run of each stage from the same inputs.
+
+        E  text_encoder       ids                                       -> x_enc [H,T], m_p, logs_p [C,T]
+        D  sdp_reverse        given["x_enc"], noise_w [2,>=T]           -> logw [T], w = exp(logw) * length_scale [T]
+        R  generate_path      given["stats"] [2C,T] (m_p | logs_p), given["durations"] [T] integers, noise_z [C,>=F]
+                              -> frames, frame_id [F] (the id whose column frame f takes, -1 = none), z_p_m and z_p_n [C,F]
+                              (the two terms of the prior sample), z_p = z_p_m + z_p_n
+        F  flow_reverse       given["z_p"] [C,F]                        -> z [C,F]
+        G  generator          given["z"] [C,F]                          -> audio [F * hop]
+
+    `stages` selects a subset; only the selected stages' entries of `given` are read. Returns numpy arrays in `dtype`."""
+    if not isinstance(next(iter(w.values())), torch.Tensor) or next(iter(w.values())).dtype != dtype:
+        w = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in w.items()}
+    noise_scale, length_scale, noise_scale_w = (float(s) for s in scales)
+    ids_t = torch.as_tensor(np.asarray(ids), dtype=torch.long).view(1, -1)
+    T = ids_t.shape[1]
+    x_mask = torch.ones(1, 1, T, dtype=dtype)
+    g = None
+    if cfg.n_speakers > 1:
+        g = F.embedding(torch.tensor([int(sid or 0)]), w["emb_g.weight"]).unsqueeze(-1)
+
+    def tt(a):
+        return torch.as_tensor(np.asarray(a)).to(dtype)[None]
+
+    out: Dict[str, object] = {}
+    if "E" in stages:
+        x, m_p, logs_p, _ = text_encoder(w, cfg, ids_t, torch.tensor([T], dtype=torch.long))
+        out.update(x_enc=x[0], m_p=m_p[0], logs_p=logs_p[0])
+    if "D" in stages:
+        nw = tt(noise_w).view(1, 2, -1)[:, :, :T]
+        logw = sdp_reverse(w, cfg, tt(given["x_enc"]), x_mask, nw, noise_scale_w, g=g)
+        out.update(logw=logw[0, 0], w=(torch.exp(logw) * x_mask * length_scale)[0, 0])
+    if "R" in stages:
+        stats = tt(given["stats"])
+        m_p, logs_p = torch.split(stats, cfg.inter, dim=1)
+        w_ceil = torch.as_tensor(np.asarray(given["durations"]).astype(np.int64)).to(dtype).view(1, 1, T)
+        Fr = int(torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long().max())
+        y_mask = torch.ones(1, 1, Fr, dtype=dtype)
+        attn = generate_path(w_ceil, x_mask.unsqueeze(2) * y_mask.unsqueeze(-1)).squeeze(1)          # [1, F, T], one-hot rows
+        m_pe = torch.matmul(attn, m_p.transpose(1, 2)).transpose(1, 2)
+        logs_pe = torch.matmul(attn, logs_p.transpose(1, 2)).transpose(1, 2)
+        n = tt(noise_z)[:, :, :Fr] * torch.exp(logs_pe) * noise_scale
+        hot = attn[0].sum(-1) > 0
+        fid = torch.where(hot, attn[0].argmax(-1), torch.full((Fr,), -1, dtype=torch.long))
+        out.update(frames=Fr, frame_id=fid, z_p_m=m_pe[0], z_p_n=n[0], z_p=(m_pe + n)[0])
+    if "F" in stages:
+        zp = tt(given["z_p"])
+        y_mask = torch.ones(1, 1, zp.shape[2], dtype=dtype)
+        out.update(z=flow_reverse(w, cfg, zp, y_mask, g=g)[0])
+    if "G" in stages:
+        out.update(audio=generator(w, cfg, tt(given["z"]), g=g)[0, 0])
+    return {k: (v.numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+
+
 _WEIGHT_DIGESTS: Dict[int, tuple] = {}
 
 

@@ -7,6 +7,7 @@ import dataclasses
 import json
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest

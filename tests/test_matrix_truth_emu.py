@@ -17,6 +17,7 @@ from oracle import vits_oracle as O
 from piper_amd import _lib as L
 from piper_amd import weights as W
 from piper_amd.engine import Engine
+from one_utterance_truth_case import truth_gates          # (shared with the one-utterance truth tests)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tests", "emu", "libpiper_hip_emu.so")
@@ -156,22 +157,6 @@ def test_f16x3_on_rescaled_and_overflow_voices(emu_lib, monkeypatch, preset, rou
         assert np.array_equal(ov["zp"][b], rs["zp"][b])
         assert np.all(np.isfinite(ov["audio"][b])), f"utterance {b}: non-finite f16x3 audio on the overflow voice"
         assert np.array_equal(ov["pcm"][b], O.audio_float_to_int16(ov["audio"][b]))
-
-
-def truth_gates(err, mode, family):
-    """The gates of tests/test_gpu_matrix_truth.py, from the operand bits: err = {setting: max |d audio| against f64},
-    'torch' = the oracle's own f32 run, fl = 2^-23 * peak of the truth. One difference: the emulator rounds the f32
-    accumulator after EVERY product of an MFMA (tests/emu/hip_emu.h), so bf16x6 takes six accumulator roundings per k
-    element where the f32 kernel takes one: sqrt(6 + 1) ~ 2.65 times the f32 kernel's rounding error with the dropped
-    2^-24 products, gate 3 here (2 on the hardware, whose bf16x6 lands below its f32 kernels: profiles/matrix_truth.md)."""
-    fl = err["fl"]
-    if mode == "f32":
-        return err["f32"] <= 8 * err["torch"] + fl            # two f32 summation orders
-    if mode == "bf16x6":
-        return err[mode] <= 3 * err["f32"] + fl               # exact operands, dropped products at 2^-24, 6 roundings
-    if mode == "f16x3":
-        return err[mode] <= 4 * err["f32"] + fl if family != "rescaled" else err[mode] < PRODUCT_GATE   # 22 of 24 bits
-    return err[mode] <= 2 ** 8 * err["f32"] and err[mode] < PRODUCT_GATE      # bf16x3: 16 of 24 bits
 
 
 @pytest.mark.parametrize("route", sorted(ROUTES))
