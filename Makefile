@@ -53,7 +53,12 @@ tests/cpp/test_piper: tests/cpp/test_piper.cpp $(LIB) include/piper.hpp
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_piper.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
 tests/cpp/test_piper_emu: tests/cpp/test_piper.cpp $(EMULIB) include/piper.hpp
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_piper.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
+# SynthesisConfig::targetLufs through the piper:: API (tests/test_loudness_cpp.py)
+tests/cpp/test_loudness: tests/cpp/test_loudness.cpp $(LIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_loudness.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
+tests/cpp/test_loudness_emu: tests/cpp/test_loudness.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_loudness.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
 
 clean:
-	rm -rf build $(LIB) $(EMULIB) tests/cpp/test_piper tests/cpp/test_piper_emu
+	rm -rf build $(LIB) $(EMULIB) tests/cpp/test_piper tests/cpp/test_piper_emu tests/cpp/test_loudness tests/cpp/test_loudness_emu
 .PHONY: all emu stamps clean

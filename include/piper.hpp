@@ -94,6 +94,11 @@ struct SynthesisConfig {
   // textToAudio set the engine accordingly, and the silences and the WAV header of textToWavFile use this rate. (Beyond the
   // reference, which always delivers sampleRate.)
   int outputSampleRate = 0;
+  // Target integrated loudness in LUFS (ITU-R BS.1770-4, mono) of every whole utterance -- every phrase of textToAudio lands
+  // on the same level -- under a SAMPLE-peak ceiling of peakCeilingDb dBFS (piper_hip.h: pe_set_loudness). Unset, the default:
+  // the reference's rule, every phrase scaled to its own peak. (Beyond the reference.)
+  std::optional<float> targetLufs;
+  float peakCeilingDb = -1.0f;
   int sampleWidth = 2;  // 16-bit
   int channels = 1;     // mono
 

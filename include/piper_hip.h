@@ -287,6 +287,44 @@ int pe_get_stream_gain(pe_engine* e, int32_t* mode, float* peak, int32_t* ramp_s
  * afterwards. */
 int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacity, int32_t* n);
 
+/* Target loudness of whole utterances. By default every utterance of pe_synthesize*, pe_fetch, the groups and the coalescer
+ * is scaled by 32767 / max(0.01, its peak) (the reference's rule, piper.cpp:410-431): the PEAK is fixed, the level is not, and a
+ * nearly empty phrase is amplified by up to 100. With on != 0 every whole-utterance call delivers its int16 PCM at a target
+ * integrated loudness instead, measured and applied on the device with no host round trip:
+ *   x[0 .. n)  the floats the call delivers for the utterance, at the delivered rate fs (output samples when a rate is set).
+ *              They never change.
+ *   y          x through the K-weighting of ITU-R BS.1770-4 (shelf + 38 Hz high-pass, the coefficients of pe_loudness_filter,
+ *              zero state at sample 0), mono.
+ *   blocks     h = (fs + 5) / 10 samples; z_j = mean of y^2 over [j h, (j + 4) h) for every j with (j + 4) h <= n;
+ *              l_j = -0.691 + 10 log10 z_j. Absolute gate l_j > -70; relative gate G = -0.691 + 10 log10(mean z over the
+ *              absolute-gated blocks) - 10; L = -0.691 + 10 log10(mean z over blocks with l_j > -70 and l_j > G).
+ *   n < 4 h    PE_LOUD_SHORT: one block over the whole utterance (mean of y^2 over n), no relative gate.
+ *   silence    nothing passes the absolute gate, or n == 0: PE_LOUD_UNMEASURABLE, scale = 32767 (the waveform as generated).
+ *   scale      32767 * min(10^((target_lufs - L) / 20), C / p), C = 10^(ceiling_db / 20), p = max |x|; PE_LOUD_LIMITED when
+ *              the second term is the smaller. One f32 per utterance; products are clamped to [-32768, 32767] and truncated.
+ * The ceiling is a SAMPLE peak: inter-sample (true) peaks are not measured. The measurement is mono and covers whole
+ * utterances only: pe_stream_next, pe_stream_next_batch and pe_stream_pool_next keep their chunk rule and the
+ * pe_set_stream_gain modes -- an integrated loudness is not known before an utterance ends -- and the setting may change
+ * while a stream is live. target_lufs in [-40, -5], ceiling_db in [-20, 0], both finite (on == 0: ignored); a voice without
+ * a header rate needs pe_set_output_rate(native, ...) first. A refused call names the value and changes nothing. target and
+ * ceiling are data the kernels read in place: new values replay the captured graphs; on / off is part of the graph keys.
+ * With on == 0 -- the default -- every launch, graph and bit of output is what it is without this call. One setting per
+ * handle (the engines of a group: pe_group_engine). pe_get_loudness reads it back (any pointer may be NULL). */
+enum { PE_LOUD_SHORT = 1, PE_LOUD_UNMEASURABLE = 2, PE_LOUD_LIMITED = 4 };
+int pe_set_loudness(pe_engine* e, int32_t on, float target_lufs, float ceiling_db);
+int pe_get_loudness(pe_engine* e, int32_t* on, float* target_lufs, float* ceiling_db);
+/* The last fetched whole-utterance call on the handle: *n utterances (0: it ran with the setting off); lufs[i] = L (-inf when
+ * not measurable), scale[i], peak[i] = p, flags[i] = PE_LOUD_* bits. Any array may be NULL; capacity < *n is an error. */
+int pe_last_loudness(pe_engine* e, float* lufs, float* scale, float* peak, int32_t* flags, int64_t capacity, int32_t* n);
+/* Host only: the K-weighting biquads at rate fs (4000 .. 192000), bilinear transforms of the analog prototypes computed in
+ * f64: coef = shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2} (a0 = 1). At 48000 Hz the table of BS.1770-4. */
+int pe_loudness_filter(int32_t fs, double coef[10]);
+/* Test hook: the two loudness kernels alone on caller-supplied rows x[batch][stride] (host), row b holding valid[b] samples at
+ * rate fs, with the given target and ceiling: lufs / scale / flags [batch] as pe_last_loudness reports them. Independent of
+ * the handle's setting and rate. */
+int pe_debug_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs,
+                      float target_lufs, float ceiling_db, float* lufs, float* scale, int32_t* flags);
+
 /* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
  * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them
  * counts as zero. out[b][0 .. count[b]) receives outputs n0[b] .. n0[b] + count[b] - 1 of that utterance (out_stride floats

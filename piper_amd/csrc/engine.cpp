@@ -80,6 +80,7 @@ void Engine::free_all() {
   sb_active_ = false;
   stream_pool_free();
   rs_free();
+  loud_free();
   if (ev0_) hipEventDestroy(ev0_);
   if (ev1_) hipEventDestroy(ev1_);
   for (auto& k : kev_) { hipEventDestroy(k.a); hipEventDestroy(k.b); }
@@ -342,6 +343,7 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
     side_floats_ = want;
   }
   if (rs_on_) ensure_resample();
+  if (ld_on_) ensure_loudness();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -655,7 +657,8 @@ void Engine::run() {
     for (int b = 0; b < B; ++b)
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_);
+    // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, ld_on_ ? "|l1" : "");
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -682,7 +685,7 @@ void Engine::run() {
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, ld_on_ ? "|l1" : "");
     run_stage('B', key);
   }
 }
@@ -742,7 +745,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d", B_, Fg_, Fs_, Ts_);
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, ld_on_ ? "|l1" : "");
   run_stage('B', key);
   return false;
 }
@@ -778,6 +781,7 @@ void Engine::download(bool want_audio, bool want_pcm) {
     if (want_pcm && !zc) PE_HIP(hipMemcpyAsync(h_pcm_, psrc(), n * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
     if (finish_run()) {                        // synchronises; sample_off_ now holds the real length
       pcm_zc_live_ = zc;
+      loud_collect();
       return;
     }
     // the guess missed: stage B was re-issued (its pcm16_kernel writes the host buffer again); copies below
@@ -798,6 +802,7 @@ void Engine::download(bool want_audio, bool want_pcm) {
                             stream_));
   PE_HIP(hipStreamSynchronize(stream_));
   pcm_zc_live_ = zc;
+  loud_collect();
 }
 
 int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise) {
@@ -1373,6 +1378,7 @@ void Engine::set_output_rate(int native, int output) {
     throw std::runtime_error(std::string("the output rate cannot change while a ") +
                              (sp_slots_ ? "stream pool is open" : "stream is live") + " on this handle");
   const bool on = output != 0 && output != native;
+  if (ld_on_) loud_check_rate(on ? output : native);    // (the target loudness is measured at the delivered rate)
   const std::string pair = std::to_string(native) + " -> " + std::to_string(output) + " Hz";
   int L = 1, M = 1, K = 0, Tp = 0, tile = RS_TILE;
   std::vector<float> table;
@@ -1408,6 +1414,13 @@ void Engine::set_output_rate(int native, int output) {
   }
   if (on == rs_on_ && (!on || (native == rs_native_ && output == rs_out_))) {      // nothing changes (the native rate is noted)
     rs_native_ = native;
+    if (ld_on_ && output_rate() != ld_fs_) {           // (a voice without a header rate was told another native rate)
+      PE_HIP(hipSetDevice(device_));
+      finish_run();
+      PE_HIP(hipStreamSynchronize(stream_));
+      drop_graphs();
+      loud_upload_filter(output_rate());
+    }
     return;
   }
   PE_HIP(hipSetDevice(device_));
@@ -1437,6 +1450,7 @@ void Engine::set_output_rate(int native, int output) {
     So_ = Ss_;
   }
   // (on: the next call's ensure_stage_b derives So_ and sizes the zero-copy PCM buffer and the resampled rows)
+  if (ld_on_) loud_upload_filter(output_rate());       // the K-weighting filter of the new delivered rate
 }
 
 // The resampled rows [capB_B_][So_] (floats + int16) and the two row blocks, (re)allocated when the workspace capacity or
@@ -1535,6 +1549,271 @@ void Engine::debug_resample(const float* x, int batch, int64_t stride, const int
       if (count[b] > 0)
         PE_HIP(hipMemcpyAsync(out + (size_t)b * out_stride, dy + (size_t)b * ys, (size_t)count[b] * sizeof(float), hipMemcpyDeviceToHost, stream_));
     PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
+}
+
+// ------------------------------------------------------------------------------------------------
+// target loudness
+// ------------------------------------------------------------------------------------------------
+
+// The K-weighting biquads from their analog prototypes by the bilinear transform: at 48000 Hz the
+// coefficient table of ITU-R BS.1770-4 to 1e-14.
+void Engine::loudness_filter(int fs, double coef[10]) {
+  if (fs < 4000 || fs > 192000) throw std::runtime_error("loudness filter: rate " + std::to_string(fs) + " Hz outside [4000, 192000]");
+  const double pi = 3.14159265358979323846;
+  {
+    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    const double K = std::tan(pi * f0 / (double)fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+    const double a0 = 1.0 + K / Q + K * K;
+    coef[0] = (Vh + Vb * K / Q + K * K) / a0;
+    coef[1] = 2.0 * (K * K - Vh) / a0;
+    coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+    coef[3] = 2.0 * (K * K - 1.0) / a0;
+    coef[4] = (1.0 - K / Q + K * K) / a0;
+  }
+  {
+    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+    const double K = std::tan(pi * f0 / (double)fs), a0 = 1.0 + K / Q + K * K;
+    coef[5] = 1.0; coef[6] = -2.0; coef[7] = 1.0;
+    coef[8] = 2.0 * (K * K - 1.0) / a0;
+    coef[9] = (1.0 - K / Q + K * K) / a0;
+  }
+}
+
+void Engine::loud_check_rate(int fs) {
+  if (fs <= 0)
+    throw std::runtime_error("the target loudness needs the delivered sample rate, and this voice carries none (an .onnx does "
+                             "not): call pe_set_output_rate with the sample rate of its .onnx.json first");
+  if (fs < 4000 || fs > 192000)
+    throw std::runtime_error("the target loudness is not available at " + std::to_string(fs) + " Hz (outside [4000, 192000])");
+}
+
+// Everything of the setting that follows the rate: the segment length h = 100 ms, the warm-up W = 50 ms (12 time constants
+// of the high-pass's double pole at 38 Hz: (1 + 12) e^-12 = 8e-5 of a state's start is left), the run R of one thread, and
+// the filter block -- the coefficients and A^(R 2^k), A = what one sample of silence makes of the four states (the state
+// update of loud_step, kernels/loudness.h, with x = 0).
+static void loud_plan(int fs, int& h, int& W, int& R, double* blk) {
+  Engine::loudness_filter(fs, blk);
+  h = (fs + 5) / 10;
+  W = (fs + 10) / 20;
+  R = (h + W + LOUD_TPB - 1) / LOUD_TPB;
+  const double* c = blk;
+  long double A[4][4], P[4][4], Tm[4][4];
+  for (int col = 0; col < 4; ++col) {
+    long double z[4] = {0, 0, 0, 0};
+    z[col] = 1;
+    const long double ya = z[0];
+    const long double n0 = -c[3] * ya + z[1], n1 = -c[4] * ya;
+    const long double yb = c[5] * ya + z[2];
+    const long double n2 = -c[8] * yb + c[6] * ya + z[3], n3 = -c[9] * yb + c[7] * ya;
+    A[0][col] = n0; A[1][col] = n1; A[2][col] = n2; A[3][col] = n3;
+  }
+  auto mul = [&](long double (&X)[4][4], long double (&Y)[4][4], long double (&Z)[4][4]) {
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) {
+        long double v = 0;
+        for (int k = 0; k < 4; ++k) v += X[i][k] * Y[k][j];
+        Z[i][j] = v;
+      }
+  };
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) P[i][j] = i == j ? 1 : 0;
+  for (int r = 0; r < R; ++r) { mul(A, P, Tm); memcpy(P, Tm, sizeof(P)); }
+  for (int k = 0; k < LOUD_LEVELS; ++k) {
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) blk[10 + 16 * k + 4 * i + j] = (double)P[i][j];
+    mul(P, P, Tm);
+    memcpy(P, Tm, sizeof(P));
+  }
+}
+
+void Engine::loud_upload_filter(int fs) {
+  double blk[LOUD_COEF_DOUBLES];
+  int h, W, R;
+  loud_plan(fs, h, W, R, blk);
+  if (!ld_coef_) PE_HIP(hipMalloc((void**)&ld_coef_, sizeof(blk)));
+  PE_HIP(hipMemcpy(ld_coef_, blk, sizeof(blk), hipMemcpyHostToDevice));
+  ld_fs_ = fs; ld_h_ = h; ld_W_ = W; ld_R_ = R;
+}
+
+void Engine::loud_write_ctl() {
+  if (!ld_ctl_) return;
+  const float C = (float)std::pow(10.0, (double)ld_cdb_ / 20.0);
+  memcpy(ld_ctl_, &ld_T_, sizeof(float));
+  memcpy(ld_ctl_ + 1, &C, sizeof(float));
+}
+
+void Engine::loud_free() {
+  if (ld_coef_) hipFree(ld_coef_);
+  if (ld_seg_) hipFree(ld_seg_);
+  if (ld_dev_) hipFree(ld_dev_);
+  if (ld_ctl_) hipHostFree(ld_ctl_);
+  ld_coef_ = ld_seg_ = nullptr; ld_dev_ = ld_ctl_ = nullptr;
+  ld_seg_rows_ = 0; ld_nseg_cap_ = 0; ld_cap_ = 0;
+}
+
+void Engine::set_loudness(bool on, float target_lufs, float ceiling_db) {
+  EntryLock entry_lock;
+  if (on) {
+    if (!std::isfinite(target_lufs) || target_lufs < -40.f || target_lufs > -5.f)
+      throw std::runtime_error("target loudness " + std::to_string(target_lufs) + " LUFS outside [-40, -5]");
+    if (!std::isfinite(ceiling_db) || ceiling_db < -20.f || ceiling_db > 0.f)
+      throw std::runtime_error("peak ceiling " + std::to_string(ceiling_db) + " dB outside [-20, 0]");
+    loud_check_rate(output_rate());
+  }
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles first)
+  PE_HIP(hipStreamSynchronize(stream_));               // nothing on the device reads the control block any more
+  if (on) {
+    if (!ld_coef_ || ld_fs_ != output_rate()) {
+      if (ld_coef_) drop_graphs();                     // (h / W / R are kernel arguments inside the graphs)
+      loud_upload_filter(output_rate());
+    }
+    ld_T_ = target_lufs; ld_cdb_ = ceiling_db;
+    loud_write_ctl();
+  }
+  // target and ceiling are data; on / off picks the launches and is part of the graph keys, so nothing else is dropped:
+  // both sets of graphs stay cached side by side. Streams are not touched.
+  ld_on_ = on;
+}
+
+// The segment sums [capB_B_][So_ / h + 2] and the control / gain blocks, (re)allocated when the workspace capacity or the
+// rate grew; called at the end of ensure_stage_b, which has set So_.
+void Engine::ensure_loudness() {
+  if (!ld_coef_ || ld_fs_ != output_rate()) loud_upload_filter(output_rate());
+  const int nseg = (int)(So_ / ld_h_) + 2;
+  const int want_cap = (int)((std::max<size_t>(std::max(capA_B_, capB_B_), 64) + 1) & ~(size_t)1);
+  if (ld_seg_ && ld_seg_rows_ >= capB_B_ && ld_nseg_cap_ >= nseg && ld_ctl_ && ld_dev_ && ld_cap_ >= want_cap) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  drop_graphs();
+  if (!(ld_seg_ && ld_seg_rows_ >= capB_B_ && ld_nseg_cap_ >= nseg)) {
+    if (ld_seg_) { PE_HIP(hipFree(ld_seg_)); ld_seg_ = nullptr; }
+    const size_t rows = std::max(ld_seg_rows_, capB_B_);
+    const int cols = std::max(ld_nseg_cap_, nseg);
+    ld_seg_rows_ = 0; ld_nseg_cap_ = 0;
+    if (hipMalloc((void**)&ld_seg_, rows * (size_t)cols * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      ld_seg_ = nullptr;
+      throw std::runtime_error("out of device memory: " + std::to_string((rows * (size_t)cols * sizeof(double)) >> 20) + " MiB of loudness segment sums");
+    }
+    if (pol_.debug_poison) poison(ld_seg_, rows * (size_t)cols * sizeof(double));
+    ld_seg_rows_ = rows; ld_nseg_cap_ = cols;
+  }
+  if (!(ld_ctl_ && ld_dev_ && ld_cap_ >= want_cap)) {
+    if (ld_ctl_) { PE_HIP(hipHostFree(ld_ctl_)); ld_ctl_ = nullptr; }
+    if (ld_dev_) { PE_HIP(hipFree(ld_dev_)); ld_dev_ = nullptr; }
+    ld_cap_ = 0;
+    PE_HIP(hipHostMalloc((void**)&ld_ctl_, (size_t)ldc_words(want_cap) * sizeof(int)));
+    PE_HIP(hipMalloc((void**)&ld_dev_, (size_t)ld_words(want_cap) * sizeof(int)));
+    memset(ld_ctl_, 0, (size_t)ldc_words(want_cap) * sizeof(int));
+    PE_HIP(hipMemset(ld_dev_, 0, (size_t)ld_words(want_cap) * sizeof(int)));
+    PE_HIP(hipDeviceSynchronize());
+    ld_cap_ = want_cap;
+    loud_write_ctl();
+  }
+}
+
+void Engine::loud_collect() {
+  if (!ld_on_ || !ld_ctl_ || B_ > ld_cap_) { ll_n_ = 0; return; }
+  const int n = B_, cap = ld_cap_;
+  const float* rf = reinterpret_cast<const float*>(ld_ctl_ + ldc_o_report(cap));
+  ll_lufs_.assign(rf, rf + n);
+  ll_scale_.assign(rf + ld_o_scale(cap), rf + ld_o_scale(cap) + n);
+  ll_peak_.assign(rf + ld_o_peak(cap), rf + ld_o_peak(cap) + n);
+  ll_flags_.assign(ld_ctl_ + ldc_o_report(cap) + ld_o_flags(cap), ld_ctl_ + ldc_o_report(cap) + ld_o_flags(cap) + n);
+  ll_n_ = n;
+}
+
+int Engine::last_loudness(float* lufs, float* scale, float* peak, int32_t* flags, int64_t capacity) {
+  EntryLock entry_lock;
+  if (ll_n_ < 0) throw std::runtime_error("no whole-utterance call fetched on this handle yet");
+  if ((lufs || scale || peak || flags) && capacity < ll_n_) throw std::runtime_error("loudness report buffer too small");
+  for (int b = 0; b < ll_n_; ++b) {
+    if (lufs) lufs[b] = ll_lufs_[b];
+    if (scale) scale[b] = ll_scale_[b];
+    if (peak) peak[b] = ll_peak_[b];
+    if (flags) flags[b] = ll_flags_[b];
+  }
+  return ll_n_;
+}
+
+void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
+                            float* lufs, float* scale, int32_t* flags) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!x || !valid || !lufs || !scale || !flags) throw std::runtime_error("null argument");
+  if (stride < 0 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [0, 2^28]");
+  if (!std::isfinite(target) || target < -40.f || target > -5.f)
+    throw std::runtime_error("target loudness " + std::to_string(target) + " LUFS outside [-40, -5]");
+  if (!std::isfinite(ceiling_db) || ceiling_db < -20.f || ceiling_db > 0.f)
+    throw std::runtime_error("peak ceiling " + std::to_string(ceiling_db) + " dB outside [-20, 0]");
+  loud_check_rate(fs);
+  int maxn = 0;
+  std::vector<unsigned> peaks((size_t)batch, 0u);
+  for (int b = 0; b < batch; ++b) {
+    if (valid[b] < 0 || valid[b] > stride) throw std::runtime_error("row " + std::to_string(b) + ": valid length outside [0, stride]");
+    maxn = std::max(maxn, valid[b]);
+    float m = 0.f;
+    for (int i = 0; i < valid[b]; ++i) m = std::max(m, std::fabs(x[(size_t)b * stride + i]));
+    memcpy(&peaks[b], &m, sizeof(float));
+  }
+  double blk[LOUD_COEF_DOUBLES];
+  int h, W, R;
+  loud_plan(fs, h, W, R, blk);
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const int cap = (batch + 1) & ~1, nseg_cap = maxn / h + 2;
+  const long xs = (long)((std::max<int64_t>(stride, 1) + 3) & ~(int64_t)3);
+  float* dx = nullptr;
+  double *dcoef = nullptr, *dseg = nullptr;
+  int *dval = nullptr, *ctl = nullptr, *gd = nullptr;
+  unsigned* dpk = nullptr;
+  auto release = [&]() {
+    if (dx) hipFree(dx);
+    if (dcoef) hipFree(dcoef);
+    if (dseg) hipFree(dseg);
+    if (dval) hipFree(dval);
+    if (dpk) hipFree(dpk);
+    if (gd) hipFree(gd);
+    if (ctl) hipHostFree(ctl);
+  };
+  try {
+    PE_HIP(hipMalloc((void**)&dx, (size_t)batch * xs * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&dcoef, sizeof(blk)));
+    PE_HIP(hipMalloc((void**)&dseg, (size_t)batch * nseg_cap * sizeof(double)));
+    PE_HIP(hipMalloc((void**)&dval, (size_t)batch * sizeof(int)));
+    PE_HIP(hipMalloc((void**)&dpk, (size_t)batch * sizeof(unsigned)));
+    PE_HIP(hipMalloc((void**)&gd, (size_t)ld_words(cap) * sizeof(int)));
+    PE_HIP(hipHostMalloc((void**)&ctl, (size_t)ldc_words(cap) * sizeof(int)));
+    memset(ctl, 0, (size_t)ldc_words(cap) * sizeof(int));
+    const float C = (float)std::pow(10.0, (double)ceiling_db / 20.0);
+    memcpy(ctl, &target, sizeof(float));
+    memcpy(ctl + 1, &C, sizeof(float));
+    for (int b = 0; b < batch; ++b)
+      if (stride > 0)
+        PE_HIP(hipMemcpyAsync(dx + (size_t)b * xs, x + (size_t)b * stride, (size_t)stride * sizeof(float), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dcoef, blk, sizeof(blk), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dval, valid, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dpk, peaks.data(), (size_t)batch * sizeof(unsigned), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemsetAsync(dseg, 0xFF, (size_t)batch * nseg_cap * sizeof(double), stream_));
+    PE_HIP(hipStreamSynchronize(stream_));             // (the staging vectors are pageable)
+    LoudP p{};
+    p.x = dx; p.x_bs = xs; p.lens = dval; p.len_mul = 1; p.x_cap = (long)stride;
+    p.coef = dcoef; p.h = h; p.W = W; p.R = R; p.seg = dseg; p.nseg_cap = nseg_cap;
+    launch::loudness_seg(dim3((unsigned)std::max(1, (maxn + h - 1) / h), batch), stream_, p);
+    launch::loudness_gain(stream_, batch, dseg, nseg_cap, dval, 1, (long)stride, h, dpk, ctl, gd, cap);
+    PE_HIP(hipStreamSynchronize(stream_));
+    const float* rf = reinterpret_cast<const float*>(ctl + ldc_o_report(cap));
+    for (int b = 0; b < batch; ++b) {
+      lufs[b] = rf[b];
+      scale[b] = rf[ld_o_scale(cap) + b];
+      flags[b] = ctl[ldc_o_report(cap) + ld_o_flags(cap) + b];
+    }
   } catch (...) {
     hipStreamSynchronize(stream_);
     release();

@@ -128,6 +128,28 @@ class Engine {
   void debug_resample(const float* x, int batch, int64_t stride, const int32_t* vlen, const int64_t* n0, const int32_t* count,
                       const int64_t* origin, float* out, int64_t out_stride);
 
+  // Target loudness of whole utterances (kernels/loudness.h). Off, the default, is the reference's rule: every
+  // utterance scaled by 32767 / max(0.01, its peak). On: every whole-utterance call -- synthesize, the batch calls, run /
+  // fetch -- measures the gated integrated loudness L (ITU-R BS.1770-4, mono) of each float waveform it delivers, at the
+  // delivered rate, on the device, and converts with scale = 32767 min(10^((target - L) / 20), C / peak),
+  // C = 10^(ceiling_db / 20) a SAMPLE-peak ceiling; an utterance whose loudness cannot be measured (silence) keeps
+  // scale 32767. The delivered floats are not touched and stream chunks keep their own rules. Throws, and changes nothing,
+  // for a target outside [-40, -5] LUFS, a ceiling outside [-20, 0] dB, values that are not finite, or a voice whose
+  // delivered rate is unknown or outside [4000, 192000] Hz. target and ceiling are data the kernels read in place; on / off
+  // is part of the graph keys of the stages that end in the conversion.
+  void set_loudness(bool on, float target_lufs, float ceiling_db);
+  bool loudness_on() const { return ld_on_; }
+  float loudness_target() const { return ld_T_; }
+  float loudness_ceiling_db() const { return ld_cdb_; }
+  // per utterance of the last fetched call: loudness (LUFS, -inf: not measurable), scale, peak, LOUD_* flags; returns the
+  // utterances (0: that call ran with the setting off)
+  int last_loudness(float* lufs, float* scale, float* peak, int32_t* flags, int64_t capacity);
+  // host only: the K-weighting biquads at rate fs, shelf {b0, b1, b2, a1, a2} then high-pass {b0, b1, b2, a1, a2}
+  static void loudness_filter(int fs, double coef[10]);
+  // test hook: the two loudness kernels alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs
+  void debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
+                      float* lufs, float* scale, int32_t* flags);
+
   // The int16 level of stream chunks (kernels/params.h: GAIN_*). GAIN_CHUNK, the default, is the
   // reference's rule: every chunk scaled by 32767 / max(0.01, its own peak). GAIN_FIXED: 32767 / max(0.01, peak) for every
   // sample. GAIN_RUNNING: every stream -- the one-utterance stream, a batch-stream row, a pool slot -- carries a running
@@ -606,6 +628,29 @@ class Engine {
   void rs_host_row(int b, int64_t n0, int64_t org, int count, int vlen);
   const unsigned* rs_peaks() const { return reinterpret_cast<const unsigned*>(rs_dev_) + rs_o_peak(rs_cap_); }
   const int* rs_counts() const { return rs_dev_ + rs_o_count(rs_cap_); }
+  // target loudness. The filter block, the segment sums [rows][ld_nseg_cap_] and the control / gain blocks (params.h: ld_*,
+  // pinned host + device) are allocations of their own, outside both workspaces; their addresses are kernel arguments inside
+  // the graphs, so (re)allocating them drops every graph. h / W / R follow the delivered rate, which only set_output_rate
+  // changes (it drops the graphs itself).
+  bool ld_on_ = false;
+  float ld_T_ = -23.f, ld_cdb_ = -1.f;
+  int ld_fs_ = 0, ld_h_ = 0, ld_W_ = 0, ld_R_ = 0;
+  double* ld_coef_ = nullptr;
+  double* ld_seg_ = nullptr; size_t ld_seg_rows_ = 0; int ld_nseg_cap_ = 0;
+  int* ld_ctl_ = nullptr; int* ld_dev_ = nullptr; int ld_cap_ = 0;
+  std::vector<float> ll_lufs_, ll_scale_, ll_peak_;
+  std::vector<int32_t> ll_flags_;
+  int ll_n_ = -1;                               // utterances of the last fetched call's report (-1: none yet)
+  static void loud_check_rate(int fs);          // throws the refusal
+  void loud_upload_filter(int fs);              // h / W / R and the filter block for rate fs
+  void loud_write_ctl();
+  void ensure_loudness();                       // after ensure_stage_b sized the workspace (and ensure_resample the rows)
+  void loud_free();
+  void loud_collect();                          // the pinned report of the call just synchronised -> ll_*
+  // segment sums, gain and the int16 conversion of B delivered rows x (stride x_bs, lengths lens[b] * len_mul, peak words
+  // `peaks`); max_n bounds every row's length (grid)
+  void issue_loudness(int B, const float* x, long x_bs, const int* lens, int len_mul, const unsigned* peaks, long max_n,
+                      int16_t* pcm, int16_t* zc, double samples);
   float* audio_ = nullptr;
   int16_t* pcm_ = nullptr;
   unsigned* absmax_ = nullptr;

@@ -447,6 +447,28 @@ void Engine::issue_resample(int B, const float* x, long x_bs, const int* hst, co
                launch::resample(dim3((unsigned)((max_out + rs_tile_ - 1) / rs_tile_), B), stream_, p));
 }
 
+// Target loudness of B delivered rows (whole utterances): the segment sums of the K-weighted rows, the gated loudness and
+// the scale per row, and the int16 conversion with that scale in pcm16_kernel's place (kernels/loudness.h).
+// The floats are only read, so it does not matter which kernel wrote them (conv_post, the fused stage tail, the resampler).
+void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, int len_mul, const unsigned* peaks, long max_n,
+                            int16_t* pcm, int16_t* zc, double samples) {
+  if (!ld_coef_ || !ld_seg_ || !ld_ctl_ || !ld_dev_ || B > ld_cap_ || (size_t)B > ld_seg_rows_ || ld_h_ < 1)
+    throw std::runtime_error("loudness buffers are not sized for this call");
+  max_n = std::max<long>(1, std::min<long>(max_n, x_bs));
+  LoudP p{};
+  p.x = x; p.x_bs = x_bs; p.lens = lens; p.len_mul = len_mul; p.x_cap = x_bs;
+  p.coef = ld_coef_; p.h = ld_h_; p.W = ld_W_; p.R = ld_R_;
+  p.seg = ld_seg_; p.nseg_cap = ld_nseg_cap_;
+  const int nseg = (int)std::min<long>((max_n + ld_h_ - 1) / ld_h_, ld_nseg_cap_);
+  // algorithmic bytes: every delivered sample in once (the warm-up is read again out of the caches)
+  PE_LAUNCH_KB("loudness_seg_kernel", 4.0 * samples, launch::loudness_seg(dim3((unsigned)nseg, B), stream_, p));
+  PE_LAUNCH_K("loudness_gain_kernel",
+              launch::loudness_gain(stream_, B, ld_seg_, ld_nseg_cap_, lens, len_mul, x_bs, ld_h_, peaks, ld_ctl_, ld_dev_, ld_cap_));
+  PE_LAUNCH_KB("pcm16_gain_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
+               launch::pcm16_gain(dim3((unsigned)((max_n + 255) / 256), B), stream_, x, x_bs, ld_dev_, ld_cap_, lens, len_mul, pcm,
+                                  x_bs, zc));
+}
+
 // Lock-step window stage of a row set (the batch stream's utterances, the pool's slots): every row's window of its latent ->
 // window buffer (the dead prior-noise buffer) -> generator on the published window lengths -> per-chunk peak and int16 /
 // float delivery into pinned host memory. One linear chain. The rows' gain blocks (params.h: sg_*, sgd_*) are used in the
@@ -650,10 +672,15 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
       // RESAMPLED waveform (a band-limited interpolation can overshoot the native peak)
       const long max_out = out_samples((long)Lmax);
       issue_resample(B, audio_, Ss_, nullptr, lens, max_out, fsum * hop_);
+      if (ld_on_)
+        issue_loudness(B, raudio_, So_, rs_counts(), 1, rs_peaks(), max_out, rpcm_, zc, fsum * hop_ * ((double)rs_L_ / rs_M_));
+      else
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * ((double)rs_L_ / rs_M_) * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
                    launch::pcm16(dim3((unsigned)((max_out + 255) / 256), B), stream_, raudio_, So_, rs_peaks(), rs_counts(), 1,
                                  rpcm_, So_, zc));
-    } else if (with_pcm16)
+    } else if (with_pcm16 && ld_on_ && !zero_absmax)
+      issue_loudness(B, audio_, Ss_, lens, hop_, absmax_, Lmax, pcm_, zc, fsum * hop_);
+    else if (with_pcm16)
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * (4.0 + 2.0 + (zc ? 2.0 : 0.0)), launch::pcm16(dim3((Lmax + 255) / 256, B), stream_, audio_, Ss_, absmax_, lens, hop_, pcm_, Ss_, zc));
     prof_end(4, tail_done ? 0.0 : 2.0 * fsum * hop_ * post_cin_ * K);
   }

@@ -97,6 +97,13 @@ void resample(dim3 grid, hipStream_t stream, const RsP& p);
 void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap);
 void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
                        const int* gq);
+// target loudness (params.h: ld_*, LoudP): grid = (100 ms segments of the bucket, rows), then one wave per row; pcm16_gain =
+// pcm16 with the scale loudness_gain wrote to `gq`
+void loudness_seg(dim3 grid, hipStream_t stream, const LoudP& p);
+void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
+                   const unsigned* peaks, int* ctl, int* gd, int cap);
+void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
+                int len_mul, short* pcm, long p_bs, short* host);
 
 }  // namespace launch
 }  // namespace pe

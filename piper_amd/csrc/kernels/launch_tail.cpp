@@ -4,6 +4,7 @@
 #include "mrf.h"
 #include "post.h"
 #include "resample.h"
+#include "loudness.h"
 
 namespace pe {
 namespace launch {
@@ -95,6 +96,20 @@ void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, cons
 void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
                        const int* gq) {
   PE_LAUNCH(chunk_pcm_rs_gain_kernel, grid, dim3(256), 0, stream, y, y_bs, rows, rcap, st, cap, gq);
+}
+
+void loudness_seg(dim3 grid, hipStream_t stream, const LoudP& p) {
+  PE_LAUNCH(loudness_seg_kernel, grid, dim3(LOUD_TPB), 0, stream, p);
+}
+
+void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
+                   const unsigned* peaks, int* ctl, int* gd, int cap) {
+  PE_LAUNCH(loudness_gain_kernel, dim3(B), dim3(64), 0, stream, seg, nseg_cap, lens, len_mul, x_cap, h, peaks, ctl, gd, cap);
+}
+
+void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
+                int len_mul, short* pcm, long p_bs, short* host) {
+  PE_LAUNCH(pcm16_gain_kernel, grid, dim3(PCM16_TPB), 0, stream, lens, len_mul, gq, gcap, audio, a_bs, pcm, p_bs, host);
 }
 
 }  // namespace launch

@@ -307,6 +307,32 @@ struct RsP {
   int tile;                                    // output samples per workgroup: its native span fits RS_SPAN
 };
 
+// ---- target loudness of whole utterances (loudness.h: loudness_seg_kernel, loudness_gain_kernel; post.h: pcm16_gain_kernel)
+// The setting's numbers are DATA, like the stream gain's: a pinned host control block for `cap` rows that
+// loudness_gain_kernel reads in place and into which it writes what pe_last_loudness reports; the conversion's operand
+// lives in a device block of the report's layout.
+//   control (pinned host)  T (target, LUFS), C (ceiling as a sample-peak ratio) as f32, then the report
+//   report / device block  L[cap] (f32 LUFS, -inf: not measurable), scale[cap] (f32), peak[cap] (f32), flags[cap]
+// The filter block (device, f64): shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2}, then LOUD_LEVELS 4 x 4
+// matrices A^(R 2^k), k = 0 .. LOUD_LEVELS - 1, row-major: what R samples of silence make of the cascade's four states.
+enum { LOUD_SHORT = 1, LOUD_UNMEASURABLE = 2, LOUD_LIMITED = 4 };
+static constexpr int LOUD_TPB = 256;           // threads (= runs) of a segment's workgroup
+static constexpr int LOUD_LEVELS = 8;          // log2(LOUD_TPB)
+static constexpr int LOUD_COEF_DOUBLES = 10 + 16 * LOUD_LEVELS;
+static constexpr int ld_o_scale(int cap) { return cap; }
+static constexpr int ld_o_peak(int cap) { return 2 * cap; }
+static constexpr int ld_o_flags(int cap) { return 3 * cap; }
+static constexpr int ld_words(int cap) { return 4 * cap; }
+static constexpr int ldc_o_report(int cap) { (void)cap; return 2; }
+static constexpr int ldc_words(int cap) { return 2 + 4 * cap; }
+struct LoudP {
+  const float* x; long x_bs;                   // delivered rows x[b][0 .. n_b), n_b = lens[b] * len_mul cut to x_cap
+  const int* lens; int len_mul; long x_cap;
+  const double* coef;                          // filter block
+  int h, W, R;                                 // samples of a 100 ms segment, of the warm-up in front of it, of one thread's run
+  double* seg; int nseg_cap;                   // segment sums seg[b][nseg_cap]
+};
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

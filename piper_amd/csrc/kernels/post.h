@@ -83,14 +83,22 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* x, long x_b
 // Kernel entry: the parameters arrive in SGPRs in the order the kernel needs them (the two data-dependent scalars' pointers
 // first), and the block size is a constant instead of the hidden blockDim argument.
 constexpr int PCM16_TPB = 256;
-__global__ __launch_bounds__(PCM16_TPB) void pcm16_kernel(const int* lens, int len_mul, const unsigned* absmax, const float* audio,
-                                                          long a_bs, short* pcm, long p_bs, short* host) {
-  PE_KTRACE(18);
+// GAIN (pcm16_gain_kernel, the target-loudness setting): the scale is the one loudness_gain_kernel (loudness.h) left in the
+// device block `gq` (params.h: ld_*) instead of 32767 / max(0.01, peak). The default instantiation is the kernel as it was:
+// nothing of the gain path is in it.
+template <bool GAIN>
+__device__ __forceinline__ void pcm16_body(const int* lens, int len_mul, const unsigned* absmax, const float* audio, long a_bs,
+                                           short* pcm, long p_bs, short* host, const int* gq, int gcap) {
   const int b = blockIdx.y, L = lens[b] * len_mul;
   const int t = blockIdx.x * PCM16_TPB + threadIdx.x;
   if (t >= L) return;
-  const float peak = fmaxf(0.01f, __uint_as_float(absmax[b]));
-  const float scale = 32767.0f / peak;
+  float scale;
+  if constexpr (GAIN) {
+    scale = __uint_as_float(reinterpret_cast<const unsigned*>(gq)[ld_o_scale(gcap) + b]);
+  } else {
+    const float peak = fmaxf(0.01f, __uint_as_float(absmax[b]));
+    scale = 32767.0f / peak;
+  }
   float v = audio[(long)b * a_bs + t] * scale;
   v = fminf(fmaxf(v, -32768.0f), 32767.0f);
   pcm[(long)b * p_bs + t] = (short)v;
@@ -100,6 +108,16 @@ __global__ __launch_bounds__(PCM16_TPB) void pcm16_kernel(const int* lens, int l
     for (int u = 0; u < b; ++u) off += (long)lens[u] * len_mul;
     host[off + t] = (short)v;
   }
+}
+__global__ __launch_bounds__(PCM16_TPB) void pcm16_kernel(const int* lens, int len_mul, const unsigned* absmax, const float* audio,
+                                                          long a_bs, short* pcm, long p_bs, short* host) {
+  PE_KTRACE(18);
+  pcm16_body<false>(lens, len_mul, absmax, audio, a_bs, pcm, p_bs, host, nullptr, 0);
+}
+__global__ __launch_bounds__(PCM16_TPB) void pcm16_gain_kernel(const int* lens, int len_mul, const int* gq, int gcap, const float* audio,
+                                                               long a_bs, short* pcm, long p_bs, short* host) {
+  PE_KTRACE(34);
+  pcm16_body<true>(lens, len_mul, nullptr, audio, a_bs, pcm, p_bs, host, gq, gcap);
 }
 
 // Streaming decode: copy frames [win[0], win[0]+win[1]) of z [C][zs] into the window buffer [C][ws]

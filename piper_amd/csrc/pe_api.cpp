@@ -475,6 +475,44 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
   });
 }
 
+int pe_set_loudness(pe_engine* e, int32_t on, float target_lufs, float ceiling_db) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_loudness(on != 0, target_lufs, ceiling_db);
+  });
+}
+
+int pe_get_loudness(pe_engine* e, int32_t* on, float* target_lufs, float* ceiling_db) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (on) *on = e->eng->loudness_on() ? 1 : 0;
+    if (target_lufs) *target_lufs = e->eng->loudness_target();
+    if (ceiling_db) *ceiling_db = e->eng->loudness_ceiling_db();
+  });
+}
+
+int pe_last_loudness(pe_engine* e, float* lufs, float* scale, float* peak, int32_t* flags, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->last_loudness(lufs, scale, peak, flags, capacity);
+  });
+}
+
+int pe_loudness_filter(int32_t fs, double coef[10]) {
+  return guard([&] {
+    if (!coef) throw std::runtime_error("null argument");
+    pe::Engine::loudness_filter(fs, coef);
+  });
+}
+
+int pe_debug_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs,
+                      float target_lufs, float ceiling_db, float* lufs, float* scale, int32_t* flags) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_loudness(x, batch, stride, valid, fs, target_lufs, ceiling_db, lufs, scale, flags);
+  });
+}
+
 int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
                       const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
   return guard([&] {

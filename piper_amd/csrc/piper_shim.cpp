@@ -355,6 +355,16 @@ static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) 
   } else if (!on || out != sc.outputSampleRate) {
     check(pe_set_output_rate(session.engine, sc.sampleRate, sc.outputSampleRate));
   }
+  // SynthesisConfig::targetLufs, likewise: pe_set_loudness only when the engine is not already there
+  int32_t lon = 0;
+  float lt = 0.f, lc = 0.f;
+  check(pe_get_loudness(session.engine, &lon, &lt, &lc));
+  if (!sc.targetLufs) {
+    if (lon) check(pe_set_loudness(session.engine, 0, 0.f, 0.f));
+  } else if (!lon || lt != *sc.targetLufs || lc != sc.peakCeilingDb) {
+    if (!want) check(pe_set_output_rate(session.engine, sc.sampleRate, 0));      // (an .onnx carries no rate: sampleRate is the native one)
+    check(pe_set_loudness(session.engine, 1, *sc.targetLufs, sc.peakCeilingDb));
+  }
 }
 
 void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisConfig, ModelSession& session,

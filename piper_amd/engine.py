@@ -404,6 +404,53 @@ class Engine:
                                                    p.ctypes.data_as(C.POINTER(C.c_float)), g.size, C.byref(n)))
         return g[:n.value], p[:n.value]
 
+    LOUD_SHORT, LOUD_UNMEASURABLE, LOUD_LIMITED = 1, 2, 4
+
+    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0):
+        """Deliver every WHOLE utterance at ``target_lufs`` LUFS (ITU-R BS.1770-4 gated integrated loudness, mono,
+        measured on the device on the floats the call delivers) under a sample-peak ceiling of ``ceiling_db`` dBFS
+        (include/piper_hip.h: pe_set_loudness). ``None``: off, the default -- every utterance scaled by
+        ``32767 / max(0.01, peak)``. The floats never change; stream chunks keep their own rules."""
+        if target_lufs is None:
+            self._check(self._lib.pe_set_loudness(self._h, 0, 0.0, 0.0))
+        else:
+            self._check(self._lib.pe_set_loudness(self._h, 1, float(target_lufs), float(ceiling_db)))
+
+    def loudness(self):
+        """(target_lufs or None while off, ceiling_db) as set by ``set_loudness``."""
+        on, t, c = C.c_int32(), C.c_float(), C.c_float()
+        self._check(self._lib.pe_get_loudness(self._h, C.byref(on), C.byref(t), C.byref(c)))
+        return (float(t.value) if on.value else None), float(c.value)
+
+    def last_loudness(self):
+        """(lufs, scale, peak, flags) arrays of the last fetched whole-utterance call, one entry per utterance
+        (pe_last_loudness); empty when that call ran with the setting off. ``lufs`` is -inf where not measurable."""
+        n = C.c_int32()
+        self._check(self._lib.pe_last_loudness(self._h, None, None, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        L, s, p, f = np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_last_loudness(self._h, L.ctypes.data_as(fp), s.ctypes.data_as(fp), p.ctypes.data_as(fp),
+                                               f.ctypes.data_as(C.POINTER(C.c_int32)), m, C.byref(n)))
+        return L[:n.value], s[:n.value], p[:n.value], f[:n.value]
+
+    def debug_loudness(self, rows, fs: int, target_lufs: float = -23.0, ceiling_db: float = -1.0):
+        """Test hook (pe_debug_loudness): the two loudness kernels alone on ``rows``, a list of 1-D float arrays at rate
+        ``fs``. Returns (lufs, scale, flags) arrays, one entry per row."""
+        B = len(rows)
+        valid = np.asarray([len(r) for r in rows], np.int32)
+        stride = max(1, int(valid.max()))
+        x = np.zeros((B, stride), np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        L, s, f = np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.int32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_debug_loudness(
+            self._h, x.ctypes.data_as(fp), B, stride, valid.ctypes.data_as(C.POINTER(C.c_int32)), int(fs),
+            float(target_lufs), float(ceiling_db), L.ctypes.data_as(fp), s.ctypes.data_as(fp),
+            f.ctypes.data_as(C.POINTER(C.c_int32))))
+        return L, s, f
+
     def _rates(self):
         nat, out, k = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.pe_get_output_rate(self._h, C.byref(nat), C.byref(out), C.byref(k)))
@@ -654,3 +701,13 @@ class StreamPool:
     def leave(self, slot: int):
         """Free an occupied slot at once (the listener hung up)."""
         self._eng._check(self._eng._lib.pe_stream_pool_leave(self._eng._h, int(slot)))
+
+
+def loudness_filter(fs: int, lib=None) -> np.ndarray:
+    """The K-weighting biquads of ITU-R BS.1770-4 at rate ``fs`` (pe_loudness_filter; host only): float64
+    [shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2]."""
+    lib = lib if lib is not None else L.get_lib()
+    out = np.zeros(10, np.float64)
+    if lib.pe_loudness_filter(int(fs), out.ctypes.data_as(C.POINTER(C.c_double))):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    return out

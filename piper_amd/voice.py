@@ -56,10 +56,13 @@ class PiperVoice:
 
     @staticmethod
     def load(model_path: Union[str, Path], config_path: Optional[Union[str, Path]] = None,
-             use_cuda: bool = True, device: int = 0, output_sample_rate: Optional[int] = None) -> "PiperVoice":
+             use_cuda: bool = True, device: int = 0, output_sample_rate: Optional[int] = None,
+             target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0) -> "PiperVoice":
         """Load an ONNX voice and its config. ``use_cuda`` is accepted for signature compatibility;
         the engine always runs on the GPU (``device``). ``output_sample_rate`` (new): deliver the audio at this rate,
-        resampled on the GPU before the int16 conversion (Engine.set_output_rate; the config's rate is the native one)."""
+        resampled on the GPU before the int16 conversion (Engine.set_output_rate; the config's rate is the native one).
+        ``target_lufs`` (new): deliver every whole utterance at this integrated loudness (ITU-R BS.1770-4, mono) under a
+        sample-peak ceiling of ``peak_ceiling_db`` dBFS (Engine.set_loudness); streams keep their chunk rule."""
         if config_path is None:
             config_path = f"{model_path}.json"
         with open(config_path, "r", encoding="utf-8") as config_file:
@@ -68,6 +71,10 @@ class PiperVoice:
         session = Engine(onnx_path=str(model_path), device=device)
         if output_sample_rate:
             session.set_output_rate(int(output_sample_rate), native=int(config.sample_rate))
+        if target_lufs is not None:
+            if not output_sample_rate:
+                session.set_output_rate(None, native=int(config.sample_rate))      # (an .onnx carries no rate of its own)
+            session.set_loudness(float(target_lufs), float(peak_ceiling_db))
         return PiperVoice(config=config, session=session, output_sample_rate=output_sample_rate or None)
 
     @property
