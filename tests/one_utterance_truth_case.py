@@ -43,6 +43,10 @@ from piper_amd import _lib as L, weights as W            # noqa: E402
 from piper_amd.engine import Engine                      # noqa: E402
 
 SCALES = (0.667, 1.0, 0.8)
+# {noise_scale, length_scale, noise_w} per utterance of a batched call that mixes them (the first MIXED_SCALES[:B]): f32, as
+# the engine takes them, so that a truth is computed at the very values
+MIXED_SCALES = np.array([(0.667, 1.0, 0.8), (0.5, 1.3, 0.6), (0.8, 0.85, 1.0), (0.3, 1.15, 0.4), (0.9, 0.75, 0.9), (1.0, 1.0, 0.2),
+                         (0.1, 1.4, 0.7), (0.667, 0.9, 0.5)], np.float32)
 PRODUCT_GATE = 2e-4          # max |d audio| of the f32 path's own parity gate
 CEIL_FLIP = 2e-5             # relative distance from an integer below which a ceil may flip in another summation order
 STAGES = ("x_enc", "m_p", "logs_p", "logw", "z", "audio")
@@ -51,7 +55,9 @@ WIDE = {"tiny192": dict(hidden=192, inter=192, filter=96, n_layers=2)}      # ti
 
 # K per stage tensor (max and rms gate alike), from the measured worst ratios in profiles/one_utterance_truth.md: 8 wherever
 # the worst ratio is at most 4.
-GATES = {"gpu": {s: 8 for s in STAGES}, "emu": {s: 8 for s in STAGES}}
+GATES = {"gpu": {s: 8 for s in STAGES}, "emu": {s: 8 for s in STAGES},
+         # the batched path (tests/test_gpu_batched_truth.py, tests/test_batched_truth_emu.py; profiles/batched_truth.md)
+         "gpu-batched": {s: 8 for s in STAGES}, "emu-batched": {s: 8 for s in STAGES}}
 ORACLE_MARGIN = 1e-4         # relative distance from an integer that the chosen seeds keep with the oracle alone
 
 ROWS = []        # (target, voice, lens, route, mode, utterance, stage, e_hip, e_ref, r_hip, r_ref): the table of the profile file
@@ -176,8 +182,11 @@ def run(eng, ids, scales, sids, nw, nz=None, graph="spec"):
     # repeat does not pin)
     other = [np.ascontiguousarray(np.asarray(s)[::-1]) for s in ids]
     onw = np.zeros_like(nw)
+    top = 1 + max(int(np.max(s)) for s in ids)
     for b, s in enumerate(ids):
         onw[b, :, :len(s)] = nw[b, :, :len(s)][:, ::-1]
+        if np.array_equal(other[b], s):          # a palindrome (one id of a batched call): the next id and the negated noise instead
+            other[b], onw[b] = (np.asarray(s) + 1) % top, -nw[b]
     first = _tensors(eng, eng.synthesize_batch(other, scales, sids=sids, noise_w=onw), other)
     s0, g0 = eng.speculation_stats, eng.graph_stats
     r = eng.synthesize_batch(ids, scales, sids=sids, noise_w=nw)
@@ -223,26 +232,29 @@ def figures(hip, t64, t32):
             "r_ref": float(np.sqrt(np.mean(dr * dr))), "fl": 2.0 ** -23 * float(np.max(np.abs(t64)))}
 
 
-def measure(w, cfg, ids, scales, nw, got, sid=None):
-    """Figures per stage tensor of one utterance, plus the f64 truths of stages D and R that the exact checks need."""
+def measure(w, cfg, ids, scales, nw, got, sid=None, stages="EDRFG"):
+    """Figures per stage tensor of one utterance, plus the f64 truths of stages D and R that the exact checks need. `stages`:
+    the stages computed (a long utterance of a batched call leaves its flow and generator out: their f64 truths cost minutes)."""
     nz = got["noise_z"]
     C = cfg.inter
     t = {}
     for dt in (torch.float64, torch.float32):
         d = {}
-        for st in "EDRFG":
+        for st in stages:
             d.update(_truth(w, cfg, st, dt, ids, scales, nw, nz, got, sid))
         t[dt] = d
     t64, t32 = t[torch.float64], t[torch.float32]
     hip = {"x_enc": got["x_enc"], "m_p": got["stats"][:C], "logs_p": got["stats"][C:], "logw": got["logw"], "z": got["z"],
            "audio": got["audio"]}
-    return {s: figures(hip[s], t64[s], t32[s]) for s in STAGES}, t64
+    return {s: figures(hip[s], t64[s], t32[s]) for s in STAGES if s in t64}, t64
 
 
 def check_gates(fig, gates, what):
     """e_hip <= K e_ref + fl and r_hip <= K r_ref per stage tensor; every figure is printed before anything is asserted."""
     bad = []
     for s in STAGES:
+        if s not in fig:                   # a stage left out of this utterance (check_call's `stages`)
+            continue
         f, K = fig[s], gates[s]
         print(f"{what} {s}: e_hip {f['e_hip']:.3e} e_ref {f['e_ref']:.3e} ratio {f['e_hip'] / max(f['e_ref'], 1e-300):.2f} | "
               f"r_hip {f['r_hip']:.3e} r_ref {f['r_ref']:.3e} ratio {f['r_hip'] / max(f['r_ref'], 1e-300):.2f} | fl {f['fl']:.2e} K {K}")
@@ -282,10 +294,13 @@ def check_regulator(got, t64, what):
     assert np.all(err <= bound), (what, worst, np.argwhere(err > bound)[:4])
 
 
-def check_call(target, vname, ids, scales, sids, nw, got, route, mode="f32", wseed=1234, gated=STAGES, k_case=None):
-    """Every check of one compared call; returns the figures per utterance. `gated`: the stage tensors under the K gates (a
-    split matrix mode gates z and audio by truth_gates instead). `k_case`: {stage: K} of this case alone where its measured
-    ratio asks for more than GATES (profiles/one_utterance_truth.md says why)."""
+def check_call(target, vname, ids, scales, sids, nw, got, route, mode="f32", wseed=1234, gated=STAGES, k_case=None, stages=None):
+    """Every check of one compared call, on every utterance of it; returns the figures per utterance. `scales`: one triple,
+    or one per utterance ([B][3]: each utterance against the truth of its own). `gated`: the stage tensors under the K gates
+    (a split matrix mode gates z and audio by truth_gates instead). `k_case`: {stage: K}, or {(utterance, stage): K}
+    for one utterance of a batched call, of this case alone where its measured ratio asks for more than GATES (the profile file
+    of the target's path says why). `stages`: {utterance: the stages
+    checked on it} where that is not all of "EDRFG" (an utterance too long for its f64 flow and generator: "ED")."""
     cfg, w = voice(vname, wseed)
     lens = [len(s) for s in ids]
     figs = []
@@ -294,15 +309,24 @@ def check_call(target, vname, ids, scales, sids, nw, got, route, mode="f32", wse
         sid = None if sids is None else sids[b]
         g = got[b]
         assert np.array_equal(g["noise_w"], nw[b][:, :lens[b]]), what
-        fig, t64 = measure(w, cfg, ids[b], tuple(float(x) for x in scales), nw[b], g, sid)
+        sc = tuple(float(x) for x in (scales[b] if np.ndim(scales) == 2 else scales))
+        todo = (stages or {}).get(b, "EDRFG")
+        assert "E" in todo and "D" in todo, todo
+        fig, t64 = measure(w, cfg, ids[b], sc, nw[b], g, sid, todo)
         for s in STAGES:
-            f = fig[s]
-            ROWS.append((target, vname, lens, route, mode, b, s, f["e_hip"], f["e_ref"], f["r_hip"], f["r_ref"]))
-        sc = tuple(float(x) for x in scales)
+            if s in fig:
+                f = fig[s]
+                ROWS.append((target, vname, lens, route, mode, b, s, f["e_hip"], f["e_ref"], f["r_hip"], f["r_ref"]))
         alone = _truth(w, cfg, "D", torch.float64, ids[b], sc, nw[b], None, {"x_enc": t64["x_enc"]}, sid)["w"]
         check_durations(g, t64, what, alone)
-        check_regulator(g, t64, what)
-        K = dict(GATES[target], **(k_case or {}))
+        if "R" in todo:
+            check_regulator(g, t64, what)
+        K = dict(GATES[target])
+        for key, k in (k_case or {}).items():          # a stage, or (utterance, stage)
+            if not isinstance(key, tuple):
+                K[key] = k
+            elif key[0] == b:
+                K[key[1]] = k
         check_gates(fig, {s: (K[s] if s in gated else None) for s in STAGES}, what)
         figs.append(fig)
     return figs
