@@ -95,10 +95,12 @@ struct SynthesisConfig {
   // reference, which always delivers sampleRate.)
   int outputSampleRate = 0;
   // Target integrated loudness in LUFS (ITU-R BS.1770-4, mono) of every whole utterance -- every phrase of textToAudio lands
-  // on the same level -- under a SAMPLE-peak ceiling of peakCeilingDb dBFS (piper_hip.h: pe_set_loudness). Unset, the default:
-  // the reference's rule, every phrase scaled to its own peak. (Beyond the reference.)
+  // on the same level -- under a ceiling of peakCeilingDb dB (piper_hip.h: pe_set_loudness). Unset, the default:
+  // the reference's rule, every phrase scaled to its own peak. The ceiling holds the sample peak, or with truePeak the true
+  // peak of BS.1770-4 Annex 2 as well (dBTP; piper_hip.h: pe_set_loudness_ceiling). (Beyond the reference.)
   std::optional<float> targetLufs;
   float peakCeilingDb = -1.0f;
+  bool truePeak = false;
   int sampleWidth = 2;  // 16-bit
   int channels = 1;     // mono
 

@@ -300,9 +300,10 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
  *              absolute-gated blocks) - 10; L = -0.691 + 10 log10(mean z over blocks with l_j > -70 and l_j > G).
  *   n < 4 h    PE_LOUD_SHORT: one block over the whole utterance (mean of y^2 over n), no relative gate.
  *   silence    nothing passes the absolute gate, or n == 0: PE_LOUD_UNMEASURABLE, scale = 32767 (the waveform as generated).
- *   scale      32767 * min(10^((target_lufs - L) / 20), C / p), C = 10^(ceiling_db / 20), p = max |x|; PE_LOUD_LIMITED when
- *              the second term is the smaller. One f32 per utterance; products are clamped to [-32768, 32767] and truncated.
- * The ceiling is a SAMPLE peak: inter-sample (true) peaks are not measured. The measurement is mono and covers whole
+ *   scale      32767 * min(10^((target_lufs - L) / 20), C / P), C = 10^(ceiling_db / 20), P = p = max |x|, or with the
+ *              true-peak ceiling below P = max(p, t); PE_LOUD_LIMITED when the second term is the smaller. One f32 per
+ *              utterance; products are clamped to [-32768, 32767] and truncated.
+ * The ceiling holds the sample peak by default and the true peak after the call below. The measurement is mono and covers whole
  * utterances only: pe_stream_next, pe_stream_next_batch and pe_stream_pool_next keep their chunk rule and the
  * pe_set_stream_gain modes -- an integrated loudness is not known before an utterance ends -- and the setting may change
  * while a stream is live. target_lufs in [-40, -5], ceiling_db in [-20, 0], both finite (on == 0: ignored); a voice without
@@ -324,6 +325,38 @@ int pe_loudness_filter(int32_t fs, double coef[10]);
  * the handle's setting and rate. */
 int pe_debug_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs,
                       float target_lufs, float ceiling_db, float* lufs, float* scale, int32_t* flags);
+
+/* What the ceiling of the target loudness holds. PE_PEAK_SAMPLE, the default: p, the largest |sample|. PE_PEAK_TRUE: the true
+ * peak of ITU-R BS.1770-4 Annex 2 as well, which delivery specifications name (EBU R128: -23 LUFS, at most -1 dBTP). It is
+ * measured on the device by one more launch per whole-utterance call, with no host round trip:
+ *   Q          ceil(192000 / fs): 4 at 48000 Hz, 5 at 44100, 9 at 22050, 12 at 16000, 24 at 8000.
+ *   y[m]       x interpolated Q times, m = 0 .. n Q - 1, x = 0 outside [0, n), by the filter the rate conversion builds for the
+ *              pair fs -> Q fs: Kaiser-windowed sinc, cutoff 0.46 fs, 16 zero crossings a side, beta = 8.6, half-width
+ *              K = 18 samples of x; computed in f64, rounded once to f32.
+ *   t          max |y[m]| (0 for n == 0); P = max(p, t), because phase 0 of that filter has gain 0.92, not 1: a lone
+ *              impulse of 1.0 has t = 0.92.
+ * The measure is flat within the rate conversion's 0.07 dB up to 0.8 of the Nyquist frequency and under-reads above it
+ * (-3.8 dB at 0.9 of Nyquist, computed in f64) -- the compromise Annex 2's own filter makes. Everything else of the loudness
+ * setting is unchanged, and pe_last_loudness keeps reporting p. The kind may be set while the loudness is off (it is
+ * remembered and takes effect once it is on) and while a stream is live (streams do not see it). An unknown kind is refused
+ * with a message that names the value, and so is PE_PEAK_TRUE while the loudness is on at a delivered rate outside
+ * [8000, 48000] Hz; pe_set_loudness and pe_set_output_rate refuse what would make that combination true. A refused call
+ * changes nothing. The kind is part of the graph keys next to on / off; with PE_PEAK_SAMPLE every launch, graph and bit of
+ * output is what it is without this call. The read-back gives the kind, Q at the delivered rate (0 where the rate is unknown
+ * or outside the range) and K; any pointer may be NULL. */
+enum { PE_PEAK_SAMPLE = 0, PE_PEAK_TRUE = 1 };
+int pe_set_loudness_ceiling(pe_engine* e, int32_t kind);
+int pe_get_loudness_ceiling(pe_engine* e, int32_t* kind, int32_t* oversample, int32_t* half_width);
+/* The last fetched whole-utterance call on the handle: true_peak[i] = t of utterance i, *n utterances (0: it did not run with
+ * PE_PEAK_TRUE and the loudness on). true_peak may be NULL; capacity < *n is an error. */
+int pe_last_true_peak(pe_engine* e, float* true_peak, int64_t capacity, int32_t* n);
+/* Host only: the interpolator at rate fs (8000 .. 48000) in f64, before the rounding to f32: *oversample = Q, *half_width = K,
+ * *n = Q * 2 K, and coef[ph * 2 K + k] = the tap of phase ph on x[c - K + 1 + k] for the outputs y[c Q + ph] (coef may be
+ * NULL to ask for *n; capacity < *n is an error). */
+int pe_true_peak_filter(int32_t fs, int32_t* oversample, int32_t* half_width, double* coef, int64_t capacity, int64_t* n);
+/* Test hook: the true-peak kernel alone on caller-supplied rows x[batch][stride] (host), row b holding valid[b] samples at
+ * rate fs: t[batch]. Independent of the handle's setting and rate. */
+int pe_debug_true_peak(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, float* t);
 
 /* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
  * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them

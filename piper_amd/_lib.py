@@ -22,6 +22,7 @@ SYMBOLS = [
     "pe_get_durations", "pe_get_info", "pe_set_output_rate", "pe_get_output_rate", "pe_debug_resample",
     "pe_set_stream_gain", "pe_get_stream_gain", "pe_stream_last_gains",
     "pe_set_loudness", "pe_get_loudness", "pe_last_loudness", "pe_loudness_filter", "pe_debug_loudness",
+    "pe_set_loudness_ceiling", "pe_get_loudness_ceiling", "pe_last_true_peak", "pe_true_peak_filter", "pe_debug_true_peak",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
     "pe_stream", "pe_debug_tensor", "pe_debug_randn", "pe_rng_calls", "pe_run_launches", "pe_speculation_stats", "pe_warmup", "pe_graph_stats", "pe_xcc_pattern", "pe_device_pci_bus_id", "pe_policy_describe", "pe_last_error", "pe_destroy",
     "pe_group_create", "pe_group_broadcast_path", "pe_group_size", "pe_group_engine", "pe_group_synthesize_batch", "pe_group_synthesize_batch_scaled",
@@ -107,6 +108,11 @@ def bind(path: str) -> C.CDLL:
     lib.pe_last_loudness.argtypes = [vp, f32p, f32p, f32p, i32p, C.c_int64, i32p]
     lib.pe_loudness_filter.argtypes = [C.c_int32, C.POINTER(C.c_double)]
     lib.pe_debug_loudness.argtypes = [vp, f32p, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_float, C.c_float, f32p, f32p, i32p]
+    lib.pe_set_loudness_ceiling.argtypes = [vp, C.c_int32]
+    lib.pe_get_loudness_ceiling.argtypes = [vp, i32p, i32p, i32p]
+    lib.pe_last_true_peak.argtypes = [vp, f32p, C.c_int64, i32p]
+    lib.pe_true_peak_filter.argtypes = [C.c_int32, i32p, i32p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
+    lib.pe_debug_true_peak.argtypes = [vp, f32p, C.c_int32, C.c_int64, i32p, C.c_int32, f32p]
     lib.pe_set_seed.argtypes = [vp, C.c_uint64]
     lib.pe_set_seed.restype = None
     lib.pe_profile_enable.argtypes = [vp, C.c_int]

@@ -658,7 +658,7 @@ void Engine::run() {
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
     // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, ld_on_ ? "|l1" : "");
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -685,7 +685,7 @@ void Engine::run() {
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, ld_on_ ? "|l1" : "");
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
     run_stage('B', key);
   }
 }
@@ -745,7 +745,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, ld_on_ ? "|l1" : "");
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
   run_stage('B', key);
   return false;
 }
@@ -1358,6 +1358,31 @@ static double bessel_i0(double x) {
   return sum;
 }
 
+// The interpolation filter of the rate pair native -> output, shared by the resampler and the true-peak
+// measure: L = output / gcd, M = native / gcd, the half-width K in native samples, Tp = 2 K rounded up to 4 taps per phase.
+// table != null: the L x Tp polyphase table in f64, entry [ph][k] the Kaiser-windowed sinc (cutoff 0.46 of the lower rate,
+// Z = 16 zero crossings a side, beta = 8.6) at (ph + (K - 1 - k) L) / (L native) seconds; entries past the window's
+// support, the padding up to Tp included, are exact zeros. The device tables are these values rounded once to f32.
+void Engine::resample_filter(int native, int output, int& L, int& M, int& K, int& Tp, std::vector<double>* table) {
+  const int g = std::gcd(native, output);
+  L = output / g; M = native / g;
+  const double fmin = std::min(native, output), fc = 0.92 * fmin / 2.0, Z = 16.0, beta = 8.6, Th = Z / (2.0 * fc);
+  K = (int)std::ceil(Z * (double)native / (0.92 * fmin) - 1e-9);
+  Tp = rup(2 * K, 4);
+  if (!table) return;
+  table->assign((size_t)L * Tp, 0.0);
+  const double i0b = bessel_i0(beta), pi = 3.14159265358979323846;
+  for (int ph = 0; ph < L; ++ph)
+    for (int k = 0; k < 2 * K; ++k) {
+      const double t = ((double)ph + (double)(K - 1 - k) * (double)L) / ((double)L * (double)native);
+      const double u = t / Th;
+      if (std::fabs(u) > 1.0) continue;
+      const double x = 2.0 * fc * t;
+      const double sinc = std::fabs(x) < 1e-12 ? 1.0 : std::sin(pi * x) / (pi * x);
+      (*table)[(size_t)ph * Tp + k] = (2.0 * fc / (double)native) * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b;
+    }
+}
+
 void Engine::set_output_rate(int native, int output) {
   EntryLock entry_lock;
   const int header = arch_[A_SR];
@@ -1379,38 +1404,27 @@ void Engine::set_output_rate(int native, int output) {
                              (sp_slots_ ? "stream pool is open" : "stream is live") + " on this handle");
   const bool on = output != 0 && output != native;
   if (ld_on_) loud_check_rate(on ? output : native);    // (the target loudness is measured at the delivered rate)
+  if (ld_on_ && ld_kind_ == PEAK_TRUE) tp_check_rate(on ? output : native);
   const std::string pair = std::to_string(native) + " -> " + std::to_string(output) + " Hz";
   int L = 1, M = 1, K = 0, Tp = 0, tile = RS_TILE;
   std::vector<float> table;
   if (on) {
     if (output < 8000 || output > 48000)
       throw std::runtime_error("output rate outside [8000, 48000]: " + pair);
-    const int g = std::gcd(native, output);
-    L = output / g; M = native / g;
+    resample_filter(native, output, L, M, K, Tp, nullptr);
     if (L > 640)
       throw std::runtime_error("rate pair " + pair + " needs a table of " + std::to_string(L) + " phases (output / gcd), more than 640");
-    const double fmin = std::min(native, output), fc = 0.92 * fmin / 2.0, Z = 16.0, beta = 8.6, Th = Z / (2.0 * fc);
-    K = (int)std::ceil(Z * (double)native / (0.92 * fmin) - 1e-9);
     if (K > hop_)
       throw std::runtime_error("rate pair " + pair + " needs a filter half-width of " + std::to_string(K) +
                                " native samples, more than the voice's hop size " + std::to_string(hop_));
-    Tp = rup(2 * K, 4);
     // output samples per workgroup: as many as keep the native span (tile * M / L + Tp + alignment slack) inside the LDS array
     const long room = (long)(RS_SPAN - Tp - 6) * L / M;
     tile = (int)std::min<long>(RS_TILE, room / 64 * 64);
     if (tile < 64) throw std::runtime_error("rate pair " + pair + ": the native span of 64 outputs exceeds the staging buffer");
-    table.assign((size_t)L * Tp, 0.f);
-    const double i0b = bessel_i0(beta), pi = 3.14159265358979323846;
-    for (int ph = 0; ph < L; ++ph)
-      for (int k = 0; k < 2 * K; ++k) {
-        const double t = ((double)ph + (double)(K - 1 - k) * (double)L) / ((double)L * (double)native);
-        const double u = t / Th;
-        if (std::fabs(u) > 1.0) continue;
-        const double x = 2.0 * fc * t;
-        const double sinc = std::fabs(x) < 1e-12 ? 1.0 : std::sin(pi * x) / (pi * x);
-        table[(size_t)ph * Tp + k] =
-            (float)((2.0 * fc / (double)native) * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b);
-      }
+    std::vector<double> exact;
+    resample_filter(native, output, L, M, K, Tp, &exact);
+    table.resize(exact.size());
+    for (size_t i = 0; i < exact.size(); ++i) table[i] = (float)exact[i];
   }
   if (on == rs_on_ && (!on || (native == rs_native_ && output == rs_out_))) {      // nothing changes (the native rate is noted)
     rs_native_ = native;
@@ -1653,8 +1667,48 @@ void Engine::loud_free() {
   if (ld_seg_) hipFree(ld_seg_);
   if (ld_dev_) hipFree(ld_dev_);
   if (ld_ctl_) hipHostFree(ld_ctl_);
+  if (tp_coef_) hipFree(tp_coef_);
+  if (tp_words_) hipFree(tp_words_);
   ld_coef_ = ld_seg_ = nullptr; ld_dev_ = ld_ctl_ = nullptr;
   ld_seg_rows_ = 0; ld_nseg_cap_ = 0; ld_cap_ = 0;
+  tp_coef_ = nullptr; tp_words_ = nullptr; tp_fs_ = tp_Q_ = tp_cap_ = 0;
+}
+
+void Engine::tp_check_rate(int fs) {
+  if (fs < 8000 || fs > 48000)
+    throw std::runtime_error("the true-peak ceiling is not available at " + std::to_string(fs) + " Hz (outside [8000, 48000])");
+}
+
+void Engine::true_peak_filter(int fs, int& Q, int& K, std::vector<double>& coef) {
+  tp_check_rate(fs);
+  Q = true_peak_oversample(fs);
+  int L, M, Tp;
+  resample_filter(fs, Q * fs, L, M, K, Tp, &coef);
+  if (L != Q || M != 1 || K != TP_K || Tp != TP_TAPS || Q > TP_MAXQ)
+    throw std::runtime_error("true-peak filter at " + std::to_string(fs) + " Hz: unexpected geometry");
+}
+
+void Engine::tp_upload_table(int fs) {
+  int Q, K;
+  std::vector<double> exact;
+  true_peak_filter(fs, Q, K, exact);
+  float table[TP_MAXQ * TP_TAPS] = {};
+  for (size_t i = 0; i < exact.size(); ++i) table[i] = (float)exact[i];
+  if (!tp_coef_) PE_HIP(hipMalloc((void**)&tp_coef_, sizeof(table)));
+  PE_HIP(hipMemcpy(tp_coef_, table, sizeof(table), hipMemcpyHostToDevice));
+  tp_fs_ = fs; tp_Q_ = Q;
+}
+
+void Engine::set_loudness_ceiling(int kind) {
+  EntryLock entry_lock;
+  if (kind != PEAK_SAMPLE && kind != PEAK_TRUE)
+    throw std::runtime_error("unknown loudness ceiling kind " + std::to_string(kind) + " (0: sample peak, 1: true peak)");
+  if (kind == PEAK_TRUE && ld_on_) tp_check_rate(output_rate());
+  if (kind == ld_kind_) return;
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles first)
+  // the kind picks the launches and is part of the graph keys: nothing is dropped, streams are not touched
+  ld_kind_ = kind;
 }
 
 void Engine::set_loudness(bool on, float target_lufs, float ceiling_db) {
@@ -1665,6 +1719,7 @@ void Engine::set_loudness(bool on, float target_lufs, float ceiling_db) {
     if (!std::isfinite(ceiling_db) || ceiling_db < -20.f || ceiling_db > 0.f)
       throw std::runtime_error("peak ceiling " + std::to_string(ceiling_db) + " dB outside [-20, 0]");
     loud_check_rate(output_rate());
+    if (ld_kind_ == PEAK_TRUE) tp_check_rate(output_rate());
   }
   PE_HIP(hipSetDevice(device_));
   finish_run();                                        // (a speculative run still in flight settles first)
@@ -1688,6 +1743,24 @@ void Engine::ensure_loudness() {
   if (!ld_coef_ || ld_fs_ != output_rate()) loud_upload_filter(output_rate());
   const int nseg = (int)(So_ / ld_h_) + 2;
   const int want_cap = (int)((std::max<size_t>(std::max(capA_B_, capB_B_), 64) + 1) & ~(size_t)1);
+  if (ld_kind_ == PEAK_TRUE) {
+    // (a first allocation is in no graph yet; a changed table or grown words are inside the PEAK_TRUE graphs)
+    if (!tp_coef_ || tp_fs_ != output_rate()) {
+      PE_HIP(hipStreamSynchronize(stream_));
+      if (tp_coef_) drop_graphs();
+      tp_upload_table(output_rate());
+    }
+    if (!tp_words_ || tp_cap_ < want_cap) {
+      PE_HIP(hipStreamSynchronize(stream_));
+      if (tp_words_) { drop_graphs(); PE_HIP(hipFree(tp_words_)); tp_words_ = nullptr; }
+      tp_cap_ = 0;
+      PE_HIP(hipMalloc((void**)&tp_words_, (size_t)want_cap * sizeof(unsigned)));
+      if (pol_.debug_poison) poison(tp_words_, (size_t)want_cap * sizeof(unsigned));
+      else PE_HIP(hipMemset(tp_words_, 0, (size_t)want_cap * sizeof(unsigned)));
+      PE_HIP(hipDeviceSynchronize());
+      tp_cap_ = want_cap;
+    }
+  }
   if (ld_seg_ && ld_seg_rows_ >= capB_B_ && ld_nseg_cap_ >= nseg && ld_ctl_ && ld_dev_ && ld_cap_ >= want_cap) return;
   PE_HIP(hipStreamSynchronize(stream_));
   drop_graphs();
@@ -1719,8 +1792,14 @@ void Engine::ensure_loudness() {
 }
 
 void Engine::loud_collect() {
+  ll_tn_ = 0;
   if (!ld_on_ || !ld_ctl_ || B_ > ld_cap_) { ll_n_ = 0; return; }
   const int n = B_, cap = ld_cap_;
+  if (ld_kind_ == PEAK_TRUE) {
+    const float* tf = reinterpret_cast<const float*>(ld_ctl_) + ldc_o_tpeak(cap);
+    ll_tpeak_.assign(tf, tf + n);
+    ll_tn_ = n;
+  }
   const float* rf = reinterpret_cast<const float*>(ld_ctl_ + ldc_o_report(cap));
   ll_lufs_.assign(rf, rf + n);
   ll_scale_.assign(rf + ld_o_scale(cap), rf + ld_o_scale(cap) + n);
@@ -1740,6 +1819,67 @@ int Engine::last_loudness(float* lufs, float* scale, float* peak, int32_t* flags
     if (flags) flags[b] = ll_flags_[b];
   }
   return ll_n_;
+}
+
+int Engine::last_true_peak(float* t, int64_t capacity) {
+  EntryLock entry_lock;
+  if (ll_n_ < 0) throw std::runtime_error("no whole-utterance call fetched on this handle yet");
+  if (t && capacity < ll_tn_) throw std::runtime_error("true-peak report buffer too small");
+  if (t)
+    for (int b = 0; b < ll_tn_; ++b) t[b] = ll_tpeak_[b];
+  return ll_tn_;
+}
+
+void Engine::debug_true_peak(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float* t) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!x || !valid || !t) throw std::runtime_error("null argument");
+  if (stride < 0 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [0, 2^28]");
+  int Q, K, maxn = 0;
+  std::vector<double> exact;
+  true_peak_filter(fs, Q, K, exact);
+  float table[TP_MAXQ * TP_TAPS] = {};
+  for (size_t i = 0; i < exact.size(); ++i) table[i] = (float)exact[i];
+  for (int b = 0; b < batch; ++b) {
+    if (valid[b] < 0 || valid[b] > stride) throw std::runtime_error("row " + std::to_string(b) + ": valid length outside [0, stride]");
+    maxn = std::max(maxn, valid[b]);
+  }
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const long xs = (long)((std::max<int64_t>(stride, 1) + 3) & ~(int64_t)3);
+  float *dx = nullptr, *dcoef = nullptr;
+  int* dval = nullptr;
+  unsigned* dtp = nullptr;
+  auto release = [&]() {
+    if (dx) hipFree(dx);
+    if (dcoef) hipFree(dcoef);
+    if (dval) hipFree(dval);
+    if (dtp) hipFree(dtp);
+  };
+  try {
+    PE_HIP(hipMalloc((void**)&dx, (size_t)batch * xs * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&dcoef, sizeof(table)));
+    PE_HIP(hipMalloc((void**)&dval, (size_t)batch * sizeof(int)));
+    PE_HIP(hipMalloc((void**)&dtp, (size_t)batch * sizeof(unsigned)));
+    for (int b = 0; b < batch; ++b)
+      if (stride > 0)
+        PE_HIP(hipMemcpyAsync(dx + (size_t)b * xs, x + (size_t)b * stride, (size_t)stride * sizeof(float), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dcoef, table, sizeof(table), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dval, valid, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemsetAsync(dtp, 0, (size_t)batch * sizeof(unsigned), stream_));
+    PE_HIP(hipStreamSynchronize(stream_));             // (the staging arrays are pageable)
+    TpP p{};
+    p.x = dx; p.x_bs = xs; p.lens = dval; p.len_mul = 1; p.x_cap = (long)stride;
+    p.coef = dcoef; p.Q = Q; p.tpeak = dtp;
+    launch::true_peak(dim3((unsigned)std::max(1, (maxn + TP_TILE - 1) / TP_TILE), batch), stream_, p);
+    PE_HIP(hipMemcpyAsync(t, dtp, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
 }
 
 void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
@@ -1806,7 +1946,7 @@ void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int
     p.x = dx; p.x_bs = xs; p.lens = dval; p.len_mul = 1; p.x_cap = (long)stride;
     p.coef = dcoef; p.h = h; p.W = W; p.R = R; p.seg = dseg; p.nseg_cap = nseg_cap;
     launch::loudness_seg(dim3((unsigned)std::max(1, (maxn + h - 1) / h), batch), stream_, p);
-    launch::loudness_gain(stream_, batch, dseg, nseg_cap, dval, 1, (long)stride, h, dpk, ctl, gd, cap);
+    launch::loudness_gain(stream_, batch, dseg, nseg_cap, dval, 1, (long)stride, h, dpk, nullptr, ctl, gd, cap);
     PE_HIP(hipStreamSynchronize(stream_));
     const float* rf = reinterpret_cast<const float*>(ctl + ldc_o_report(cap));
     for (int b = 0; b < batch; ++b) {

@@ -118,6 +118,8 @@ class Engine {
   // L = output / gcd <= 640, half-width K <= hop), a native rate that contradicts the header, or while a stream, a batch
   // stream or a stream pool is live. A change drops every captured graph.
   void set_output_rate(int native, int output);
+  // host only: geometry and (table != null) the f64 polyphase table of a rate pair; the one place the filter is built
+  static void resample_filter(int native, int output, int& L, int& M, int& K, int& Tp, std::vector<double>* table);
   int native_rate() const { return rs_native_ ? rs_native_ : arch_[A_SR]; }
   int output_rate() const { return rs_on_ ? rs_out_ : native_rate(); }
   int resample_half_width() const { return rs_on_ ? rs_K_ : 0; }
@@ -132,7 +134,8 @@ class Engine {
   // utterance scaled by 32767 / max(0.01, its peak). On: every whole-utterance call -- synthesize, the batch calls, run /
   // fetch -- measures the gated integrated loudness L (ITU-R BS.1770-4, mono) of each float waveform it delivers, at the
   // delivered rate, on the device, and converts with scale = 32767 min(10^((target - L) / 20), C / peak),
-  // C = 10^(ceiling_db / 20) a SAMPLE-peak ceiling; an utterance whose loudness cannot be measured (silence) keeps
+  // C = 10^(ceiling_db / 20) a ceiling on the sample peak, or with set_loudness_ceiling(PEAK_TRUE) on the true peak (below:
+  // `peak` is then max(sample peak, true peak)); an utterance whose loudness cannot be measured (silence) keeps
   // scale 32767. The delivered floats are not touched and stream chunks keep their own rules. Throws, and changes nothing,
   // for a target outside [-40, -5] LUFS, a ceiling outside [-20, 0] dB, values that are not finite, or a voice whose
   // delivered rate is unknown or outside [4000, 192000] Hz. target and ceiling are data the kernels read in place; on / off
@@ -146,6 +149,22 @@ class Engine {
   int last_loudness(float* lufs, float* scale, float* peak, int32_t* flags, int64_t capacity);
   // host only: the K-weighting biquads at rate fs, shelf {b0, b1, b2, a1, a2} then high-pass {b0, b1, b2, a1, a2}
   static void loudness_filter(int fs, double coef[10]);
+  // What the ceiling of the target loudness holds (kernels/true_peak.h). PEAK_SAMPLE, the default: the
+  // largest |sample|. PEAK_TRUE: the true peak of ITU-R BS.1770-4 Annex 2 as well -- the largest |sample| of the delivered
+  // floats interpolated Q = ceil(192000 / fs) times by the resampler's own filter for the pair fs -> Q fs, measured on the
+  // device by one more launch per call. The kind may be set with the loudness off (it is remembered) and while a stream is
+  // live (streams do not see it). Throws, and changes nothing, for an unknown kind, or for PEAK_TRUE while the loudness is on
+  // at a delivered rate outside [8000, 48000] Hz; set_loudness and set_output_rate refuse what would make that true. The
+  // kind is part of the graph keys next to on / off: the three sets of graphs stay cached.
+  void set_loudness_ceiling(int kind);
+  int loudness_ceiling_kind() const { return ld_kind_; }
+  static int true_peak_oversample(int fs) { return fs > 0 ? (192000 + fs - 1) / fs : 0; }
+  // per utterance of the last fetched call: the true peak t; returns the utterances (0: that call did not run with PEAK_TRUE)
+  int last_true_peak(float* t, int64_t capacity);
+  // host only: the interpolator at rate fs in f64, coef[ph * 2 K + k] (kernels/true_peak.h); throws outside [8000, 48000]
+  static void true_peak_filter(int fs, int& Q, int& K, std::vector<double>& coef);
+  // test hook: true_peak_kernel alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs
+  void debug_true_peak(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float* t);
   // test hook: the two loudness kernels alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs
   void debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
                       float* lufs, float* scale, int32_t* flags);
@@ -641,6 +660,16 @@ class Engine {
   std::vector<float> ll_lufs_, ll_scale_, ll_peak_;
   std::vector<int32_t> ll_flags_;
   int ll_n_ = -1;                               // utterances of the last fetched call's report (-1: none yet)
+  // true-peak ceiling: the interpolator's table [tp_Q_][TP_TAPS] for the delivered rate tp_fs_ and one word per row, device
+  // allocations of their own next to the loudness blocks (ensure_loudness; kernel arguments inside the PEAK_TRUE graphs)
+  int ld_kind_ = PEAK_SAMPLE;
+  bool tp_on() const { return ld_on_ && ld_kind_ == PEAK_TRUE; }
+  float* tp_coef_ = nullptr; int tp_fs_ = 0, tp_Q_ = 0;
+  unsigned* tp_words_ = nullptr; int tp_cap_ = 0;
+  std::vector<float> ll_tpeak_;
+  int ll_tn_ = 0;
+  static void tp_check_rate(int fs);            // throws the refusal
+  void tp_upload_table(int fs);
   static void loud_check_rate(int fs);          // throws the refusal
   void loud_upload_filter(int fs);              // h / W / R and the filter block for rate fs
   void loud_write_ctl();

@@ -459,11 +459,23 @@ void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, i
   p.x = x; p.x_bs = x_bs; p.lens = lens; p.len_mul = len_mul; p.x_cap = x_bs;
   p.coef = ld_coef_; p.h = ld_h_; p.W = ld_W_; p.R = ld_R_;
   p.seg = ld_seg_; p.nseg_cap = ld_nseg_cap_;
+  const bool tp = ld_kind_ == PEAK_TRUE;
+  if (tp && (!tp_coef_ || !tp_words_ || B > tp_cap_ || tp_fs_ != output_rate()))
+    throw std::runtime_error("true-peak buffers are not sized for this call");
+  p.tpeak = tp ? tp_words_ : nullptr;
   const int nseg = (int)std::min<long>((max_n + ld_h_ - 1) / ld_h_, ld_nseg_cap_);
   // algorithmic bytes: every delivered sample in once (the warm-up is read again out of the caches)
   PE_LAUNCH_KB("loudness_seg_kernel", 4.0 * samples, launch::loudness_seg(dim3((unsigned)nseg, B), stream_, p));
+  if (tp) {
+    // true-peak ceiling: max |x interpolated tp_Q_ times| per row, into the words loudness_seg_kernel cleared
+    TpP q{};
+    q.x = x; q.x_bs = x_bs; q.lens = lens; q.len_mul = len_mul; q.x_cap = x_bs;
+    q.coef = tp_coef_; q.Q = tp_Q_; q.tpeak = tp_words_;
+    PE_LAUNCH_KB("true_peak_kernel", 4.0 * samples, launch::true_peak(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, q));
+  }
   PE_LAUNCH_K("loudness_gain_kernel",
-              launch::loudness_gain(stream_, B, ld_seg_, ld_nseg_cap_, lens, len_mul, x_bs, ld_h_, peaks, ld_ctl_, ld_dev_, ld_cap_));
+              launch::loudness_gain(stream_, B, ld_seg_, ld_nseg_cap_, lens, len_mul, x_bs, ld_h_, peaks, tp ? tp_words_ : nullptr,
+                                    ld_ctl_, ld_dev_, ld_cap_));
   PE_LAUNCH_KB("pcm16_gain_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
                launch::pcm16_gain(dim3((unsigned)((max_n + 255) / 256), B), stream_, x, x_bs, ld_dev_, ld_cap_, lens, len_mul, pcm,
                                   x_bs, zc));

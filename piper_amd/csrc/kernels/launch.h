@@ -98,10 +98,12 @@ void chunk_pcm_rs(dim3 grid, hipStream_t stream, const float* y, long y_bs, cons
 void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs, const int* rows, int rcap, const int* st, int cap,
                        const int* gq);
 // target loudness (params.h: ld_*, LoudP): grid = (100 ms segments of the bucket, rows), then one wave per row; pcm16_gain =
-// pcm16 with the scale loudness_gain wrote to `gq`
+// pcm16 with the scale loudness_gain wrote to `gq`. True-peak ceiling (TpP): true_peak between the two, grid = (tiles of
+// TP_TILE native samples, rows), and its words as `tpeaks` (null: the sample-peak ceiling)
 void loudness_seg(dim3 grid, hipStream_t stream, const LoudP& p);
+void true_peak(dim3 grid, hipStream_t stream, const TpP& p);
 void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
-                   const unsigned* peaks, int* ctl, int* gd, int cap);
+                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap);
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
                 int len_mul, short* pcm, long p_bs, short* host);
 

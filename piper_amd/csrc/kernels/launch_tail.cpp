@@ -5,6 +5,7 @@
 #include "post.h"
 #include "resample.h"
 #include "loudness.h"
+#include "true_peak.h"
 
 namespace pe {
 namespace launch {
@@ -102,9 +103,13 @@ void loudness_seg(dim3 grid, hipStream_t stream, const LoudP& p) {
   PE_LAUNCH(loudness_seg_kernel, grid, dim3(LOUD_TPB), 0, stream, p);
 }
 
+void true_peak(dim3 grid, hipStream_t stream, const TpP& p) {
+  PE_LAUNCH(true_peak_kernel, grid, dim3(256), 0, stream, p);
+}
+
 void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
-                   const unsigned* peaks, int* ctl, int* gd, int cap) {
-  PE_LAUNCH(loudness_gain_kernel, dim3(B), dim3(64), 0, stream, seg, nseg_cap, lens, len_mul, x_cap, h, peaks, ctl, gd, cap);
+                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap) {
+  PE_LAUNCH(loudness_gain_kernel, dim3(B), dim3(64), 0, stream, seg, nseg_cap, lens, len_mul, x_cap, h, peaks, tpeaks, ctl, gd, cap);
 }
 
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,

@@ -37,6 +37,8 @@ __global__ __launch_bounds__(LOUD_TPB) void loudness_seg_kernel(LoudP p) {
   __shared__ double sv[2][LOUD_TPB][4];
   __shared__ double red[LOUD_TPB];
   const int b = blockIdx.y, j = blockIdx.x, t = threadIdx.x;
+  // (true-peak ceiling: the row's word is cleared here, stream-ordered before true_peak_kernel folds into it)
+  if (p.tpeak && j == 0 && t == 0) p.tpeak[b] = 0u;
   long nl = (long)p.lens[b] * p.len_mul;
   nl = nl < 0 ? 0 : (nl > p.x_cap ? p.x_cap : nl);
   const int n = (int)nl;
@@ -102,11 +104,15 @@ __global__ __launch_bounds__(LOUD_TPB) void loudness_seg_kernel(LoudP p) {
 //   L = -0.691 + 10 log10(mean z over blocks with l_j > -70 and l_j > G).
 //   n < 4 h (SHORT): one block over the whole row, mean of y^2 over n, kept when it passes the absolute gate.
 //   nothing kept, or n == 0 (UNMEASURABLE): scale = 32767, L = -inf.
-//   else scale = 32767 min(10^((T - L) / 20), C / p), LIMITED when the second term is the smaller; p = the row's peak word.
+//   else scale = 32767 min(10^((T - L) / 20), C / P), LIMITED when the second term is the smaller; P = p, the row's
+//   sample-peak word, or with a true-peak ceiling (tpeaks != null) max(p, t), t = the word of true_peak_kernel
+//   (true_peak.h): phase 0 of its interpolator has gain 0.92, so t alone can read below p.
 // T and C are read in place from the pinned control block `ctl`; {L, scale, p, flags} go to the device block `gd` for the
-// conversion and into the control block's report for pe_last_loudness. Every index is cut to its block.
+// conversion and into the control block's report for pe_last_loudness, t behind it for pe_last_true_peak. Every index is
+// cut to its block.
 __global__ __launch_bounds__(64) void loudness_gain_kernel(const double* seg, int nseg_cap, const int* lens, int len_mul,
-                                                           long x_cap, int h, const unsigned* peaks, int* ctl, int* gd, int cap) {
+                                                           long x_cap, int h, const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd,
+                                                           int cap) {
   PE_KTRACE(33);
   __shared__ double ps[64];
   __shared__ int pc[64];
@@ -159,14 +165,16 @@ __global__ __launch_bounds__(64) void loudness_gain_kernel(const double* seg, in
   const float T = __uint_as_float(reinterpret_cast<const unsigned*>(ctl)[0]);
   const float C = __uint_as_float(reinterpret_cast<const unsigned*>(ctl)[1]);
   const float p = __uint_as_float(peaks[b]);
+  const float tp = tpeaks ? __uint_as_float(tpeaks[b]) : 0.f;
+  const float P = fmaxf(p, tp);
   int flags = is_short ? LOUD_SHORT : 0;
   float scale = 32767.0f, Lf = -__builtin_inff();
-  if (ok && p > 0.f) {
-    const double g1 = exp(((double)T - L) * 0.11512925464970228), g2 = (double)C / (double)p;      // 10^(x / 20) = e^(x ln 10 / 20)
+  if (ok && P > 0.f) {
+    const double g1 = exp(((double)T - L) * 0.11512925464970228), g2 = (double)C / (double)P;      // 10^(x / 20) = e^(x ln 10 / 20)
     if (g2 < g1) flags |= LOUD_LIMITED;
     scale = (float)(32767.0 * (g2 < g1 ? g2 : g1));
     // (the rounding to f32 must not lift the row's peak over the ceiling)
-    if ((flags & LOUD_LIMITED) && (double)scale * (double)p > 32767.0 * (double)C) scale = __uint_as_float(__float_as_uint(scale) - 1u);
+    if ((flags & LOUD_LIMITED) && (double)scale * (double)P > 32767.0 * (double)C) scale = __uint_as_float(__float_as_uint(scale) - 1u);
     Lf = (float)L;
   } else {
     flags |= LOUD_UNMEASURABLE;
@@ -177,6 +185,7 @@ __global__ __launch_bounds__(64) void loudness_gain_kernel(const double* seg, in
   gf[ld_o_scale(cap) + b] = scale; rf[ld_o_scale(cap) + b] = scale;
   gf[ld_o_peak(cap) + b] = p; rf[ld_o_peak(cap) + b] = p;
   gd[ld_o_flags(cap) + b] = flags; ctl[ldc_o_report(cap) + ld_o_flags(cap) + b] = flags;
+  if (tpeaks) reinterpret_cast<float*>(ctl)[ldc_o_tpeak(cap) + b] = tp;
 }
 
 }  // namespace pe

@@ -311,7 +311,7 @@ struct RsP {
 // The setting's numbers are DATA, like the stream gain's: a pinned host control block for `cap` rows that
 // loudness_gain_kernel reads in place and into which it writes what pe_last_loudness reports; the conversion's operand
 // lives in a device block of the report's layout.
-//   control (pinned host)  T (target, LUFS), C (ceiling as a sample-peak ratio) as f32, then the report
+//   control (pinned host)  T (target, LUFS), C (ceiling as a peak ratio) as f32, then the report, then the true peaks
 //   report / device block  L[cap] (f32 LUFS, -inf: not measurable), scale[cap] (f32), peak[cap] (f32), flags[cap]
 // The filter block (device, f64): shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2}, then LOUD_LEVELS 4 x 4
 // matrices A^(R 2^k), k = 0 .. LOUD_LEVELS - 1, row-major: what R samples of silence make of the cascade's four states.
@@ -324,13 +324,34 @@ static constexpr int ld_o_peak(int cap) { return 2 * cap; }
 static constexpr int ld_o_flags(int cap) { return 3 * cap; }
 static constexpr int ld_words(int cap) { return 4 * cap; }
 static constexpr int ldc_o_report(int cap) { (void)cap; return 2; }
-static constexpr int ldc_words(int cap) { return 2 + 4 * cap; }
+static constexpr int ldc_words(int cap) { return 2 + 5 * cap; }      // (the report, then the true peaks: ldc_o_tpeak)
 struct LoudP {
   const float* x; long x_bs;                   // delivered rows x[b][0 .. n_b), n_b = lens[b] * len_mul cut to x_cap
   const int* lens; int len_mul; long x_cap;
   const double* coef;                          // filter block
   int h, W, R;                                 // samples of a 100 ms segment, of the warm-up in front of it, of one thread's run
   double* seg; int nseg_cap;                   // segment sums seg[b][nseg_cap]
+  unsigned* tpeak;                             // true-peak words [rows] to clear for true_peak_kernel, or null (sample-peak ceiling)
+};
+
+// ---- true-peak ceiling of the target loudness (true_peak.h: true_peak_kernel)
+// The kind of ceiling picks the launches (PEAK_TRUE: one more, between the segment sums and the gain) and is part of the
+// graph keys. The table is the resampler's for the pair fs -> Q fs, Q = ceil(192000 / fs): its half-width is TP_K native
+// samples at every fs in [8000, 48000], where Q <= TP_MAXQ. One word per row (max |interpolated sample| as a float's bit
+// pattern) in a device allocation of its own; loudness_gain_kernel copies it into the control block's report behind the
+// flags: tpeak[cap] at ldc_o_tpeak.
+enum { PEAK_SAMPLE = 0, PEAK_TRUE = 1 };
+static constexpr int TP_K = 18;                // ceil(16 / 0.92)
+static constexpr int TP_TAPS = 2 * TP_K;       // taps of a phase (a multiple of 4: the table needs no padding)
+static constexpr int TP_MAXQ = 24;             // Q at 8000 Hz
+static constexpr int TP_TILE = 1024;           // native samples per workgroup
+static constexpr int TP_SPAN = TP_TILE + TP_TAPS + 4;      // floats of LDS: the tile, its halo, alignment slack
+static constexpr int ldc_o_tpeak(int cap) { return 2 + 4 * cap; }
+struct TpP {
+  const float* x; long x_bs;                   // delivered rows x[b][0 .. n_b), n_b = lens[b] * len_mul cut to x_cap
+  const int* lens; int len_mul; long x_cap;
+  const float* coef; int Q;                    // [Q][TP_TAPS] polyphase table
+  unsigned* tpeak;                             // [rows], zero before the launch
 };
 
 // ---- fused MRF stage (mrf.h)

@@ -513,6 +513,52 @@ int pe_debug_loudness(pe_engine* e, const float* x, int32_t batch, int64_t strid
   });
 }
 
+int pe_set_loudness_ceiling(pe_engine* e, int32_t kind) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_loudness_ceiling(kind);
+  });
+}
+
+int pe_get_loudness_ceiling(pe_engine* e, int32_t* kind, int32_t* oversample, int32_t* half_width) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    const int fs = e->eng->output_rate();
+    if (kind) *kind = e->eng->loudness_ceiling_kind();
+    if (oversample) *oversample = fs >= 8000 && fs <= 48000 ? pe::Engine::true_peak_oversample(fs) : 0;
+    if (half_width) *half_width = pe::TP_K;
+  });
+}
+
+int pe_last_true_peak(pe_engine* e, float* true_peak, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->last_true_peak(true_peak, capacity);
+  });
+}
+
+int pe_true_peak_filter(int32_t fs, int32_t* oversample, int32_t* half_width, double* coef, int64_t capacity, int64_t* n) {
+  return guard([&] {
+    int Q, K;
+    std::vector<double> table;
+    pe::Engine::true_peak_filter(fs, Q, K, table);
+    if (oversample) *oversample = Q;
+    if (half_width) *half_width = K;
+    if (n) *n = (int64_t)table.size();
+    if (coef) {
+      if (capacity < (int64_t)table.size()) throw std::runtime_error("true-peak filter buffer too small");
+      for (size_t i = 0; i < table.size(); ++i) coef[i] = table[i];
+    }
+  });
+}
+
+int pe_debug_true_peak(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, float* t) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_true_peak(x, batch, stride, valid, fs, t);
+  });
+}
+
 int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
                       const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
   return guard([&] {

@@ -359,6 +359,11 @@ static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) 
   int32_t lon = 0;
   float lt = 0.f, lc = 0.f;
   check(pe_get_loudness(session.engine, &lon, &lt, &lc));
+  // SynthesisConfig::truePeak: the kind of ceiling, remembered by the engine while the loudness is off
+  int32_t kind = PE_PEAK_SAMPLE;
+  check(pe_get_loudness_ceiling(session.engine, &kind, nullptr, nullptr));
+  const int32_t want_kind = sc.truePeak ? PE_PEAK_TRUE : PE_PEAK_SAMPLE;
+  if (kind != want_kind) check(pe_set_loudness_ceiling(session.engine, want_kind));
   if (!sc.targetLufs) {
     if (lon) check(pe_set_loudness(session.engine, 0, 0.f, 0.f));
   } else if (!lon || lt != *sc.targetLufs || lc != sc.peakCeilingDb) {

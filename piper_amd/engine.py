@@ -406,15 +406,61 @@ class Engine:
 
     LOUD_SHORT, LOUD_UNMEASURABLE, LOUD_LIMITED = 1, 2, 4
 
-    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0):
+    PEAK_SAMPLE, PEAK_TRUE = 0, 1
+
+    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0, true_peak: bool = False):
         """Deliver every WHOLE utterance at ``target_lufs`` LUFS (ITU-R BS.1770-4 gated integrated loudness, mono,
-        measured on the device on the floats the call delivers) under a sample-peak ceiling of ``ceiling_db`` dBFS
-        (include/piper_hip.h: pe_set_loudness). ``None``: off, the default -- every utterance scaled by
-        ``32767 / max(0.01, peak)``. The floats never change; stream chunks keep their own rules."""
+        measured on the device on the floats the call delivers) under a ceiling of ``ceiling_db`` dB -- on the sample
+        peak, or with ``true_peak`` on the true peak of BS.1770-4 Annex 2 as well (dBTP), measured on the device
+        (include/piper_hip.h: pe_set_loudness, pe_set_loudness_ceiling). ``None``: off, the default -- every utterance
+        scaled by ``32767 / max(0.01, peak)``; the kind of ceiling is remembered. The floats never change; stream chunks
+        keep their own rules. A refused call changes nothing."""
+        kind = self.PEAK_TRUE if true_peak else self.PEAK_SAMPLE
         if target_lufs is None:
             self._check(self._lib.pe_set_loudness(self._h, 0, 0.0, 0.0))
-        else:
-            self._check(self._lib.pe_set_loudness(self._h, 1, float(target_lufs), float(ceiling_db)))
+            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
+            return
+        before = self.loudness_ceiling()[0]
+        # (the true-peak kind first: it is refused while the loudness is on at a rate it does not cover)
+        if true_peak:
+            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
+        if self._lib.pe_set_loudness(self._h, 1, float(target_lufs), float(ceiling_db)):
+            err = EngineError(self._lib.pe_last_error().decode(errors="replace"))
+            self._lib.pe_set_loudness_ceiling(self._h, before)
+            raise err
+        if not true_peak:
+            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
+
+    def loudness_ceiling(self):
+        """(kind, oversample, half_width) of the ceiling (pe_get_loudness_ceiling): ``PEAK_SAMPLE`` or ``PEAK_TRUE``, the
+        interpolation factor of the true-peak measure at the delivered rate (0 where it has none) and its half-width."""
+        k, q, w = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._lib.pe_get_loudness_ceiling(self._h, C.byref(k), C.byref(q), C.byref(w)))
+        return k.value, q.value, w.value
+
+    def last_true_peak(self):
+        """The true peak of every utterance of the last fetched whole-utterance call (pe_last_true_peak); empty when
+        that call did not run with the true-peak ceiling."""
+        n = C.c_int32()
+        self._check(self._lib.pe_last_true_peak(self._h, None, 0, C.byref(n)))
+        t = np.zeros(max(n.value, 1), np.float32)
+        self._check(self._lib.pe_last_true_peak(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.size, C.byref(n)))
+        return t[:n.value]
+
+    def debug_true_peak(self, rows, fs: int, pad=0.0):
+        """Test hook (pe_debug_true_peak): the true-peak kernel alone on ``rows``, a list of 1-D float arrays at rate
+        ``fs``; what lies behind a row's end in the staging matrix holds ``pad``. Returns one float per row."""
+        B = len(rows)
+        valid = np.asarray([len(r) for r in rows], np.int32)
+        stride = max(1, int(valid.max()))
+        x = np.full((B, stride), pad, np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        t = np.zeros(B, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_debug_true_peak(self._h, x.ctypes.data_as(fp), B, stride,
+                                                 valid.ctypes.data_as(C.POINTER(C.c_int32)), int(fs), t.ctypes.data_as(fp)))
+        return t
 
     def loudness(self):
         """(target_lufs or None while off, ceiling_db) as set by ``set_loudness``."""
@@ -711,3 +757,16 @@ def loudness_filter(fs: int, lib=None) -> np.ndarray:
     if lib.pe_loudness_filter(int(fs), out.ctypes.data_as(C.POINTER(C.c_double))):
         raise EngineError(lib.pe_last_error().decode(errors="replace"))
     return out
+
+
+def true_peak_filter(fs: int, lib=None):
+    """The interpolator of the true-peak measure at rate ``fs`` (pe_true_peak_filter; host only): (Q, K, float64 table
+    [Q][2 K]), row ph holding the taps of the outputs ``c Q + ph`` on ``x[c - K + 1 .. c + K]``."""
+    lib = lib if lib is not None else L.get_lib()
+    q, k, n = C.c_int32(), C.c_int32(), C.c_int64()
+    if lib.pe_true_peak_filter(int(fs), C.byref(q), C.byref(k), None, 0, C.byref(n)):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    out = np.zeros(n.value, np.float64)
+    if lib.pe_true_peak_filter(int(fs), C.byref(q), C.byref(k), out.ctypes.data_as(C.POINTER(C.c_double)), out.size, C.byref(n)):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    return q.value, k.value, out.reshape(q.value, 2 * k.value)

@@ -102,7 +102,9 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
                         help="deliver the audio at this rate, resampled on the GPU from --sample-rate (0: off)")
     parser.add_argument("--target-lufs", type=float, default=None,
                         help="deliver every utterance at this integrated loudness (ITU-R BS.1770-4, LUFS; default: peak-normalised)")
-    parser.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="sample-peak ceiling in dBFS with --target-lufs")
+    parser.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="peak ceiling in dB with --target-lufs (sample peak; with --true-peak: dBTP)")
+    parser.add_argument("--true-peak", action="store_true",
+                        help="hold the ceiling as a true peak (ITU-R BS.1770-4 Annex 2), measured on the GPU; with --target-lufs")
     parser.add_argument("--noise-scale", type=float, default=0.667)
     parser.add_argument("--noise-scale-w", type=float, default=0.8)
     parser.add_argument("--length-scale", type=float, default=1.0)
@@ -125,7 +127,7 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     if args.target_lufs is not None:
         if not args.output_rate:
             engine.set_output_rate(None, native=args.sample_rate)      # (an .onnx carries no rate of its own)
-        engine.set_loudness(args.target_lufs, args.peak_ceiling_db)
+        engine.set_loudness(args.target_lufs, args.peak_ceiling_db, true_peak=args.true_peak)
     scales = (args.noise_scale, args.length_scale, args.noise_scale_w)
     lines = list(stdin if stdin is not None else sys.stdin)
     utts = read_utterances(lines)
