@@ -63,8 +63,13 @@ tests/cpp/test_true_peak: tests/cpp/test_true_peak.cpp $(LIB) include/piper.hpp 
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_true_peak.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
 tests/cpp/test_true_peak_emu: tests/cpp/test_true_peak.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_true_peak.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
+# SynthesisConfig::limiter through the piper:: API (tests/test_limiter_cpp.py)
+tests/cpp/test_limiter: tests/cpp/test_limiter.cpp $(LIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_limiter.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
+tests/cpp/test_limiter_emu: tests/cpp/test_limiter.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_limiter.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
 
 clean:
 	rm -rf build $(LIB) $(EMULIB) tests/cpp/test_piper tests/cpp/test_piper_emu tests/cpp/test_loudness tests/cpp/test_loudness_emu \
-	       tests/cpp/test_true_peak tests/cpp/test_true_peak_emu
+	       tests/cpp/test_true_peak tests/cpp/test_true_peak_emu tests/cpp/test_limiter tests/cpp/test_limiter_emu
 .PHONY: all emu stamps clean

@@ -101,6 +101,12 @@ struct SynthesisConfig {
   std::optional<float> targetLufs;
   float peakCeilingDb = -1.0f;
   bool truePeak = false;
+  // Look-ahead limiter: where the ceiling and targetLufs conflict, a phrase keeps the gain of its target and only the
+  // neighbourhood of its peaks is turned down, by a zero-phase window of limiterMs (1 to 10 ms) -- instead of the whole
+  // phrase being lowered. Only the int16 is shaped. Either kind of ceiling (piper_hip.h: pe_set_loudness_limiter).
+  // (Beyond the reference.)
+  bool limiter = false;
+  float limiterMs = 5.0f;
   int sampleWidth = 2;  // 16-bit
   int channels = 1;     // mono
 

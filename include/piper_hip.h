@@ -358,6 +358,50 @@ int pe_true_peak_filter(int32_t fs, int32_t* oversample, int32_t* half_width, do
  * rate fs: t[batch]. Independent of the handle's setting and rate. */
 int pe_debug_true_peak(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, float* t);
 
+/* Look-ahead limiter of the target loudness. Off, the default: when the ceiling and the target conflict the whole utterance
+ * is lowered (PE_LOUD_LIMITED), so one plosive decides the level of a sentence. On: such an utterance keeps the gain of its
+ * target, g = 10^((target_lufs - L) / 20), and a zero-phase envelope turns down the neighbourhood of its peaks only
+ * (PE_LOUD_SHAPED, set next to PE_LOUD_LIMITED, which keeps its meaning: C / P < g). Every other utterance is delivered bit
+ * for bit as with the limiter off. On the device, one launch in the conversion's place:
+ *   W          max(1, floor(window_ms fs / 1000 + 0.5)) samples at the delivered rate fs: 8 at 8000 Hz with 1 ms, 480 at
+ *              48000 Hz with 10 ms.
+ *   r[i]       min(1, C / (g |x[i]|)), 1 where x[i] = 0 and outside [0, n)
+ *   m[j], d    m[j] = min r[j - W .. j + W], d = 1 - m
+ *   e[i]       min(r[i], 1 - sum_{k = -W .. W} h_k d[i + k]), h_k = H_k / sum H, H_k = (1 + cos(pi k / (W + 1))) / 2; e is
+ *              exactly 1 wherever no sample within 2 W passes the ceiling
+ *   pcm[i]     trunc(clamp((x[i] e[i]) * scale, +-floor(32767 C))), scale = 32767 g: |pcm| <= 32767 C holds exactly
+ * With PE_PEAK_TRUE the rule's P is max(p, t) as before, and in r stands a[i] = max(|x[i]|, v[i - 1], v[i]) for |x[i]|,
+ * v[c] = max over ph of |y[c Q + ph]| of the true-peak interpolation (v[-1] = 0); z = x e is kept in f32, its sample peak p_z
+ * and true peak t_z are measured by the same kernel that measures t, and scale = 32767 min(g, C / max(p_z, t_z)) with the
+ * one-ulp lowering of the ceiling's term: three launches more. The second term is a guarantee, not the mechanism; it is
+ * reported as trim = min(1, C / (g max(p_z, t_z))). The rate refusals of PE_PEAK_TRUE hold as without the limiter.
+ * The float `audio` a call returns stays x, unchanged: only the int16 is shaped. pe_last_loudness reports the scale that was
+ * used and L, the measured loudness of x; the delivered loudness is NOT measured again and there is no make-up gain, so it
+ * lies at or below target_lufs (by a few tenths of a dB on speech with 5 ms, the recommended window). window_ms in [1, 10],
+ * finite (on == 0: ignored); a value outside is refused with a message that names it, before anything changes, and so is a
+ * window of more than 480 samples at the delivered rate. The setting is remembered while the loudness is off. Only whole-utterance calls use it; streams,
+ * batch streams and the pool are untouched. On / off is part of the graph keys; a new window_ms or delivered rate drops the
+ * captured graphs. The read-back gives on / off, window_ms and W at the delivered rate (0 where the rate is unknown); any
+ * pointer may be NULL. */
+enum { PE_LOUD_SHAPED = 8 };
+int pe_set_loudness_limiter(pe_engine* e, int32_t on, float window_ms);
+int pe_get_loudness_limiter(pe_engine* e, int32_t* on, float* window_ms, int32_t* window_samples);
+/* The last fetched whole-utterance call on the handle, per utterance: max_reduction[i] = 1 - min e, shaped_samples[i] = the
+ * count of samples with e < 1 (both 0 for an utterance that is not shaped), trim[i] = min(1, C / (g max(p_z, t_z))) with
+ * PE_PEAK_TRUE and 1 with PE_PEAK_SAMPLE, which holds by construction. *n utterances (0: the call did not run with the limiter and the
+ * loudness on). Any array may be NULL; capacity < *n is an error. */
+int pe_last_limiter(pe_engine* e, float* max_reduction, int32_t* shaped_samples, float* trim, int64_t capacity, int32_t* n);
+/* Host only: *window_samples = W and the weights h_k in f64, before the rounding to f32: coef[k + W], k = -W .. W, *n =
+ * 2 W + 1 (coef may be NULL to ask for *n; capacity < *n is an error). */
+int pe_limiter_window(int32_t fs, float window_ms, int32_t* window_samples, double* coef, int64_t capacity, int64_t* n);
+/* Test hook: the limiter kernel alone on caller-supplied rows x[batch][stride] (host), row b holding valid[b] samples at rate
+ * fs with the gain g[b] (scale = 32767 g[b], one f32 product; shaped iff C / max |x| < g[b]). env_out[batch][stride] receives e
+ * (1 on rows that are not shaped) and pcm_out[batch][stride] the int16; what lies behind a row's end is left as it was.
+ * kind: PE_PEAK_SAMPLE, or PE_PEAK_TRUE (fs in [8000, 48000]; shaped iff C / max(p, t) < g[b]; the four launches of that path).
+ * Independent of the handle's setting and rate. */
+int pe_debug_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, const float* g,
+                     float ceiling_db, int32_t kind, float window_ms, float* env_out, int16_t* pcm_out);
+
 /* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
  * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them
  * counts as zero. out[b][0 .. count[b]) receives outputs n0[b] .. n0[b] + count[b] - 1 of that utterance (out_stride floats

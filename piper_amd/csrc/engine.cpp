@@ -658,7 +658,7 @@ void Engine::run() {
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
     // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key());
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -685,7 +685,7 @@ void Engine::run() {
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, loud_key());
     run_stage('B', key);
   }
 }
@@ -745,7 +745,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, ld_on_ ? (ld_kind_ == PEAK_TRUE ? "|l2" : "|l1") : "");
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, loud_key());
   run_stage('B', key);
   return false;
 }
@@ -779,6 +779,7 @@ void Engine::download(bool want_audio, bool want_pcm) {
     grow(n);
     if (want_audio) PE_HIP(hipMemcpyAsync(h_audio_, asrc(), n * sizeof(float), hipMemcpyDeviceToHost, stream_));
     if (want_pcm && !zc) PE_HIP(hipMemcpyAsync(h_pcm_, psrc(), n * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
+    lim_enqueue_report();
     if (finish_run()) {                        // synchronises; sample_off_ now holds the real length
       pcm_zc_live_ = zc;
       loud_collect();
@@ -800,6 +801,7 @@ void Engine::download(bool want_audio, bool want_pcm) {
       PE_HIP(hipMemcpyAsync(h_pcm_ + sample_off_[b], psrc() + (size_t)b * So_,
                             (size_t)(sample_off_[b + 1] - sample_off_[b]) * sizeof(int16_t), hipMemcpyDeviceToHost,
                             stream_));
+  lim_enqueue_report();
   PE_HIP(hipStreamSynchronize(stream_));
   pcm_zc_live_ = zc;
   loud_collect();
@@ -1405,6 +1407,9 @@ void Engine::set_output_rate(int native, int output) {
   const bool on = output != 0 && output != native;
   if (ld_on_) loud_check_rate(on ? output : native);    // (the target loudness is measured at the delivered rate)
   if (ld_on_ && ld_kind_ == PEAK_TRUE) tp_check_rate(on ? output : native);
+  if (ld_on_ && lim_on_ && limiter_window_samples(on ? output : native, (double)lim_ms_) > LIM_MAXW)
+    throw std::runtime_error("limiter window " + std::to_string(lim_ms_) + " ms is more than " + std::to_string(LIM_MAXW) +
+                             " samples at " + std::to_string(on ? output : native) + " Hz");
   const std::string pair = std::to_string(native) + " -> " + std::to_string(output) + " Hz";
   int L = 1, M = 1, K = 0, Tp = 0, tile = RS_TILE;
   std::vector<float> table;
@@ -1672,6 +1677,13 @@ void Engine::loud_free() {
   ld_coef_ = ld_seg_ = nullptr; ld_dev_ = ld_ctl_ = nullptr;
   ld_seg_rows_ = 0; ld_nseg_cap_ = 0; ld_cap_ = 0;
   tp_coef_ = nullptr; tp_words_ = nullptr; tp_fs_ = tp_Q_ = tp_cap_ = 0;
+  if (lim_h_) hipFree(lim_h_);
+  if (lim_rep_) hipFree(lim_rep_);
+  if (lim_host_) hipHostFree(lim_host_);
+  if (lim_v_) hipFree(lim_v_);
+  if (lim_z_) hipFree(lim_z_);
+  lim_v_ = lim_z_ = nullptr; lim_zv_floats_ = 0;
+  lim_h_ = nullptr; lim_rep_ = lim_host_ = nullptr; lim_fs_ = lim_W_ = lim_cap_ = 0; lim_h_ms_ = 0.f;
 }
 
 void Engine::tp_check_rate(int fs) {
@@ -1704,11 +1716,61 @@ void Engine::set_loudness_ceiling(int kind) {
   if (kind != PEAK_SAMPLE && kind != PEAK_TRUE)
     throw std::runtime_error("unknown loudness ceiling kind " + std::to_string(kind) + " (0: sample peak, 1: true peak)");
   if (kind == PEAK_TRUE && ld_on_) tp_check_rate(output_rate());
+  lim_check(kind, lim_on_, lim_ms_);
   if (kind == ld_kind_) return;
   PE_HIP(hipSetDevice(device_));
   finish_run();                                        // (a speculative run still in flight settles first)
   // the kind picks the launches and is part of the graph keys: nothing is dropped, streams are not touched
   ld_kind_ = kind;
+}
+
+void Engine::lim_check(int kind, bool on, float window_ms) {
+  if (!on) return;
+  if (!std::isfinite(window_ms) || window_ms < 1.f || window_ms > 10.f)
+    throw std::runtime_error("limiter window " + std::to_string(window_ms) + " ms outside [1, 10]");
+  (void)kind;
+}
+
+// h_k = H_k / sum H, H_k = (1 + cos(pi k / (W + 1))) / 2, k = -W .. W: a raised cosine that ends above zero, in f64
+void Engine::limiter_window(int fs, float window_ms, int& W, std::vector<double>& coef) {
+  lim_check(PEAK_SAMPLE, true, window_ms);
+  loud_check_rate(fs);
+  W = limiter_window_samples(fs, (double)window_ms);
+  if (W > LIM_MAXW) throw std::runtime_error("limiter window of " + std::to_string(W) + " samples at " + std::to_string(fs) +
+                                             " Hz, more than " + std::to_string(LIM_MAXW));
+  coef.assign((size_t)(2 * W + 1), 0.0);
+  const double pi = 3.14159265358979323846;
+  double sum = 0;
+  for (int k = -W; k <= W; ++k) sum += coef[(size_t)(k + W)] = 0.5 * (1.0 + std::cos(pi * (double)k / (double)(W + 1)));
+  for (double& c : coef) c /= sum;
+}
+
+void Engine::lim_upload_window(int fs) {
+  int W;
+  std::vector<double> exact;
+  limiter_window(fs, lim_ms_, W, exact);
+  float table[2 * LIM_MAXW + 1] = {};
+  for (size_t i = 0; i < exact.size(); ++i) table[i] = (float)exact[i];
+  if (!lim_h_) PE_HIP(hipMalloc((void**)&lim_h_, sizeof(table)));
+  PE_HIP(hipMemcpy(lim_h_, table, sizeof(table), hipMemcpyHostToDevice));
+  lim_fs_ = fs; lim_W_ = W; lim_h_ms_ = lim_ms_;
+}
+
+void Engine::set_loudness_limiter(bool on, float window_ms) {
+  EntryLock entry_lock;
+  lim_check(ld_kind_, on, window_ms);
+  if (on && ld_on_ && limiter_window_samples(output_rate(), (double)window_ms) > LIM_MAXW)
+    throw std::runtime_error("limiter window " + std::to_string(window_ms) + " ms is more than " + std::to_string(LIM_MAXW) +
+                             " samples at " + std::to_string(output_rate()) + " Hz");
+  if (on == lim_on_ && (!on || window_ms == lim_ms_)) return;
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles first)
+  PE_HIP(hipStreamSynchronize(stream_));
+  // on / off picks the launches and is part of the graph keys: nothing is dropped. A new window is a new kernel argument
+  // (and a new table behind the same pointer): the graphs go, as with a new rate.
+  if (on && lim_h_ && window_ms != lim_h_ms_) drop_graphs();
+  lim_on_ = on;
+  if (on) lim_ms_ = window_ms;
 }
 
 void Engine::set_loudness(bool on, float target_lufs, float ceiling_db) {
@@ -1720,6 +1782,9 @@ void Engine::set_loudness(bool on, float target_lufs, float ceiling_db) {
       throw std::runtime_error("peak ceiling " + std::to_string(ceiling_db) + " dB outside [-20, 0]");
     loud_check_rate(output_rate());
     if (ld_kind_ == PEAK_TRUE) tp_check_rate(output_rate());
+    if (lim_on_ && limiter_window_samples(output_rate(), (double)lim_ms_) > LIM_MAXW)
+      throw std::runtime_error("limiter window " + std::to_string(lim_ms_) + " ms is more than " + std::to_string(LIM_MAXW) +
+                               " samples at " + std::to_string(output_rate()) + " Hz");
   }
   PE_HIP(hipSetDevice(device_));
   finish_run();                                        // (a speculative run still in flight settles first)
@@ -1761,6 +1826,46 @@ void Engine::ensure_loudness() {
       tp_cap_ = want_cap;
     }
   }
+  if (lim_on_) {
+    // (as above: a first allocation is in no graph yet; a changed table or grown words are inside the limiter's graphs)
+    if (!lim_h_ || lim_fs_ != output_rate() || lim_h_ms_ != lim_ms_) {
+      PE_HIP(hipStreamSynchronize(stream_));
+      if (lim_h_) drop_graphs();
+      lim_upload_window(output_rate());
+    }
+    if (!lim_rep_ || lim_cap_ < want_cap) {
+      PE_HIP(hipStreamSynchronize(stream_));
+      if (lim_rep_) { drop_graphs(); PE_HIP(hipFree(lim_rep_)); lim_rep_ = nullptr; }
+      if (lim_host_) { PE_HIP(hipHostFree(lim_host_)); lim_host_ = nullptr; }
+      lim_cap_ = 0;
+      PE_HIP(hipMalloc((void**)&lim_rep_, (size_t)lim_words(want_cap) * sizeof(int)));
+      PE_HIP(hipHostMalloc((void**)&lim_host_, (size_t)lim_words(want_cap) * sizeof(int)));
+      memset(lim_host_, 0, (size_t)lim_words(want_cap) * sizeof(int));
+      if (pol_.debug_poison) poison(lim_rep_, (size_t)lim_words(want_cap) * sizeof(int));
+      else PE_HIP(hipMemset(lim_rep_, 0, (size_t)lim_words(want_cap) * sizeof(int)));
+      PE_HIP(hipDeviceSynchronize());
+      lim_cap_ = want_cap;
+    }
+    if (ld_kind_ == PEAK_TRUE) {
+      const size_t want = std::max<size_t>(capB_B_, 1) * (size_t)std::max<long>(std::max<long>(So_, Ss_), 4);
+      if (!lim_z_ || !lim_v_ || lim_zv_floats_ < want) {
+        PE_HIP(hipStreamSynchronize(stream_));
+        if (lim_z_ || lim_v_) drop_graphs();
+        if (lim_z_) { PE_HIP(hipFree(lim_z_)); lim_z_ = nullptr; }
+        if (lim_v_) { PE_HIP(hipFree(lim_v_)); lim_v_ = nullptr; }
+        lim_zv_floats_ = 0;
+        if (hipMalloc((void**)&lim_z_, want * sizeof(float)) != hipSuccess || hipMalloc((void**)&lim_v_, want * sizeof(float)) != hipSuccess) {
+          (void)hipGetLastError();
+          if (lim_z_) { hipFree(lim_z_); lim_z_ = nullptr; }
+          lim_v_ = nullptr;
+          throw std::runtime_error("out of device memory: " + std::to_string((2 * want * sizeof(float)) >> 20) + " MiB of limiter rows");
+        }
+        if (pol_.debug_poison) { poison(lim_z_, want * sizeof(float)); poison(lim_v_, want * sizeof(float)); }
+        PE_HIP(hipDeviceSynchronize());
+        lim_zv_floats_ = want;
+      }
+    }
+  }
   if (ld_seg_ && ld_seg_rows_ >= capB_B_ && ld_nseg_cap_ >= nseg && ld_ctl_ && ld_dev_ && ld_cap_ >= want_cap) return;
   PE_HIP(hipStreamSynchronize(stream_));
   drop_graphs();
@@ -1791,10 +1896,24 @@ void Engine::ensure_loudness() {
   }
 }
 
+void Engine::lim_enqueue_report() {
+  if (!run_lim_ || !lim_rep_ || !lim_host_ || B_ > lim_cap_) return;
+  PE_HIP(hipMemcpyAsync(lim_host_, lim_rep_, (size_t)lim_words(lim_cap_) * sizeof(int), hipMemcpyDeviceToHost, stream_));
+}
+
 void Engine::loud_collect() {
   ll_tn_ = 0;
+  ll_ln_ = 0;
   if (!ld_on_ || !ld_ctl_ || B_ > ld_cap_) { ll_n_ = 0; return; }
   const int n = B_, cap = ld_cap_;
+  if (run_lim_ && lim_host_ && n <= lim_cap_) {
+    const float* mr = reinterpret_cast<const float*>(lim_host_) + lim_o_maxred(lim_cap_);
+    ll_maxred_.assign(mr, mr + n);
+    ll_shaped_.assign(lim_host_ + lim_o_count(lim_cap_), lim_host_ + lim_o_count(lim_cap_) + n);
+    const float* tr = reinterpret_cast<const float*>(lim_host_) + lim_o_trim(lim_cap_);
+    ll_trim_.assign(tr, tr + n);
+    ll_ln_ = n;
+  }
   if (ld_kind_ == PEAK_TRUE) {
     const float* tf = reinterpret_cast<const float*>(ld_ctl_) + ldc_o_tpeak(cap);
     ll_tpeak_.assign(tf, tf + n);
@@ -1819,6 +1938,156 @@ int Engine::last_loudness(float* lufs, float* scale, float* peak, int32_t* flags
     if (flags) flags[b] = ll_flags_[b];
   }
   return ll_n_;
+}
+
+int Engine::last_limiter(float* max_reduction, int32_t* shaped_samples, float* trim, int64_t capacity) {
+  EntryLock entry_lock;
+  if (ll_n_ < 0) throw std::runtime_error("no whole-utterance call fetched on this handle yet");
+  if ((max_reduction || shaped_samples || trim) && capacity < ll_ln_) throw std::runtime_error("limiter report buffer too small");
+  for (int b = 0; b < ll_ln_; ++b) {
+    if (max_reduction) max_reduction[b] = ll_maxred_[b];
+    if (shaped_samples) shaped_samples[b] = ll_shaped_[b];
+    if (trim) trim[b] = ll_trim_[b];
+  }
+  return ll_ln_;
+}
+
+void Engine::debug_limiter(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, const float* g, float ceiling_db,
+                           int kind, float window_ms, float* env, int16_t* pcm) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!x || !valid || !g || !env || !pcm) throw std::runtime_error("null argument");
+  if (stride < 0 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [0, 2^28]");
+  if (!std::isfinite(ceiling_db) || ceiling_db < -20.f || ceiling_db > 0.f)
+    throw std::runtime_error("peak ceiling " + std::to_string(ceiling_db) + " dB outside [-20, 0]");
+  if (kind != PEAK_SAMPLE && kind != PEAK_TRUE)
+    throw std::runtime_error("unknown loudness ceiling kind " + std::to_string(kind) + " (0: sample peak, 1: true peak)");
+  lim_check(kind, true, window_ms);
+  int W, maxn = 0;
+  std::vector<double> exact;
+  limiter_window(fs, window_ms, W, exact);
+  float table[2 * LIM_MAXW + 1] = {};
+  for (size_t i = 0; i < exact.size(); ++i) table[i] = (float)exact[i];
+  const int cap = (batch + 1) & ~1;
+  const float C = (float)std::pow(10.0, (double)ceiling_db / 20.0);
+  std::vector<int> gq((size_t)ld_words(cap), 0);
+  std::vector<float> peak((size_t)batch, 0.f);
+  for (int b = 0; b < batch; ++b) {
+    if (valid[b] < 0 || valid[b] > stride) throw std::runtime_error("row " + std::to_string(b) + ": valid length outside [0, stride]");
+    if (!std::isfinite(g[b]) || !(g[b] > 0.f)) throw std::runtime_error("row " + std::to_string(b) + ": gain " + std::to_string(g[b]) + " is not positive and finite");
+    maxn = std::max(maxn, valid[b]);
+    for (int i = 0; i < valid[b]; ++i) peak[b] = std::max(peak[b], std::fabs(x[(size_t)b * stride + i]));
+  }
+  // (the rule of loudness_gain_kernel: the ceiling's term is the smaller; P = max(p, t) with the true-peak ceiling)
+  auto fill_gq = [&](const float* tpk) {
+    for (int b = 0; b < batch; ++b) {
+      const float scale = 32767.0f * g[b], P = tpk ? std::max(peak[b], tpk[b]) : peak[b];
+      memcpy(&gq[(size_t)ld_o_scale(cap) + b], &scale, sizeof(float));
+      memcpy(&gq[(size_t)ld_o_peak(cap) + b], &peak[b], sizeof(float));
+      gq[(size_t)ld_o_flags(cap) + b] = (P > 0.f && (double)C / (double)P < (double)g[b]) ? (LOUD_LIMITED | LOUD_SHAPED) : 0;
+    }
+  };
+  const bool tp = kind == PEAK_TRUE;
+  int Q = 0, Kh = 0;
+  float tptable[TP_MAXQ * TP_TAPS] = {};
+  if (tp) {
+    std::vector<double> tex;
+    true_peak_filter(fs, Q, Kh, tex);
+    for (size_t i = 0; i < tex.size(); ++i) tptable[i] = (float)tex[i];
+  } else {
+    fill_gq(nullptr);
+  }
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const long xs = (long)((std::max<int64_t>(stride, 1) + 3) & ~(int64_t)3);
+  float *dx = nullptr, *dh = nullptr, *denv = nullptr, *dv = nullptr, *dz = nullptr, *dtab = nullptr;
+  int *dval = nullptr, *dgq = nullptr, *dctl = nullptr, *drep = nullptr;
+  unsigned* dtp = nullptr;
+  int16_t* dpcm = nullptr;
+  auto release = [&]() {
+    if (dv) hipFree(dv);
+    if (dz) hipFree(dz);
+    if (dtab) hipFree(dtab);
+    if (dtp) hipFree(dtp);
+    if (dx) hipFree(dx);
+    if (dh) hipFree(dh);
+    if (denv) hipFree(denv);
+    if (dval) hipFree(dval);
+    if (dgq) hipFree(dgq);
+    if (dctl) hipFree(dctl);
+    if (drep) hipFree(drep);
+    if (dpcm) hipFree(dpcm);
+  };
+  try {
+    const float ctl[2] = {0.f, C};
+    PE_HIP(hipMalloc((void**)&dx, (size_t)batch * xs * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&denv, (size_t)batch * xs * sizeof(float)));
+    PE_HIP(hipMalloc((void**)&dpcm, (size_t)batch * xs * sizeof(int16_t)));
+    PE_HIP(hipMalloc((void**)&dh, sizeof(table)));
+    PE_HIP(hipMalloc((void**)&dval, (size_t)batch * sizeof(int)));
+    PE_HIP(hipMalloc((void**)&dgq, gq.size() * sizeof(int)));
+    PE_HIP(hipMalloc((void**)&dctl, (size_t)ldc_words(cap) * sizeof(int)));      // (pcm16_trim_kernel writes the report's scale)
+    PE_HIP(hipMalloc((void**)&drep, (size_t)lim_words(cap) * sizeof(int)));
+    for (int b = 0; b < batch; ++b)
+      if (stride > 0) {
+        PE_HIP(hipMemcpyAsync(dx + (size_t)b * xs, x + (size_t)b * stride, (size_t)stride * sizeof(float), hipMemcpyHostToDevice, stream_));
+        // (what lies behind a row's end comes back as the caller left it)
+        PE_HIP(hipMemcpyAsync(denv + (size_t)b * xs, env + (size_t)b * stride, (size_t)stride * sizeof(float), hipMemcpyHostToDevice, stream_));
+        PE_HIP(hipMemcpyAsync(dpcm + (size_t)b * xs, pcm + (size_t)b * stride, (size_t)stride * sizeof(int16_t), hipMemcpyHostToDevice, stream_));
+      }
+    PE_HIP(hipMemcpyAsync(dh, table, sizeof(table), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dval, valid, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemsetAsync(drep, 0, (size_t)lim_words(cap) * sizeof(int), stream_));
+    TpP tq{};
+    if (tp) {
+      // the first true-peak pass: t for the rule, v for the envelope
+      PE_HIP(hipMalloc((void**)&dv, (size_t)batch * xs * sizeof(float)));
+      PE_HIP(hipMalloc((void**)&dz, (size_t)batch * xs * sizeof(float)));
+      PE_HIP(hipMalloc((void**)&dtab, sizeof(tptable)));
+      PE_HIP(hipMalloc((void**)&dtp, (size_t)batch * sizeof(unsigned)));
+      PE_HIP(hipMemcpyAsync(dtab, tptable, sizeof(tptable), hipMemcpyHostToDevice, stream_));
+      PE_HIP(hipMemsetAsync(dtp, 0, (size_t)batch * sizeof(unsigned), stream_));
+      PE_HIP(hipMemsetAsync(dv, 0xFF, (size_t)batch * xs * sizeof(float), stream_));
+      PE_HIP(hipMemsetAsync(dz, 0xFF, (size_t)batch * xs * sizeof(float), stream_));
+      PE_HIP(hipStreamSynchronize(stream_));
+      tq.x = dx; tq.x_bs = xs; tq.lens = dval; tq.len_mul = 1; tq.x_cap = (long)stride;
+      tq.coef = dtab; tq.Q = Q; tq.tpeak = dtp; tq.v = dv;
+      launch::true_peak_v(dim3((unsigned)std::max(1, (maxn + TP_TILE - 1) / TP_TILE), batch), stream_, tq);
+      std::vector<float> tpk((size_t)batch, 0.f);
+      PE_HIP(hipMemcpyAsync(tpk.data(), dtp, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, stream_));
+      PE_HIP(hipStreamSynchronize(stream_));
+      fill_gq(tpk.data());
+    }
+    PE_HIP(hipMemcpyAsync(dgq, gq.data(), gq.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));             // (the staging arrays are pageable)
+    LimP p{};
+    p.x = dx; p.x_bs = xs; p.lens = dval; p.len_mul = 1; p.x_cap = (long)stride;
+    p.gq = dgq; p.gcap = cap; p.ctl = dctl; p.h = dh; p.W = W;
+    p.pcm = dpcm; p.p_bs = xs; p.host = nullptr; p.rep = drep; p.rcap = cap; p.env = denv; p.e_bs = xs;
+    if (tp) {
+      p.v = dv; p.z = dz;
+      launch::limiter_true(dim3((unsigned)std::max(1, (maxn + LIM_TILE - 1) / LIM_TILE), batch), stream_, p);
+      tq.x = dz; tq.v = nullptr; tq.tpeak = reinterpret_cast<unsigned*>(drep) + lim_o_tz(cap);
+      launch::true_peak(dim3((unsigned)std::max(1, (maxn + TP_TILE - 1) / TP_TILE), batch), stream_, tq);
+      TrimP r{};
+      r.z = dz; r.z_bs = xs; r.lens = dval; r.len_mul = 1; r.gq = dgq; r.gcap = cap; r.ctl = dctl;
+      r.rep = drep; r.rcap = cap; r.pcm = dpcm; r.p_bs = xs; r.host = nullptr;
+      launch::pcm16_trim(dim3((unsigned)std::max(1, (maxn + 255) / 256), batch), stream_, r);
+    } else
+    launch::limiter(dim3((unsigned)std::max(1, (maxn + LIM_TILE - 1) / LIM_TILE), batch), stream_, p);
+    for (int b = 0; b < batch; ++b)
+      if (stride > 0) {
+        PE_HIP(hipMemcpyAsync(env + (size_t)b * stride, denv + (size_t)b * xs, (size_t)stride * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        PE_HIP(hipMemcpyAsync(pcm + (size_t)b * stride, dpcm + (size_t)b * xs, (size_t)stride * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
+      }
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
 }
 
 int Engine::last_true_peak(float* t, int64_t capacity) {
@@ -1946,7 +2215,7 @@ void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int
     p.x = dx; p.x_bs = xs; p.lens = dval; p.len_mul = 1; p.x_cap = (long)stride;
     p.coef = dcoef; p.h = h; p.W = W; p.R = R; p.seg = dseg; p.nseg_cap = nseg_cap;
     launch::loudness_seg(dim3((unsigned)std::max(1, (maxn + h - 1) / h), batch), stream_, p);
-    launch::loudness_gain(stream_, batch, dseg, nseg_cap, dval, 1, (long)stride, h, dpk, nullptr, ctl, gd, cap);
+    launch::loudness_gain(stream_, batch, dseg, nseg_cap, dval, 1, (long)stride, h, dpk, nullptr, ctl, gd, cap, 0);
     PE_HIP(hipStreamSynchronize(stream_));
     const float* rf = reinterpret_cast<const float*>(ctl + ldc_o_report(cap));
     for (int b = 0; b < batch; ++b) {

@@ -165,6 +165,31 @@ class Engine {
   static void true_peak_filter(int fs, int& Q, int& K, std::vector<double>& coef);
   // test hook: true_peak_kernel alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs
   void debug_true_peak(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float* t);
+  // Look-ahead limiter of the target loudness (kernels/limiter.h). Off, the default: a row whose peak would
+  // pass the ceiling at the gain of its target is lowered as a whole (LIMITED). On: such a row keeps that gain and a
+  // zero-phase envelope of window_ms (in [1, 10], W = round(window_ms fs / 1000) samples a side) turns down the
+  // neighbourhood of its peaks only (SHAPED); every other row is delivered bit for bit as without it. The floats a call
+  // returns are never shaped, only the int16. Whole-utterance calls only. The setting is remembered while the loudness is
+  // off. With PEAK_TRUE the envelope is formed from max(|x[i]|, v[i - 1], v[i]), v the per-position maxima of the
+  // true-peak interpolation, the shaped floats z = x e get a true-peak pass of their own and a last conversion kernel trims
+  // the scale to C / max(p_z, t_z) where that is the smaller term (three launches more; the existing rate refusals of
+  // PEAK_TRUE hold). Throws, and changes nothing, for a window outside [1, 10] ms or not finite. On / off is part of the
+  // graph keys; W is a kernel argument, so a new window drops the graphs.
+  void set_loudness_limiter(bool on, float window_ms);
+  bool loudness_limiter_on() const { return lim_on_; }
+  float loudness_limiter_ms() const { return lim_ms_; }
+  int loudness_limiter_window() const { return output_rate() > 0 ? limiter_window_samples(output_rate(), lim_ms_) : 0; }
+  // per utterance of the last fetched call: 1 - min e, the count of samples with e < 1, the final trim (1: the sample-peak
+  // ceiling needs none: 1); returns the utterances (0: that call did not run with the limiter)
+  int last_limiter(float* max_reduction, int32_t* shaped_samples, float* trim, int64_t capacity);
+  // host only: W and the 2 W + 1 weights in f64, before the rounding to f32; throws outside [1, 10] ms or fs outside the
+  // loudness's rates
+  static void limiter_window(int fs, float window_ms, int& W, std::vector<double>& coef);
+  // test hook: limiter_kernel alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs with the gain
+  // g[b] (scale = 32767 g[b] in f32; the row is shaped iff C / max |x| < g[b]); env[batch][stride] receives e and
+  // pcm[batch][stride] the int16 (entries behind a row's end are left alone)
+  void debug_limiter(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, const float* g, float ceiling_db,
+                     int kind, float window_ms, float* env, int16_t* pcm);
   // test hook: the two loudness kernels alone on host rows x[batch][stride], row b holding valid[b] samples at rate fs
   void debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
                       float* lufs, float* scale, int32_t* flags);
@@ -670,6 +695,32 @@ class Engine {
   int ll_tn_ = 0;
   static void tp_check_rate(int fs);            // throws the refusal
   void tp_upload_table(int fs);
+  // look-ahead limiter: the weights [2 lim_W_ + 1] for the window at the delivered rate lim_fs_, the report words on the
+  // device and their pinned host copy (params.h: lim_*), allocations of their own (ensure_loudness; kernel arguments inside
+  // the limiter's graphs). The report travels with the call's samples: download enqueues the copy in front of its wait.
+  bool lim_on_ = false;
+  float lim_ms_ = 5.f;
+  float* lim_h_ = nullptr; int lim_fs_ = 0, lim_W_ = 0; float lim_h_ms_ = 0.f;
+  int* lim_rep_ = nullptr; int* lim_host_ = nullptr; int lim_cap_ = 0;
+  // true-peak ceiling with the limiter: the per-position maxima v and the shaped floats z, [rows][lim_zv_bs_] each
+  float* lim_v_ = nullptr; float* lim_z_ = nullptr; size_t lim_zv_floats_ = 0;
+  // whether the run that is fetched next went through the limiter: noted where a run's graph key is formed and where the
+  // stage is issued, so that a setting made between run and fetch does not relabel the report
+  mutable bool run_lim_ = false;
+  std::vector<float> ll_maxred_, ll_trim_;
+  std::vector<int32_t> ll_shaped_;
+  int ll_ln_ = 0;
+  bool lim_active() const { return ld_on_ && lim_on_; }
+  // what the loudness setting adds to the 'B' and 'C' graph keys: off, sample peak, true peak, each with the limiter
+  const char* loud_key() const {
+    run_lim_ = ld_on_ && lim_on_;
+    if (!ld_on_) return "";
+    if (lim_on_) return ld_kind_ == PEAK_TRUE ? "|l4" : "|l3";
+    return ld_kind_ == PEAK_TRUE ? "|l2" : "|l1";
+  }
+  static void lim_check(int kind, bool on, float window_ms);      // throws the refusal
+  void lim_upload_window(int fs);
+  void lim_enqueue_report();                    // device report words -> lim_host_, on stream_
   static void loud_check_rate(int fs);          // throws the refusal
   void loud_upload_filter(int fs);              // h / W / R and the filter block for rate fs
   void loud_write_ctl();

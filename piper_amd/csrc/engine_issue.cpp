@@ -463,6 +463,13 @@ void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, i
   if (tp && (!tp_coef_ || !tp_words_ || B > tp_cap_ || tp_fs_ != output_rate()))
     throw std::runtime_error("true-peak buffers are not sized for this call");
   p.tpeak = tp ? tp_words_ : nullptr;
+  const bool lim = lim_on_;
+  run_lim_ = lim;
+  if (lim && tp && (!lim_z_ || !lim_v_ || (size_t)B * (size_t)x_bs > lim_zv_floats_))
+    throw std::runtime_error("limiter buffers are not sized for this call");
+  if (lim && (!lim_h_ || !lim_rep_ || B > lim_cap_ || lim_fs_ != output_rate() || lim_h_ms_ != lim_ms_))
+    throw std::runtime_error("limiter buffers are not sized for this call");
+  p.limrep = lim ? lim_rep_ : nullptr; p.limcap = lim ? lim_cap_ : 0;
   const int nseg = (int)std::min<long>((max_n + ld_h_ - 1) / ld_h_, ld_nseg_cap_);
   // algorithmic bytes: every delivered sample in once (the warm-up is read again out of the caches)
   PE_LAUNCH_KB("loudness_seg_kernel", 4.0 * samples, launch::loudness_seg(dim3((unsigned)nseg, B), stream_, p));
@@ -471,11 +478,41 @@ void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, i
     TpP q{};
     q.x = x; q.x_bs = x_bs; q.lens = lens; q.len_mul = len_mul; q.x_cap = x_bs;
     q.coef = tp_coef_; q.Q = tp_Q_; q.tpeak = tp_words_;
+    if (lim) {      // (the limiter's envelope wants the per-position maxima as well)
+      q.v = lim_v_;
+      PE_LAUNCH_KB("true_peak_v_kernel", 8.0 * samples, launch::true_peak_v(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, q));
+    } else
     PE_LAUNCH_KB("true_peak_kernel", 4.0 * samples, launch::true_peak(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, q));
   }
   PE_LAUNCH_K("loudness_gain_kernel",
               launch::loudness_gain(stream_, B, ld_seg_, ld_nseg_cap_, lens, len_mul, x_bs, ld_h_, peaks, tp ? tp_words_ : nullptr,
-                                    ld_ctl_, ld_dev_, ld_cap_));
+                                    ld_ctl_, ld_dev_, ld_cap_, lim ? 1 : 0));
+  if (lim) {
+    // look-ahead limiter: the conversion, with the rows loudness_gain_kernel marked SHAPED turned down around their peaks
+    LimP q{};
+    q.x = x; q.x_bs = x_bs; q.lens = lens; q.len_mul = len_mul; q.x_cap = x_bs;
+    q.gq = ld_dev_; q.gcap = ld_cap_; q.ctl = ld_ctl_; q.h = lim_h_; q.W = lim_W_;
+    q.pcm = pcm; q.p_bs = x_bs; q.host = zc; q.rep = lim_rep_; q.rcap = lim_cap_;
+    if (tp) {
+      // true-peak ceiling: z = x e and max |z|, the true peak of z into its word, then the conversion with the trimmed scale
+      q.v = lim_v_; q.z = lim_z_;
+      PE_LAUNCH_KB("limiter_true_kernel", 12.0 * samples,
+                   launch::limiter_true(dim3((unsigned)((max_n + LIM_TILE - 1) / LIM_TILE), B), stream_, q));
+      TpP t{};
+      t.x = lim_z_; t.x_bs = x_bs; t.lens = lens; t.len_mul = len_mul; t.x_cap = x_bs;
+      t.coef = tp_coef_; t.Q = tp_Q_; t.tpeak = reinterpret_cast<unsigned*>(lim_rep_) + lim_o_tz(lim_cap_);
+      PE_LAUNCH_KB("true_peak_kernel", 4.0 * samples, launch::true_peak(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, t));
+      TrimP r{};
+      r.z = lim_z_; r.z_bs = x_bs; r.lens = lens; r.len_mul = len_mul; r.gq = ld_dev_; r.gcap = ld_cap_; r.ctl = ld_ctl_;
+      r.rep = lim_rep_; r.rcap = lim_cap_; r.pcm = pcm; r.p_bs = x_bs; r.host = zc;
+      PE_LAUNCH_KB("pcm16_trim_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
+                   launch::pcm16_trim(dim3((unsigned)((max_n + 255) / 256), B), stream_, r));
+      return;
+    }
+    PE_LAUNCH_KB("limiter_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
+                 launch::limiter(dim3((unsigned)((max_n + LIM_TILE - 1) / LIM_TILE), B), stream_, q));
+    return;
+  }
   PE_LAUNCH_KB("pcm16_gain_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
                launch::pcm16_gain(dim3((unsigned)((max_n + 255) / 256), B), stream_, x, x_bs, ld_dev_, ld_cap_, lens, len_mul, pcm,
                                   x_bs, zc));

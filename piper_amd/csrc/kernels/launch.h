@@ -103,7 +103,15 @@ void chunk_pcm_rs_gain(dim3 grid, hipStream_t stream, const float* y, long y_bs,
 void loudness_seg(dim3 grid, hipStream_t stream, const LoudP& p);
 void true_peak(dim3 grid, hipStream_t stream, const TpP& p);
 void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
-                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap);
+                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap, int limiter);
+// look-ahead limiter (LimP): in pcm16_gain's place, grid = (tiles of LIM_TILE samples, rows); loudness_gain's `limiter` != 0
+// marks the rows it shapes
+void limiter(dim3 grid, hipStream_t stream, const LimP& p);
+// the limiter under the true-peak ceiling: true_peak_v = true_peak that also stores the per-position maxima (p.v),
+// limiter_true writes z and max |z| instead of the int16, true_peak runs on z, pcm16_trim converts (grid as pcm16_gain)
+void true_peak_v(dim3 grid, hipStream_t stream, const TpP& p);
+void limiter_true(dim3 grid, hipStream_t stream, const LimP& p);
+void pcm16_trim(dim3 grid, hipStream_t stream, const TrimP& p);
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
                 int len_mul, short* pcm, long p_bs, short* host);
 

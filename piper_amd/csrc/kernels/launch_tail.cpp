@@ -6,6 +6,7 @@
 #include "resample.h"
 #include "loudness.h"
 #include "true_peak.h"
+#include "limiter.h"
 
 namespace pe {
 namespace launch {
@@ -108,8 +109,24 @@ void true_peak(dim3 grid, hipStream_t stream, const TpP& p) {
 }
 
 void loudness_gain(hipStream_t stream, int B, const double* seg, int nseg_cap, const int* lens, int len_mul, long x_cap, int h,
-                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap) {
-  PE_LAUNCH(loudness_gain_kernel, dim3(B), dim3(64), 0, stream, seg, nseg_cap, lens, len_mul, x_cap, h, peaks, tpeaks, ctl, gd, cap);
+                   const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd, int cap, int limiter) {
+  PE_LAUNCH(loudness_gain_kernel, dim3(B), dim3(64), 0, stream, seg, nseg_cap, lens, len_mul, x_cap, h, peaks, tpeaks, ctl, gd, cap, limiter);
+}
+
+void limiter(dim3 grid, hipStream_t stream, const LimP& p) {
+  PE_LAUNCH(limiter_kernel, grid, dim3(256), 0, stream, p);
+}
+
+void true_peak_v(dim3 grid, hipStream_t stream, const TpP& p) {
+  PE_LAUNCH(true_peak_v_kernel, grid, dim3(256), 0, stream, p);
+}
+
+void limiter_true(dim3 grid, hipStream_t stream, const LimP& p) {
+  PE_LAUNCH(limiter_true_kernel, grid, dim3(256), 0, stream, p);
+}
+
+void pcm16_trim(dim3 grid, hipStream_t stream, const TrimP& p) {
+  PE_LAUNCH(pcm16_trim_kernel, grid, dim3(256), 0, stream, p);
 }
 
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,

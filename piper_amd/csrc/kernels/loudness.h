@@ -39,6 +39,12 @@ __global__ __launch_bounds__(LOUD_TPB) void loudness_seg_kernel(LoudP p) {
   const int b = blockIdx.y, j = blockIdx.x, t = threadIdx.x;
   // (true-peak ceiling: the row's word is cleared here, stream-ordered before true_peak_kernel folds into it)
   if (p.tpeak && j == 0 && t == 0) p.tpeak[b] = 0u;
+  // (limiter: so are the row's report words, before limiter_kernel folds into them)
+  if (p.limrep && j == 0 && t == 0 && b < p.limcap) {
+    p.limrep[lim_o_maxred(p.limcap) + b] = 0; p.limrep[lim_o_count(p.limcap) + b] = 0;
+    p.limrep[lim_o_pz(p.limcap) + b] = 0; p.limrep[lim_o_tz(p.limcap) + b] = 0;
+    reinterpret_cast<float*>(p.limrep)[lim_o_trim(p.limcap) + b] = 1.0f;
+  }
   long nl = (long)p.lens[b] * p.len_mul;
   nl = nl < 0 ? 0 : (nl > p.x_cap ? p.x_cap : nl);
   const int n = (int)nl;
@@ -109,10 +115,11 @@ __global__ __launch_bounds__(LOUD_TPB) void loudness_seg_kernel(LoudP p) {
 //   (true_peak.h): phase 0 of its interpolator has gain 0.92, so t alone can read below p.
 // T and C are read in place from the pinned control block `ctl`; {L, scale, p, flags} go to the device block `gd` for the
 // conversion and into the control block's report for pe_last_loudness, t behind it for pe_last_true_peak. Every index is
-// cut to its block.
+// cut to its block. limiter != 0 (the look-ahead limiter, limiter.h): a LIMITED row is SHAPED as well and its scale is the
+// first term, 32767 10^((T - L) / 20), whatever the peak is.
 __global__ __launch_bounds__(64) void loudness_gain_kernel(const double* seg, int nseg_cap, const int* lens, int len_mul,
                                                            long x_cap, int h, const unsigned* peaks, const unsigned* tpeaks, int* ctl, int* gd,
-                                                           int cap) {
+                                                           int cap, int limiter) {
   PE_KTRACE(33);
   __shared__ double ps[64];
   __shared__ int pc[64];
@@ -175,6 +182,8 @@ __global__ __launch_bounds__(64) void loudness_gain_kernel(const double* seg, in
     scale = (float)(32767.0 * (g2 < g1 ? g2 : g1));
     // (the rounding to f32 must not lift the row's peak over the ceiling)
     if ((flags & LOUD_LIMITED) && (double)scale * (double)P > 32767.0 * (double)C) scale = __uint_as_float(__float_as_uint(scale) - 1u);
+    // (look-ahead limiter, limiter.h: the row keeps the gain of its target and limiter_kernel shapes its peaks under C)
+    if (limiter && (flags & LOUD_LIMITED)) { flags |= LOUD_SHAPED; scale = (float)(32767.0 * g1); }
     Lf = (float)L;
   } else {
     flags |= LOUD_UNMEASURABLE;

@@ -315,7 +315,7 @@ struct RsP {
 //   report / device block  L[cap] (f32 LUFS, -inf: not measurable), scale[cap] (f32), peak[cap] (f32), flags[cap]
 // The filter block (device, f64): shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2}, then LOUD_LEVELS 4 x 4
 // matrices A^(R 2^k), k = 0 .. LOUD_LEVELS - 1, row-major: what R samples of silence make of the cascade's four states.
-enum { LOUD_SHORT = 1, LOUD_UNMEASURABLE = 2, LOUD_LIMITED = 4 };
+enum { LOUD_SHORT = 1, LOUD_UNMEASURABLE = 2, LOUD_LIMITED = 4, LOUD_SHAPED = 8 };      // (SHAPED: the look-ahead limiter, below)
 static constexpr int LOUD_TPB = 256;           // threads (= runs) of a segment's workgroup
 static constexpr int LOUD_LEVELS = 8;          // log2(LOUD_TPB)
 static constexpr int LOUD_COEF_DOUBLES = 10 + 16 * LOUD_LEVELS;
@@ -332,6 +332,7 @@ struct LoudP {
   int h, W, R;                                 // samples of a 100 ms segment, of the warm-up in front of it, of one thread's run
   double* seg; int nseg_cap;                   // segment sums seg[b][nseg_cap]
   unsigned* tpeak;                             // true-peak words [rows] to clear for true_peak_kernel, or null (sample-peak ceiling)
+  int* limrep; int limcap;                     // limiter report words (lim_o_*) to clear for limiter_kernel, or null (limiter off)
 };
 
 // ---- true-peak ceiling of the target loudness (true_peak.h: true_peak_kernel)
@@ -352,6 +353,53 @@ struct TpP {
   const int* lens; int len_mul; long x_cap;
   const float* coef; int Q;                    // [Q][TP_TAPS] polyphase table
   unsigned* tpeak;                             // [rows], zero before the launch
+  float* v;                                    // true_peak_v_kernel only: v[b][c] = max over ph of |y[c Q + ph]|, row stride x_bs
+};
+
+// ---- look-ahead limiter of the target loudness (limiter.h: limiter_kernel)
+// On / off picks the launches (limiter_kernel in pcm16_gain_kernel's place) and is part of the graph keys; W, the window in
+// samples of the delivered rate, is a kernel argument. A row is SHAPED when the ceiling would have won (LIMITED) and the
+// loudness is measurable: loudness_gain_kernel then leaves scale = 32767 g, g = 10^((T - L) / 20), and the flag, and
+// limiter_kernel multiplies the row by an envelope e <= 1 that holds g |x| e under the ceiling. The weights h[2 W + 1]
+// (raised cosine, sum 1, computed in f64 and rounded once) live in a device table. The report block (device ints, copied to
+// pinned host memory with the call's samples): the largest 1 - e of a row as a float's bit pattern, then the count of
+// samples with e < 1.
+static constexpr int LIM_TILE = 2048;          // samples of a row per workgroup
+static constexpr int LIM_MAXW = 480;           // 10 ms at 48000 Hz
+static constexpr int LIM_SPAN = LIM_TILE + 4 * LIM_MAXW + 4;      // floats of LDS: the tile, 2 W of halo a side, alignment slack
+static constexpr int LIM_PER = (LIM_SPAN + 255) / 256;            // span elements per thread
+static constexpr int lim_o_maxred(int cap) { (void)cap; return 0; }
+static constexpr int lim_o_count(int cap) { return cap; }
+// true-peak ceiling: max |z| and the true peak of z = x e as bit patterns (folded by atomicMax), the final trim as f32
+static constexpr int lim_o_pz(int cap) { return 2 * cap; }
+static constexpr int lim_o_tz(int cap) { return 3 * cap; }
+static constexpr int lim_o_trim(int cap) { return 4 * cap; }
+static constexpr int lim_words(int cap) { return 5 * cap; }
+static inline int limiter_window_samples(int fs, double window_ms) {
+  const int W = (int)(window_ms * (double)fs / 1000.0 + 0.5);
+  return W < 1 ? 1 : W;
+}
+struct LimP {
+  const float* x; long x_bs;                   // delivered rows x[b][0 .. n_b), n_b = lens[b] * len_mul cut to x_cap
+  const int* lens; int len_mul; long x_cap;
+  const int* gq; int gcap;                     // device block of loudness_gain_kernel (ld_*): scale and flags per row
+  const int* ctl;                              // control block: C at word 1
+  const float* h; int W;                       // [2 W + 1] weights, W <= LIM_MAXW
+  short* pcm; long p_bs; short* host;          // as pcm16_kernel's
+  int* rep; int rcap;                          // report words (lim_o_*), cleared before the launch
+  float* env; long e_bs;                       // test hook: e[b][0 .. n_b), or null
+  // true-peak ceiling (limiter_kernel<true>): v[b][c] = max over the phases of |y[c Q + ph]| from true_peak_v_kernel, row
+  // stride x_bs; z[b][i] = x e (x on rows that are not shaped), row stride x_bs, in the int16's place
+  const float* v; float* z;
+};
+// pcm16_trim_kernel: the conversion of z behind the second true-peak pass
+struct TrimP {
+  const float* z; long z_bs;
+  const int* lens; int len_mul;
+  const int* gq; int gcap;                     // scale and flags per row
+  int* ctl;                                    // control block: C at word 1; the report's scale is rewritten for shaped rows
+  int* rep; int rcap;                          // pz, tz in; trim out
+  short* pcm; long p_bs; short* host;
 };
 
 // ---- fused MRF stage (mrf.h)

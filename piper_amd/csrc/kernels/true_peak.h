@@ -22,8 +22,10 @@ namespace pe {
 // bit. max |y| meets across the lanes, then across the four waves through LDS, and goes to the row's word with one
 // atomicMax on the bit pattern per workgroup (non-negative floats order like their bit patterns). The word was zeroed by
 // loudness_seg_kernel, which is stream-ordered before this launch.
-__global__ __launch_bounds__(256) void true_peak_kernel(TpP p) {
-  PE_KTRACE(35);
+// STORE (true_peak_v_kernel, the look-ahead limiter under the true-peak ceiling): the per-position maximum over the phases
+// goes to p.v as well. The default instantiation is the kernel as it was: nothing of the store is in it.
+template <bool STORE>
+__device__ __forceinline__ void true_peak_body(const TpP& p) {
   __shared__ __attribute__((aligned(16))) float xs[TP_SPAN];
   __shared__ __attribute__((aligned(16))) float cs[TP_MAXQ * TP_TAPS];
   __shared__ float wmax[4];
@@ -62,6 +64,8 @@ __global__ __launch_bounds__(256) void true_peak_kernel(TpP p) {
   float m = 0.f;
   for (int i = threadIdx.x; i < nt; i += 256) {
     float xv[TP_TAPS];
+    float vm = 0.f;
+    (void)vm;
 #pragma unroll
     for (int k = 0; k < TP_TAPS; ++k) xv[k] = xs[lead + i + k];
     for (int ph = 0; ph < Q; ++ph) {
@@ -76,13 +80,23 @@ __global__ __launch_bounds__(256) void true_peak_kernel(TpP p) {
         acc = fmaf(c[3], xv[k + 3], acc);
       }
       m = fmaxf(m, fabsf(acc));
+      if constexpr (STORE) vm = fmaxf(vm, fabsf(acc));
     }
+    if constexpr (STORE) p.v[(long)b * p.x_bs + t0 + i] = vm;
   }
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0)
     atomicMax(p.tpeak + b, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
+}
+__global__ __launch_bounds__(256) void true_peak_kernel(TpP p) {
+  PE_KTRACE(35);
+  true_peak_body<false>(p);
+}
+__global__ __launch_bounds__(256) void true_peak_v_kernel(TpP p) {
+  PE_KTRACE(37);
+  true_peak_body<true>(p);
 }
 
 }  // namespace pe

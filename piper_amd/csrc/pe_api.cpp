@@ -559,6 +559,51 @@ int pe_debug_true_peak(pe_engine* e, const float* x, int32_t batch, int64_t stri
   });
 }
 
+int pe_set_loudness_limiter(pe_engine* e, int32_t on, float window_ms) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_loudness_limiter(on != 0, window_ms);
+  });
+}
+
+int pe_get_loudness_limiter(pe_engine* e, int32_t* on, float* window_ms, int32_t* window_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (on) *on = e->eng->loudness_limiter_on() ? 1 : 0;
+    if (window_ms) *window_ms = e->eng->loudness_limiter_ms();
+    if (window_samples) *window_samples = e->eng->loudness_limiter_window();
+  });
+}
+
+int pe_last_limiter(pe_engine* e, float* max_reduction, int32_t* shaped_samples, float* trim, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->last_limiter(max_reduction, shaped_samples, trim, capacity);
+  });
+}
+
+int pe_limiter_window(int32_t fs, float window_ms, int32_t* window_samples, double* coef, int64_t capacity, int64_t* n) {
+  return guard([&] {
+    int W;
+    std::vector<double> table;
+    pe::Engine::limiter_window(fs, window_ms, W, table);
+    if (window_samples) *window_samples = W;
+    if (n) *n = (int64_t)table.size();
+    if (coef) {
+      if (capacity < (int64_t)table.size()) throw std::runtime_error("limiter window buffer too small");
+      for (size_t i = 0; i < table.size(); ++i) coef[i] = table[i];
+    }
+  });
+}
+
+int pe_debug_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, const float* g,
+                     float ceiling_db, int32_t kind, float window_ms, float* env_out, int16_t* pcm_out) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_limiter(x, batch, stride, valid, fs, g, ceiling_db, kind, window_ms, env_out, pcm_out);
+  });
+}
+
 int pe_debug_resample(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, const int64_t* n0,
                       const int32_t* count, const int64_t* origin, float* out, int64_t out_stride) {
   return guard([&] {

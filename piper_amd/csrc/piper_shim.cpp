@@ -363,7 +363,13 @@ static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) 
   int32_t kind = PE_PEAK_SAMPLE;
   check(pe_get_loudness_ceiling(session.engine, &kind, nullptr, nullptr));
   const int32_t want_kind = sc.truePeak ? PE_PEAK_TRUE : PE_PEAK_SAMPLE;
+  // SynthesisConfig::limiter / limiterMs, likewise remembered
+  int32_t lim = 0;
+  float lim_ms = 0.f;
+  check(pe_get_loudness_limiter(session.engine, &lim, &lim_ms, nullptr));
+  if (!sc.limiter && lim) check(pe_set_loudness_limiter(session.engine, 0, 0.f));
   if (kind != want_kind) check(pe_set_loudness_ceiling(session.engine, want_kind));
+  if (sc.limiter && (!lim || lim_ms != sc.limiterMs)) check(pe_set_loudness_limiter(session.engine, 1, sc.limiterMs));
   if (!sc.targetLufs) {
     if (lon) check(pe_set_loudness(session.engine, 0, 0.f, 0.f));
   } else if (!lon || lt != *sc.targetLufs || lc != sc.peakCeilingDb) {

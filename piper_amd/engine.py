@@ -408,28 +408,89 @@ class Engine:
 
     PEAK_SAMPLE, PEAK_TRUE = 0, 1
 
-    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0, true_peak: bool = False):
+    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0, true_peak: bool = False,
+                     limiter: bool = False, limiter_ms: float = 5.0):
         """Deliver every WHOLE utterance at ``target_lufs`` LUFS (ITU-R BS.1770-4 gated integrated loudness, mono,
         measured on the device on the floats the call delivers) under a ceiling of ``ceiling_db`` dB -- on the sample
         peak, or with ``true_peak`` on the true peak of BS.1770-4 Annex 2 as well (dBTP), measured on the device
-        (include/piper_hip.h: pe_set_loudness, pe_set_loudness_ceiling). ``None``: off, the default -- every utterance
-        scaled by ``32767 / max(0.01, peak)``; the kind of ceiling is remembered. The floats never change; stream chunks
-        keep their own rules. A refused call changes nothing."""
+        (include/piper_hip.h: pe_set_loudness, pe_set_loudness_ceiling). ``limiter``: where the ceiling and the target
+        conflict, keep the target's gain and turn down only the neighbourhood of the peaks, with a zero-phase window of
+        ``limiter_ms`` in [1, 10] (pe_set_loudness_limiter; either kind of ceiling). ``None``: off, the default -- every
+        utterance scaled by ``32767 / max(0.01, peak)``; the kind of ceiling and the limiter are remembered. The floats
+        never change; stream chunks keep their own rules. A refused call changes nothing."""
         kind = self.PEAK_TRUE if true_peak else self.PEAK_SAMPLE
-        if target_lufs is None:
-            self._check(self._lib.pe_set_loudness(self._h, 0, 0.0, 0.0))
-            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
-            return
         before = self.loudness_ceiling()[0]
-        # (the true-peak kind first: it is refused while the loudness is on at a rate it does not cover)
-        if true_peak:
-            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
-        if self._lib.pe_set_loudness(self._h, 1, float(target_lufs), float(ceiling_db)):
+        lim_before = self.loudness_limiter()
+        loud_before = self.loudness()
+
+        def attempt(rc):
+            if not rc:
+                return
             err = EngineError(self._lib.pe_last_error().decode(errors="replace"))
+            # everything back as it was: the loudness off first, so that no intermediate combination is refused
+            self._lib.pe_set_loudness(self._h, 0, 0.0, 0.0)
+            self._lib.pe_set_loudness_limiter(self._h, 0, 0.0)
             self._lib.pe_set_loudness_ceiling(self._h, before)
+            self._lib.pe_set_loudness_limiter(self._h, int(lim_before[0]), float(lim_before[1]))
+            if loud_before[0] is not None:
+                self._lib.pe_set_loudness(self._h, 1, float(loud_before[0]), float(loud_before[1]))
             raise err
-        if not true_peak:
-            self._check(self._lib.pe_set_loudness_ceiling(self._h, kind))
+
+        # (the limiter's window and the kind are checked before the loudness is touched; the true-peak kind goes in front
+        # of the loudness, which it is refused with at a rate it does not cover)
+        if limiter:
+            attempt(self._lib.pe_set_loudness_limiter(self._h, 1, float(limiter_ms)))
+        if target_lufs is None:
+            attempt(self._lib.pe_set_loudness(self._h, 0, 0.0, 0.0))
+            attempt(self._lib.pe_set_loudness_ceiling(self._h, kind))
+        else:
+            if true_peak:
+                attempt(self._lib.pe_set_loudness_ceiling(self._h, kind))
+            attempt(self._lib.pe_set_loudness(self._h, 1, float(target_lufs), float(ceiling_db)))
+            if not true_peak:
+                attempt(self._lib.pe_set_loudness_ceiling(self._h, kind))
+        if not limiter:
+            attempt(self._lib.pe_set_loudness_limiter(self._h, 0, 0.0))
+
+    LOUD_SHAPED = 8
+
+    def loudness_limiter(self):
+        """(on, window_ms, W) of the look-ahead limiter (pe_get_loudness_limiter): W is the window in samples of the
+        delivered rate (0 where the rate is unknown)."""
+        on, ms, w = C.c_int32(), C.c_float(), C.c_int32()
+        self._check(self._lib.pe_get_loudness_limiter(self._h, C.byref(on), C.byref(ms), C.byref(w)))
+        return bool(on.value), float(ms.value), w.value
+
+    def last_limiter(self):
+        """(max_reduction, shaped_samples, trim) arrays of the last fetched whole-utterance call, one entry per utterance
+        (pe_last_limiter); empty when that call ran without the limiter."""
+        n = C.c_int32()
+        self._check(self._lib.pe_last_limiter(self._h, None, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        r, c, t = np.zeros(m, np.float32), np.zeros(m, np.int32), np.zeros(m, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_last_limiter(self._h, r.ctypes.data_as(fp), c.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              t.ctypes.data_as(fp), m, C.byref(n)))
+        return r[:n.value], c[:n.value], t[:n.value]
+
+    def debug_limiter(self, rows, fs: int, g, ceiling_db: float = -1.0, kind: int = 0, window_ms: float = 5.0, pad=0.0):
+        """Test hook (pe_debug_limiter): the limiter kernel alone on ``rows``, a list of 1-D float arrays at rate ``fs``
+        with one gain ``g[b]`` each; what lies behind a row's end in the staging matrix holds ``pad``. Returns (e, pcm):
+        lists of one float32 / int16 array per row."""
+        B = len(rows)
+        valid = np.asarray([len(r) for r in rows], np.int32)
+        stride = max(1, int(valid.max()))
+        x = np.full((B, stride), pad, np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        gv = np.ascontiguousarray(g, np.float32)
+        assert gv.shape == (B,)
+        env, pcm = np.full((B, stride), np.nan, np.float32), np.zeros((B, stride), np.int16)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_debug_limiter(self._h, x.ctypes.data_as(fp), B, stride, valid.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               int(fs), gv.ctypes.data_as(fp), float(ceiling_db), int(kind), float(window_ms),
+                                               env.ctypes.data_as(fp), pcm.ctypes.data_as(C.POINTER(C.c_int16))))
+        return [env[b, :valid[b]].copy() for b in range(B)], [pcm[b, :valid[b]].copy() for b in range(B)]
 
     def loudness_ceiling(self):
         """(kind, oversample, half_width) of the ceiling (pe_get_loudness_ceiling): ``PEAK_SAMPLE`` or ``PEAK_TRUE``, the
@@ -770,3 +831,15 @@ def true_peak_filter(fs: int, lib=None):
     if lib.pe_true_peak_filter(int(fs), C.byref(q), C.byref(k), out.ctypes.data_as(C.POINTER(C.c_double)), out.size, C.byref(n)):
         raise EngineError(lib.pe_last_error().decode(errors="replace"))
     return q.value, k.value, out.reshape(q.value, 2 * k.value)
+
+
+def limiter_window(fs: int, window_ms: float, lib=None):
+    """The look-ahead limiter's window at rate ``fs`` (pe_limiter_window; host only): (W, float64 weights [2 W + 1])."""
+    lib = lib if lib is not None else L.get_lib()
+    w, n = C.c_int32(), C.c_int64()
+    if lib.pe_limiter_window(int(fs), float(window_ms), C.byref(w), None, 0, C.byref(n)):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    out = np.zeros(n.value, np.float64)
+    if lib.pe_limiter_window(int(fs), float(window_ms), C.byref(w), out.ctypes.data_as(C.POINTER(C.c_double)), out.size, C.byref(n)):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    return w.value, out

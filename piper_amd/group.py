@@ -48,10 +48,11 @@ class EngineGroup:
         for i in range(len(self)):
             self._lib.pe_set_seed(C.c_void_p(self._lib.pe_group_engine(self._h, i)), int(seed) + i)
 
-    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0, true_peak: bool = False):
+    def set_loudness(self, target_lufs: Optional[float] = None, ceiling_db: float = -1.0, true_peak: bool = False,
+                     limiter: bool = False, limiter_ms: float = 5.0):
         """``Engine.set_loudness`` on every engine of the group (the setting is per handle)."""
         for i in range(len(self)):
-            self.engine(i).set_loudness(target_lufs, ceiling_db, true_peak=true_peak)
+            self.engine(i).set_loudness(target_lufs, ceiling_db, true_peak=true_peak, limiter=limiter, limiter_ms=limiter_ms)
 
     def synthesize_batch(self, id_lists: Sequence[Sequence[int]], scales=(0.667, 1.0, 0.8),
                          sids: Optional[Sequence[int]] = None) -> Synthesis:

@@ -105,6 +105,9 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     parser.add_argument("--peak-ceiling-db", type=float, default=-1.0, help="peak ceiling in dB with --target-lufs (sample peak; with --true-peak: dBTP)")
     parser.add_argument("--true-peak", action="store_true",
                         help="hold the ceiling as a true peak (ITU-R BS.1770-4 Annex 2), measured on the GPU; with --target-lufs")
+    parser.add_argument("--limiter", action="store_true",
+                        help="where the ceiling and --target-lufs conflict, turn down only the peaks (look-ahead limiter on the GPU)")
+    parser.add_argument("--limiter-ms", type=float, default=5.0, help="window of --limiter in ms, 1 to 10")
     parser.add_argument("--noise-scale", type=float, default=0.667)
     parser.add_argument("--noise-scale-w", type=float, default=0.8)
     parser.add_argument("--length-scale", type=float, default=1.0)
@@ -127,7 +130,8 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     if args.target_lufs is not None:
         if not args.output_rate:
             engine.set_output_rate(None, native=args.sample_rate)      # (an .onnx carries no rate of its own)
-        engine.set_loudness(args.target_lufs, args.peak_ceiling_db, true_peak=args.true_peak)
+        engine.set_loudness(args.target_lufs, args.peak_ceiling_db, true_peak=args.true_peak, limiter=args.limiter,
+                            limiter_ms=args.limiter_ms)
     scales = (args.noise_scale, args.length_scale, args.noise_scale_w)
     lines = list(stdin if stdin is not None else sys.stdin)
     utts = read_utterances(lines)

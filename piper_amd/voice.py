@@ -57,13 +57,15 @@ class PiperVoice:
     @staticmethod
     def load(model_path: Union[str, Path], config_path: Optional[Union[str, Path]] = None,
              use_cuda: bool = True, device: int = 0, output_sample_rate: Optional[int] = None,
-             target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, true_peak: bool = False) -> "PiperVoice":
+             target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, true_peak: bool = False,
+             limiter: bool = False, limiter_ms: float = 5.0) -> "PiperVoice":
         """Load an ONNX voice and its config. ``use_cuda`` is accepted for signature compatibility;
         the engine always runs on the GPU (``device``). ``output_sample_rate`` (new): deliver the audio at this rate,
         resampled on the GPU before the int16 conversion (Engine.set_output_rate; the config's rate is the native one).
         ``target_lufs`` (new): deliver every whole utterance at this integrated loudness (ITU-R BS.1770-4, mono) under a
         ceiling of ``peak_ceiling_db`` dB on the sample peak, or with ``true_peak`` on the true peak (dBTP, BS.1770-4
-        Annex 2) as well (Engine.set_loudness); streams keep their chunk rule."""
+        Annex 2) as well (Engine.set_loudness); ``limiter``: where ceiling and target conflict, only the peaks are turned
+        down, by a zero-phase window of ``limiter_ms`` (1 to 10; either kind of ceiling). Streams keep their chunk rule."""
         if config_path is None:
             config_path = f"{model_path}.json"
         with open(config_path, "r", encoding="utf-8") as config_file:
@@ -75,9 +77,10 @@ class PiperVoice:
         if target_lufs is not None:
             if not output_sample_rate:
                 session.set_output_rate(None, native=int(config.sample_rate))      # (an .onnx carries no rate of its own)
-            session.set_loudness(float(target_lufs), float(peak_ceiling_db), true_peak=bool(true_peak))
-        elif true_peak:
-            session.set_loudness(None, true_peak=True)      # (remembered for a later set_loudness)
+            session.set_loudness(float(target_lufs), float(peak_ceiling_db), true_peak=bool(true_peak), limiter=bool(limiter),
+                                 limiter_ms=float(limiter_ms))
+        elif true_peak or limiter:                           # (remembered for a later set_loudness)
+            session.set_loudness(None, true_peak=bool(true_peak), limiter=bool(limiter), limiter_ms=float(limiter_ms))
         return PiperVoice(config=config, session=session, output_sample_rate=output_sample_rate or None)
 
     @property
