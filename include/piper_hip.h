@@ -508,7 +508,10 @@ int pe_group_create(const void* blob, size_t nbytes, const int32_t* devices, int
  * takes the collective even for a single device (self-test on a one-GPU box). */
 const char* pe_group_broadcast_path(void);
 int32_t pe_group_size(pe_group* g);
-pe_engine* pe_group_engine(pe_group* g, int32_t i);           /* e.g. pe_set_seed / pe_get_info / pe_profile_* per device */
+/* Member i of the group, e.g. for pe_set_seed / pe_get_info / pe_profile_* per device. Seeds: pe_group_create gives member i the
+ * default seed + i (1234 + i), so that no two members draw the same noise for their share of a call; pe_set_seed on a member
+ * overrides it (to re-seed a whole group keep the rule: seed + i for member i). */
+pe_engine* pe_group_engine(pe_group* g, int32_t i);
 int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
                               const float scales[3], const int64_t* sids, pe_result* result);
 /* ... with one triple per utterance (scales[batch * 3], as pe_synthesize_batch_scaled): each shard takes its utterances'

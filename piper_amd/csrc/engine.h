@@ -268,6 +268,7 @@ class Engine {
   const int* xcc_pattern(int* period) const { if (period) *period = xcd_period_; return xcc_of_; }
 
   void set_seed(uint64_t s) { seed_ = s; }
+  uint64_t seed() const { return seed_; }
   void set_use_graphs(bool on) { use_graphs_ = on; }
   // level 0 off; 1 = one HIP-event pair per pipeline stage; 2 = additionally one pair around every
   // conv/attention/layer-norm launch (per-kernel rows after the five stage rows)

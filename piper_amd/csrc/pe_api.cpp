@@ -901,6 +901,8 @@ int pe_group_create(const void* blob, size_t nbytes, const int32_t* devices, int
       if (pe_create_in_arena(blob, i == 0 ? nbytes : header, devices[i], g->arena[i], bound, i == 0 ? 0 : 1, &e))
         throw std::runtime_error(g_err);
       g->eng.push_back(e);
+      // members draw from distinct streams: engine i starts at the default seed + i (pe_set_seed on a member overrides it)
+      e->eng->set_seed(e->eng->seed() + (uint64_t)i);
     }
     size_t used = 0;
     if (pe_weights_used(g->eng[0], &used)) throw std::runtime_error(g_err);
