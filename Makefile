@@ -68,8 +68,12 @@ tests/cpp/test_limiter: tests/cpp/test_limiter.cpp $(LIB) include/piper.hpp incl
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_limiter.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
 tests/cpp/test_limiter_emu: tests/cpp/test_limiter.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_limiter.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
+# SynthesisConfig::seed through the piper:: API (tests/test_seeds_emu.py)
+tests/cpp/test_seeds_emu: tests/cpp/test_seeds.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_seeds.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
 
 clean:
 	rm -rf build $(LIB) $(EMULIB) tests/cpp/test_piper tests/cpp/test_piper_emu tests/cpp/test_loudness tests/cpp/test_loudness_emu \
-	       tests/cpp/test_true_peak tests/cpp/test_true_peak_emu tests/cpp/test_limiter tests/cpp/test_limiter_emu
+	       tests/cpp/test_true_peak tests/cpp/test_true_peak_emu tests/cpp/test_limiter tests/cpp/test_limiter_emu \
+	       tests/cpp/test_seeds_emu
 .PHONY: all emu stamps clean

@@ -113,6 +113,12 @@ struct SynthesisConfig {
   // Speaker id from 0 to numSpeakers - 1
   std::optional<SpeakerId> speakerId;
 
+  // Noise seed (piper_hip.h: pe_seeds). Set: the audio of a request depends on the voice, the ids, the settings above and
+  // this value alone -- not on what the engine served before or beside it -- so that it can be cached, repeated or re-taken
+  // with another seed. synthesize uses it as it is; utterance k of synthesizeBatch and phrase k of a textToAudio call,
+  // counted over the whole text, get seed + k (wrapping at 2^64). Unset, the default: the engine's own stream.
+  std::optional<uint64_t> seed;
+
   // Extra silence
   float sentenceSilenceSeconds = 0.2f;
   std::optional<std::map<piper::Phoneme, float>> phonemeSilenceSeconds;

@@ -134,6 +134,33 @@ int pe_upload_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, in
                     const int64_t* sids, const pe_noise* noise, const pe_timing* timing);
 int pe_synthesize_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                               const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing);
+/* Per-utterance noise seeds: a request's audio independent of its batch (the reference's
+ * SynthesisConfig / PiperVoice seed, per utterance instead of per process). Host pointers.
+ *   seed  [batch]: the utterance's seed. Every 64-bit value is a valid seed, 0 and 2^64 - 1 included.
+ *   use   [batch]: != 0, the utterance draws from its seed; 0, from the engine's own stream as ever. NULL: all 1.
+ * The law: a seeded utterance with seed S draws, at both sampling sites, element (row = channel, column = id or frame) of the
+ * stream documented at pe_debug_randn with key S and run counter 0 -- what pe_debug_randn(site, 0, channel, n) returns under
+ * pe_set_seed(S). The engine's own stream starts at counter 1, so a seeded draw never coincides with an unseeded one. Its
+ * noise depends on (S, site, channel, column) and on nothing else: not on the engine seed or pe_rng_calls, its index in the
+ * batch or the batch size, shape buckets or speculation, the kernel that draws, the entry point, the group member, the
+ * coalesced call or the pool slot. An unseeded utterance draws bit for bit what it always did -- (engine seed, counter,
+ * row = b * channels + c) -- also beside seeded ones, and the run counter advances as before in every case.
+ * Noise injected through pe_noise wins at the site it is given for; the seed covers the other site. pe_run repeated on a
+ * seeded upload draws the same noise again (the counter still advances); the next upload of any kind drops the seeds. The
+ * seed values are call inputs like the ids: no captured graph depends on them (whether a call carries seeds at all is part
+ * of the graph keys, so a server whose calls are all seeded stops capturing like any other).
+ * The _seeded entry points are the _timed calls they are named after plus the seeds (pe_stream_begin_seeded: pe_stream_begin
+ * plus a plan and the seeds); timing and seeds may each be NULL, and with NULL seeds they are exactly those calls. A non-NULL
+ * pe_seeds whose `seed` is NULL is refused, with a message, before anything of the engine changes. */
+typedef struct pe_seeds {
+  const uint64_t* seed;
+  const uint8_t* use;
+} pe_seeds;
+int pe_upload_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                     const int64_t* sids, const pe_noise* noise, const pe_timing* timing, const pe_seeds* seeds);
+int pe_synthesize_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                               const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing,
+                               const pe_seeds* seeds);
 int pe_run(pe_engine* e);
 int pe_fetch(pe_engine* e, int want_audio, int want_pcm, pe_result* result);
 
@@ -146,6 +173,10 @@ int pe_fetch(pe_engine* e, int want_audio, int want_pcm, pe_result* result);
  * streaming script. *n_samples == 0 means the utterance is finished. */
 int pe_stream_begin(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                     const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames);
+/* ... under a timing plan and with the utterance's seed (pe_timing, pe_seeds above; seeds->seed[0]) */
+int pe_stream_begin_seeded(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                           const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames, const pe_timing* timing,
+                           const pe_seeds* seeds);
 int pe_stream_next(pe_engine* e, int32_t chunk_frames, const float** audio, const int16_t** pcm, int64_t* n_samples);
 
 /* Streaming decode of a whole batch in lock step: B listeners get their first chunk after the text encoder, the duration
@@ -162,6 +193,10 @@ int pe_stream_begin_batch(pe_engine* e, const int64_t* ids, const int64_t* offse
 int pe_stream_begin_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                                 const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
                                 const pe_timing* timing);
+/* ... and with per-utterance seeds (pe_seeds above) */
+int pe_stream_begin_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                 const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                 const pe_timing* timing, const pe_seeds* seeds);
 
 typedef struct pe_stream_chunk {
   int32_t batch;
@@ -215,6 +250,10 @@ int pe_stream_pool_join(pe_engine* e, const int64_t* ids, const int64_t* offsets
 int pe_stream_pool_join_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
                               const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
                               const pe_timing* timing);
+/* ... and with per-utterance seeds (pe_seeds above): a newcomer's audio does not depend on the slot it gets */
+int pe_stream_pool_join_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                               const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                               const pe_timing* timing, const pe_seeds* seeds);
 int pe_stream_pool_next(pe_engine* e, int32_t chunk_frames, const int32_t* chunk_frames_per_slot, int want_audio,
                         pe_stream_chunk* out);
 int pe_stream_pool_leave(pe_engine* e, int32_t slot);
@@ -518,6 +557,10 @@ int pe_group_synthesize_batch(pe_group* g, const int64_t* ids, const int64_t* of
  * triples along with their ids */
 int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
                                      const float* scales, const int64_t* sids, pe_result* result);
+/* ... and with per-utterance seeds (pe_seeds above; NULL: exactly the _scaled call): each shard takes its utterances' seeds
+ * along with their ids, so a seeded utterance's audio does not depend on the member that ran it */
+int pe_group_synthesize_batch_seeded(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                     const float* scales, const int64_t* sids, pe_result* result, const pe_seeds* seeds);
 /* which engine (index into the group) ran utterance i of the last call */
 int pe_group_assignment(pe_group* g, int32_t* engine_index, int64_t capacity);
 void pe_group_destroy(pe_group* g);
@@ -541,6 +584,12 @@ int pe_coalescer_create(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe
 int pe_coalescer_create_mixed(pe_engine* e, int32_t max_batch, int32_t max_wait_us, pe_coalescer** out);
 int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                             int16_t** pcm, int64_t* n_samples, int32_t* frames, double* infer_seconds, int32_t* batch_size);
+/* ... with the request's noise seed (*seed; pe_seeds above), NULL for an unseeded request: exactly the call above. Both kinds
+ * of coalescer merge seeded and unseeded requests into one engine call; a seeded request gets the noise of its own seeded
+ * B = 1 call whatever it was merged with. */
+int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                                   const uint64_t* seed, int16_t** pcm, int64_t* n_samples, int32_t* frames,
+                                   double* infer_seconds, int32_t* batch_size);
 int pe_coalescer_stats(pe_coalescer* c, int64_t* engine_calls, int64_t* requests);
 void pe_coalescer_destroy(pe_coalescer* c);
 

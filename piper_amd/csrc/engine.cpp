@@ -162,16 +162,18 @@ void Engine::ensure_stage_a(int B, int Tmax) {
   const int Ts = rup(Tmax, 128);    // row strides are multiples of 128 columns (conv epilogue relies on it)
   auto carve = [&](char* base, size_t Bc, size_t T) -> size_t {
     Carver c(base);
-    // input block: [rng 4 x u64 | lengths Bc | speaker ids Bc | scales Bc x 3 (padded to 4) | ids Bc x T] (contiguous,
-    // copied as one piece by upload())
-    const size_t ns = in_scale_slots(Bc);
-    d_in_ = c.take<char>(32 + (2 * Bc + ns + Bc * T) * sizeof(int));
+    // input block: [rng 4 x u64 | seed keys Bc x u64, use flags Bc (padded to 16 bytes) | lengths Bc | speaker ids Bc |
+    // scales Bc x 3 (padded to 4) | ids Bc x T] (contiguous, copied as one piece by upload())
+    const size_t ns = in_scale_slots(Bc), head = in_head_bytes(Bc);
+    d_in_ = c.take<char>(head + (2 * Bc + ns + Bc * T) * sizeof(int));
     d_rng_ = reinterpret_cast<unsigned long long*>(d_in_);
-    d_tlens_ = reinterpret_cast<int*>(d_in_ + 32);
+    d_keys_ = reinterpret_cast<unsigned long long*>(d_in_ + 32);
+    d_use_ = reinterpret_cast<int*>(d_in_ + 32 + 8 * Bc);
+    d_tlens_ = reinterpret_cast<int*>(d_in_ + head);
     d_sids_ = d_tlens_ + Bc;
     d_scales_ = reinterpret_cast<float*>(d_sids_ + Bc);
     d_ids_ = d_sids_ + Bc + ns;
-    in_bytes_ = 32 + (2 * Bc + ns + Bc * T) * sizeof(int);
+    in_bytes_ = head + (2 * Bc + ns + Bc * T) * sizeof(int);
     d_dur_ = c.take<int>(Bc * T);
     d_cum_ = c.take<int>(Bc * T);
     d_frames_ = c.take<int>(Bc);
@@ -351,10 +353,11 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
 // ------------------------------------------------------------------------------------------------
 
 void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                    const int64_t* sids, const NoiseIn* noise, bool per_utt, const TimingIn* timing) {
+                    const int64_t* sids, const NoiseIn* noise, bool per_utt, const TimingIn* timing, const SeedsIn* seeds) {
   EntryLock entry_lock;
   if (B <= 0 || B > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
   if (!scales) throw std::runtime_error("null scales");
+  if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
   const bool all_forced = timing ? check_timing(*timing, offsets, B) : false;      // (throws before anything changes)
   PE_HIP(hipSetDevice(device_));
   sb_active_ = false;               // new inputs end a batch stream: its latent and its window state go with them
@@ -379,7 +382,7 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   // final synchronisation (an abandoned upload is simply overwritten)
   const size_t Bc = capA_B_;
   unsigned long long* hr = reinterpret_cast<unsigned long long*>(h_in_);
-  int* htl = reinterpret_cast<int*>(h_in_ + 32);
+  int* htl = reinterpret_cast<int*>(h_in_ + in_head_bytes(Bc));
   int* hsid = htl + Bc;
   float* hsc = reinterpret_cast<float*>(hsid + Bc);
   int* hid = hsid + Bc + in_scale_slots(Bc);
@@ -421,10 +424,20 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   // lengths / speaker ids / generator state to device memory for the kernels behind it (the serial tells it a replay
   // without a new upload from a fresh one).
   hr[0] = seed_; hr[1] = call_; hr[2] = ++upload_serial_; hr[3] = 0;
+  // per-utterance seeds: values in the block (an unseeded call's kernels get no table and read none of it)
+  seeded_ = seeds != nullptr;
+  if (seeded_) {
+    unsigned long long* hk = reinterpret_cast<unsigned long long*>(h_in_ + 32);
+    int* hu = reinterpret_cast<int*>(h_in_ + 32 + 8 * Bc);
+    for (int b = 0; b < B; ++b) {
+      hk[b] = (unsigned long long)seeds->seed[b];
+      hu[b] = (!seeds->use || seeds->use[b]) ? 1 : 0;
+    }
+  }
   ids_zc_ = pol_.ids_from_host((long)B * Ts);
   if (!ids_zc_)
-    PE_HIP(hipMemcpyAsync(d_in_, h_in_, 32 + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int), hipMemcpyHostToDevice,
-                          stream_));
+    PE_HIP(hipMemcpyAsync(d_in_, h_in_, in_head_bytes(Bc) + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int),
+                          hipMemcpyHostToDevice, stream_));
   plan_on_ = timing != nullptr;
   plan_skip_ = all_forced;
   if (timing) {
@@ -658,7 +671,7 @@ void Engine::run() {
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
     // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key());
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key(), seed_key());
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -685,7 +698,7 @@ void Engine::run() {
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, loud_key());
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s", B, Fg_, Fs_, Ts_, loud_key(), seed_key());
     run_stage('B', key);
   }
 }
@@ -694,8 +707,8 @@ void Engine::run() {
 // plan is present, the duration predictor is left out -- and nothing of the plan's values.
 std::string Engine::stage_a_key(int B) const {
   char key[200];
-  if (plan_on_) snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d|p%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_, (int)plan_skip_);
-  else snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d", B, Tg_, Ts_, (int)have_noise_w_, Fs_);
+  if (plan_on_) snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d|p%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, (int)plan_skip_, seed_key());
+  else snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, seed_key());
   return key;
 }
 
@@ -745,7 +758,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s", B_, Fg_, Fs_, Ts_, loud_key());
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s", B_, Fg_, Fs_, Ts_, loud_key(), seed_key());
   run_stage('B', key);
   return false;
 }
@@ -807,11 +820,12 @@ void Engine::download(bool want_audio, bool want_pcm) {
   loud_collect();
 }
 
-int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise) {
+int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise,
+                         const TimingIn* timing, const SeedsIn* seeds) {
   EntryLock entry_lock;
   const int64_t offs[2] = {0, n};
   const int64_t sids[1] = {sid < 0 ? 0 : sid};
-  upload(ids, offs, 1, scales, sids, noise);
+  upload(ids, offs, 1, scales, sids, noise, false, timing, seeds);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   stream_front(1, 0);
@@ -946,15 +960,16 @@ void Engine::stream_front(int B, int max_frames) {
   if (have_noise_z_) {
     issue_flow();
   } else {
-    snprintf(key, sizeof(key), "F|%d|%d|%d|%d", B, Fg_, Fs_, Ts_);
+    snprintf(key, sizeof(key), "F|%d|%d|%d|%d%s", B, Fg_, Fs_, Ts_, seed_key());
     run_stage('F', key);
   }
 }
 
 const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                                                       const int64_t* sids, const NoiseIn* noise, const TimingIn* timing) {
+                                                       const int64_t* sids, const NoiseIn* noise, const TimingIn* timing,
+                                                       const SeedsIn* seeds) {
   EntryLock entry_lock;
-  upload(ids, offsets, B, scales, sids, noise, true, timing);
+  upload(ids, offsets, B, scales, sids, noise, true, timing, seeds);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
@@ -1154,9 +1169,11 @@ void Engine::stream_pool_leave(int slot) {
 }
 
 void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
-                              const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing) {
+                              const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing,
+                              const SeedsIn* seeds) {
   EntryLock entry_lock;
   stream_pool_require();
+  if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
   if (n < 1) throw std::runtime_error("batch size must be in [1, 4096]");
   std::vector<int> take;
   for (int s = 0; s < sp_slots_ && (int)take.size() < n; ++s)
@@ -1174,7 +1191,7 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
       if (timing->target[j] > sp_maxf_)
         throw std::runtime_error("utterance " + std::to_string(j) + " has a target of " + std::to_string(timing->target[j]) +
                                  " frames, the stream pool holds at most " + std::to_string(sp_maxf_) + " (max_frames)");
-  upload(ids, offsets, n, scales, sids, noise, true, timing);
+  upload(ids, offsets, n, scales, sids, noise, true, timing, seeds);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent)

@@ -63,6 +63,13 @@ struct TimingIn {
   const int32_t* target = nullptr;
 };
 
+// Per-utterance noise seeds (include/piper_hip.h: pe_seeds). Host pointers: seed[B]; use[B], null = every
+// utterance of the call is seeded.
+struct SeedsIn {
+  const uint64_t* seed = nullptr;
+  const uint8_t* use = nullptr;
+};
+
 // Where the packed voice weights live. Default: one device allocation owned by the engine. A caller-provided arena
 // (multi-GPU: a device buffer the host framework can hand to RCCL) receives them instead; with `skeleton` the engine only
 // lays the arena out (same offsets as on the packing rank, derived from tensor shapes alone) and waits for its content
@@ -87,9 +94,13 @@ class Engine {
   // device memory like the ids: no captured graph depends on their values.
   // timing: the call's plan, checked before anything of the engine changes (a refused plan leaves a live stream alone). It
   // stays with the uploaded inputs -- every run() on them follows it -- and goes with the next upload.
+  // seeds: per-utterance noise seeds, checked like the plan. They stay with the uploaded inputs -- every run() on them draws
+  // the same noise again -- and go with the next upload of any kind.
   void upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-              const int64_t* sids, const NoiseIn* noise, bool per_utt = false, const TimingIn* timing = nullptr);
+              const int64_t* sids, const NoiseIn* noise, bool per_utt = false, const TimingIn* timing = nullptr,
+              const SeedsIn* seeds = nullptr);
   bool timed() const { return plan_on_; }
+  bool seeded() const { return seeded_; }
   // test hook: duration_plan_kernel alone on caller-given logw rows (concatenated like ids, offsets[batch + 1]) with one
   // scales triple per utterance: the durations and w (concatenated) and the frame counts
   void debug_timing(const float* logw, const int64_t* offsets, int batch, const float* scales, const TimingIn* timing,
@@ -104,7 +115,8 @@ class Engine {
   // count; every stream_next decodes the next `chunk_frames` frames through HiFiGAN on a window padded
   // with the generator's exact receptive half-width, so the concatenated chunks equal the unchunked
   // waveform (the reference pads by a heuristic 5-10 frames and does not). Returns false when done.
-  int stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise);
+  int stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise,
+                   const TimingIn* timing = nullptr, const SeedsIn* seeds = nullptr);
   bool stream_next(int chunk_frames, const float** audio, const int16_t** pcm, int64_t* nsamples);
   // halo of a stream window in frames: the generator's receptive half-width, plus one frame while an output rate is set
   // (the resampler needs exact native samples up to K <= hop beyond a chunk's edges)
@@ -224,7 +236,8 @@ class Engine {
     const int32_t* frames_done = nullptr;       // [batch]
   };
   const std::vector<int32_t>& stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                                                 const int64_t* sids, const NoiseIn* noise, const TimingIn* timing = nullptr);
+                                                 const int64_t* sids, const NoiseIn* noise, const TimingIn* timing = nullptr,
+                                                 const SeedsIn* seeds = nullptr);
   void stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out);
 
   // Stream pool: a fixed number of slots whose latents and decoder conditioning rows live in storage OWNED BY THE POOL,
@@ -239,7 +252,8 @@ class Engine {
   // A join that fails (too few free slots, an utterance over max_frames, an upload error) leaves the pool as it was.
   int stream_pool_open(int slots, int max_frames);                 // returns the halo in frames
   void stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
-                        const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing = nullptr);
+                        const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing = nullptr,
+                        const SeedsIn* seeds = nullptr);
   void stream_pool_next(int chunk_frames, const int32_t* per_slot, bool want_audio, StreamChunk& out);   // out.batch == slots
   void stream_pool_leave(int slot);
   void stream_pool_close();
@@ -563,7 +577,17 @@ class Engine {
       *d_frames_ = nullptr;
   float* d_scales_ = nullptr;        // [B][3] per-utterance {noise_scale, length_scale, noise_w}, part of the input block
   static size_t in_scale_slots(size_t Bc) { return (3 * Bc + 3) & ~(size_t)3; }   // its 4-byte slots (ids stay 16-byte aligned)
-  // The small inputs of a call -- {seed, call}, lengths, speaker ids, scales, phoneme ids -- are one contiguous block in the stage-A
+  // Per-utterance seeds of the uploaded inputs: keys[Bc] (64-bit) and use[Bc] (ints) sit in the input block
+  // right behind the generator state, in front of the lengths, so that they travel with the block's one copy -- or are read
+  // in place and published by embed_kernel on the zero-copy path. The VALUES are data; whether the call carries seeds at
+  // all picks the kernels' key-table arguments (null without) and is part of the graph keys (seed_key), so an unseeded
+  // call's graphs are what they always were.
+  static size_t in_seed_bytes(size_t Bc) { return (12 * Bc + 15) & ~(size_t)15; }
+  static size_t in_head_bytes(size_t Bc) { return 32 + in_seed_bytes(Bc); }
+  unsigned long long* d_keys_ = nullptr; int* d_use_ = nullptr;
+  bool seeded_ = false;
+  const char* seed_key() const { return seeded_ ? "|s" : ""; }
+  // The small inputs of a call -- {seed, call}, seeds, lengths, speaker ids, scales, phoneme ids -- are one contiguous block in the stage-A
   // workspace (d_in_) mirrored by a pinned host block (h_in_): upload() fills the host block and enqueues ONE copy, no
   // synchronisation (the pinned block outlives the copy; the call's final synchronisation covers it)
   char* d_in_ = nullptr; char* h_in_ = nullptr; size_t in_bytes_ = 0, h_in_cap_ = 0;

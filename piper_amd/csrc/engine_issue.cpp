@@ -54,12 +54,17 @@ void Engine::issue_stage_a() {
     if (ids_zc_) {
       const size_t Bc = capA_B_;
       ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in_);
-      ep.h_lens = reinterpret_cast<const int*>(h_in_ + 32);
+      ep.h_lens = reinterpret_cast<const int*>(h_in_ + in_head_bytes(Bc));
       ep.h_sids = ep.h_lens + Bc;
       ep.h_scales = reinterpret_cast<const float*>(ep.h_sids + Bc);
       ep.h_ids = ep.h_sids + Bc + in_scale_slots(Bc);
       ep.d_lens = d_tlens_; ep.d_sids = d_sids_; ep.d_scales = d_scales_;
+      if (seeded_) {
+        ep.h_keys = reinterpret_cast<const unsigned long long*>(h_in_ + 32);
+        ep.h_use = reinterpret_cast<const int*>(h_in_ + 32 + 8 * Bc);
+      }
     }
+    if (seeded_) { ep.keys = d_keys_; ep.use = d_use_; }
     // small calls: the duration noise is drawn here too (one workgroup, <= 4 Philox blocks per thread), not by a launch of
     // its own in front of the first ConvFlow
     // (a call whose every duration is forced draws no duration noise at all)
@@ -255,7 +260,8 @@ void Engine::issue_stage_a() {
   fl += 2.0 * tsum * (2 + arch_[A_DDSLAYERS]) * dp_pre_.macs_per_col;
   // z = noise * noise_scale_w   [B][2][Ts]
   if (!have_noise_w_ && !drew_w_)
-    PE_LAUNCH_KB("randn_kernel", 4.0 * 2.0 * tsum, launch::randn(stream_, noise_w_, (long)B * 2, T, (long)Ts, 0L, d_rng_, 0));
+    PE_LAUNCH_KB("randn_kernel", 4.0 * 2.0 * tsum, launch::randn(stream_, noise_w_, (long)B * 2, T, (long)Ts, 0L, d_rng_, 0,
+                                                               seeded_ ? d_keys_ : nullptr, d_use_, 2));
   if (!pol_.fuse_dp) {
     const long n = (long)B * 2 * Ts;
     PE_LAUNCH_K("scale_kernel", launch::scale(dim3((unsigned)((n + 255) / 256)), stream_, noise_w_, z2_, n, d_scales_ + 2, (long)2 * Ts));
@@ -337,6 +343,7 @@ void Engine::issue_flow() {
     rp.out = zp_; rp.o_bs = (long)C_ * Fs; rp.o_cs = Fs; rp.C = C_;
     rp.absmax = absmax_;
     rp.rng = d_rng_; rp.gen = have_noise_z_ ? 0 : 1;
+    if (seeded_) { rp.keys = d_keys_; rp.use = d_use_; }
     rp.fold = fold_dur_ ? 1 : 0;
     if (fold_dur_) rp.dur = fold_dp_;
     PE_LAUNCH_KB("regulate_kernel", 4.0 * (2.0 * C_ * cols_ids_ + 3.0 * C_ * fsum), launch::regulate(dim3((Fmax + 255) / 256, (C_ + 3) / 4, B), stream_, rp));

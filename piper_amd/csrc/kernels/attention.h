@@ -32,8 +32,13 @@ __global__ void embed_kernel(EmbedP p) {
       // PCIe round trips)
       const int sid = p.h_sids[b];
       const float s0 = p.h_scales[3 * b], s1 = p.h_scales[3 * b + 1], s2 = p.h_scales[3 * b + 2];
+      // a seeded call's key table travels the same way (p.keys == null: the call carries no seeds, nothing more is read)
+      unsigned long long key = 0ull;
+      int use = 0;
+      if (p.keys) { key = p.h_keys[b]; use = p.h_use[b]; }
       p.d_lens[b] = len; p.d_sids[b] = sid;
       p.d_scales[3 * b] = s0; p.d_scales[3 * b + 1] = s1; p.d_scales[3 * b + 2] = s2;
+      if (p.keys) { p.keys[b] = key; p.use[b] = use; }
     }
     if (b == 0) {
       // the state of this run, read by every thread of the workgroup BEFORE thread 0 replaces it (no other workgroup reads it)
@@ -47,10 +52,15 @@ __global__ void embed_kernel(EmbedP p) {
         // the duration noise, one Philox block (four columns of one row) per thread and round: under the latency of the
         // embedding gather below instead of a launch of its own (4.5 us for 2 x 128 values)
         const int per_row = (p.draw_cols + 3) >> 2, nblk = p.draw_rows * per_row;
+        // a seeded call: the key table where this launch can read it -- the pinned block itself on the zero-copy path (the
+        // device copy is being published by the other workgroups of this launch), else the device table the copy filled
+        const unsigned long long* keys = p.keys ? (zc ? p.h_keys : p.keys) : nullptr;
+        const int* use = zc ? p.h_use : p.use;
         for (int q = threadIdx.x; q < nblk; q += blockDim.x) {
           const int row = q / per_row, c4 = (q - row * per_row) * 4;
           float g[4];
-          randn4v(((long)row * RNG_PITCH + c4) >> 2, seed, counter, 0, g);
+          if (rng_seeded(keys, use, row >> 1)) randn4v(((long)(row & 1) * RNG_PITCH + c4) >> 2, keys[row >> 1], RNG_SEEDED_COUNTER, 0, g);
+          else randn4v(((long)row * RNG_PITCH + c4) >> 2, seed, counter, 0, g);
           for (int k = 0; k < 4 && c4 + k < p.draw_cols; ++k) p.draw_out[(long)row * p.draw_stride + c4 + k] = g[k];
         }
       }

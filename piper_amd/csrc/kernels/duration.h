@@ -64,15 +64,19 @@ __global__ __launch_bounds__(256) void duration_kernel(DurP p) {
 // written to -- so for a given (seed, run counter) the noise of frame f of channel c of utterance b does not depend on
 // workspace capacities, shape buckets or whether the frame count was speculated. One thread = one Philox block = four
 // consecutive columns of one row; `row0` = first logical row (test hook: any window of the stream).
+// Per-utterance seeds (rng.h; keys null: none): the rows of a seeded utterance -- row / ch, uniform over the workgroup -- are
+// rows 0 .. ch - 1 of the stream of its own key.
 __global__ void randn_kernel(float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
-                             int site) {
+                             int site, const unsigned long long* keys, const int* use, int ch) {
   PE_KTRACE(15);
   const int nb = (cols + 1023) / 1024;                      // 256 threads x 4 columns per block
   const long row = (long)blockIdx.x / nb;
   const int c4 = (((int)((long)blockIdx.x - row * nb)) * 256 + (int)threadIdx.x) * 4;
   if (row >= rows || c4 >= cols) return;
   float g[4];
-  randn4(((row0 + row) * RNG_PITCH + c4) >> 2, state, site, g);
+  const int b = keys ? (int)((row0 + row) / ch) : 0;
+  if (rng_seeded(keys, use, b)) randn4v(((row0 + row - (long)b * ch) * RNG_PITCH + c4) >> 2, keys[b], RNG_SEEDED_COUNTER, site, g);
+  else randn4(((row0 + row) * RNG_PITCH + c4) >> 2, state, site, g);
   for (int k = 0; k < 4 && c4 + k < cols; ++k) out[row * stride + c4 + k] = g[k];
 }
 
@@ -106,7 +110,11 @@ __global__ __launch_bounds__(256) void regulate_kernel(unsigned* absmax, const i
   const int f0 = ((int)blockIdx.x * 64 + (tid & 63)) * 4;
   const int c = (int)blockIdx.y * 4 + (tid >> 6);
   float nz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (p.gen && c < p.C) randn4((((long)b * p.C + c) * RNG_PITCH + f0) >> 2, p.rng, 1, nz);
+  if (p.gen && c < p.C) {
+    // (a seeded utterance, rng.h: the choice is uniform over the workgroup, b = blockIdx.z)
+    if (rng_seeded(p.keys, p.use, b)) randn4v(((long)c * RNG_PITCH + f0) >> 2, p.keys[b], RNG_SEEDED_COUNTER, 1, nz);
+    else randn4((((long)b * p.C + c) * RNG_PITCH + f0) >> 2, p.rng, 1, nz);
+  }
   if (p.fold) {
     // ---- duration_kernel's arithmetic (modules.py:407-409; models.py:702-704), ids [lo, hi) per thread
     const DurP& d = p.dur;

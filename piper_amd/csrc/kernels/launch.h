@@ -57,8 +57,9 @@ void spline_inverse(dim3 grid, hipStream_t stream, const float* hproj, long h_bs
 void scale(dim3 grid, hipStream_t stream, const float* in, float* out, long n, const float* s, long per_utt);
 void duration(dim3 grid, hipStream_t stream, const DurP& p);
 void duration_plan(dim3 grid, hipStream_t stream, const PlanP& p);      // duration_kernel's place under a timing plan (timing.h)
+// keys / use / ch: the per-utterance seed table and the rows per utterance (rng.h); keys null: no utterance is seeded
 void randn(hipStream_t stream, float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
-           int site);
+           int site, const unsigned long long* keys = nullptr, const int* use = nullptr, int ch = 1);
 void regulate(dim3 grid, hipStream_t stream, const RegP& p);
 void xcc_probe(hipStream_t stream, int* out64);       // 64 workgroups, out64[i] = XCC id of workgroup i
 void cond(dim3 grid, hipStream_t stream, const float* emb_g, int gin, const int* sids, const float* w, const float* bias,

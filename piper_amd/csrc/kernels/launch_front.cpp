@@ -107,8 +107,9 @@ void duration(dim3 grid, hipStream_t stream, const DurP& p) { PE_LAUNCH(duration
 void duration_plan(dim3 grid, hipStream_t stream, const PlanP& p) { PE_LAUNCH(duration_plan_kernel, grid, dim3(256), 0, stream, p); }
 
 void randn(hipStream_t stream, float* out, long rows, int cols, long stride, long row0, const unsigned long long* state,
-           int site) {
-  PE_LAUNCH(randn_kernel, dim3(randn_blocks(rows, cols)), dim3(256), 0, stream, out, rows, cols, stride, row0, state, site);
+           int site, const unsigned long long* keys, const int* use, int ch) {
+  PE_LAUNCH(randn_kernel, dim3(randn_blocks(rows, cols)), dim3(256), 0, stream, out, rows, cols, stride, row0, state, site, keys, use,
+            ch);
 }
 
 void regulate(dim3 grid, hipStream_t stream, const RegP& p) {

@@ -197,6 +197,10 @@ struct EmbedP {
   // exactly the values randn_kernel writes -- drawn by workgroup (0, 0, 0), the one that advances the generator state, with
   // the state it publishes; null: randn_kernel draws it in a launch of its own.
   float* draw_out; long draw_stride; int draw_rows, draw_cols;
+  // Per-utterance seeds (rng.h; null: the call carries none): the device table keys[B] / use[B] of the input block, and on
+  // the zero-copy path its pinned mirror, which the kernel publishes to the device table like lengths and scales.
+  unsigned long long* keys; int* use;
+  const unsigned long long* h_keys; const int* h_use;
 };
 
 // ---- durations, N(0,1) generator, length regulator (duration.h)
@@ -229,6 +233,7 @@ struct RegP {
   unsigned* absmax;                            // per-utterance peak accumulator of conv_post_kernel: zeroed here
   const unsigned long long* rng; int gen;      // gen: the prior noise (site 1) is drawn here and stored to `noise`
   DurP dur; int fold;                          // fold: the durations are computed here too (duration_kernel's fields)
+  const unsigned long long* keys; const int* use;      // per-utterance seeds (rng.h), device table; keys null: none
 };
 static constexpr int REG_MAXT = 4096;          // ids whose cumulative durations fit the LDS copy; longer: search in global memory
 

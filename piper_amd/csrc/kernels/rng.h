@@ -43,5 +43,12 @@ __device__ __forceinline__ void randn4v(long q, unsigned long long seed, unsigne
 __device__ __forceinline__ void randn4(long q, const unsigned long long* state, int site, float (&g)[4]) {
   randn4v(q, state[0], state[1], site, g);
 }
+// Per-utterance seeds. An utterance b that carries a seed S (keys[b] = S, use[b] != 0; keys == null: the call
+// carries none) draws element (row = channel, column) of the stream with key S and run counter 0 -- a counter the engine's
+// own stream, which starts at 1, never has -- whatever its place in the batch, the engine seed or the runs so far.
+static constexpr unsigned long long RNG_SEEDED_COUNTER = 0ull;
+__device__ __forceinline__ bool rng_seeded(const unsigned long long* keys, const int* use, int b) {
+  return keys != nullptr && use[b] != 0;
+}
 
 }  // namespace pe

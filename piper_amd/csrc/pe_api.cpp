@@ -68,6 +68,14 @@ static const pe::TimingIn* to_timing(const pe_timing* t, pe::TimingIn& out) {
   return &out;
 }
 
+// A non-NULL pe_seeds needs its seed array: refused here, before the engine is touched (Engine::upload checks the same).
+static const pe::SeedsIn* to_seeds(const pe_seeds* s, pe::SeedsIn& out) {
+  if (!s) return nullptr;
+  if (!s->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
+  out.seed = s->seed; out.use = s->use;
+  return &out;
+}
+
 extern "C" {
 
 const char* pe_last_error(void) { return g_err.c_str(); }
@@ -197,6 +205,19 @@ int pe_upload_timed(pe_engine* e, const int64_t* ids, const int64_t* offsets, in
   });
 }
 
+int pe_upload_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                     const int64_t* sids, const pe_noise* noise, const pe_timing* timing, const pe_seeds* seeds) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t), to_seeds(seeds, s));
+  });
+}
+
 int pe_run(pe_engine* e) {
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
@@ -263,6 +284,26 @@ int pe_synthesize_batch_timed(pe_engine* e, const int64_t* ids, const int64_t* o
   });
 }
 
+int pe_synthesize_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                               const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing,
+                               const pe_seeds* seeds) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    const pe::SeedsIn* sp = to_seeds(seeds, s);
+    const auto t0 = std::chrono::steady_clock::now();
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t), sp);
+    e->eng->run();
+    e->eng->download(true, true);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fill_result(e, result, secs);
+  });
+}
+
 int pe_synthesize(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                   const pe_noise* noise, pe_result* result) {
   if (!e) {
@@ -284,6 +325,21 @@ int pe_stream_begin(pe_engine* e, const int64_t* ids, int64_t n_ids, const float
       n.noise_z = noise->noise_z; n.z_stride = noise->z_stride;
     }
     const int f = e->eng->stream_begin(ids, n_ids, scales, sid, noise ? &n : nullptr);
+    if (total_frames) *total_frames = f;
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
+int pe_stream_begin_seeded(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                           const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames, const pe_timing* timing,
+                           const pe_seeds* seeds) {
+  return guard([&] {
+    if (!e || !ids || !scales) throw std::runtime_error("null argument");
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    const int f = e->eng->stream_begin(ids, n_ids, scales, sid, noise ? &n : nullptr, to_timing(timing, t), to_seeds(seeds, s));
     if (total_frames) *total_frames = f;
     if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
   });
@@ -320,6 +376,23 @@ int pe_stream_begin_batch_timed(pe_engine* e, const int64_t* ids, const int64_t*
     pe::TimingIn t;
     const std::vector<int32_t>& f =
         e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr, to_timing(timing, t));
+    if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
+int pe_stream_begin_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                 const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                 const pe_timing* timing, const pe_seeds* seeds) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    const std::vector<int32_t>& f = e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr,
+                                                               to_timing(timing, t), to_seeds(seeds, s));
     if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
     if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
   });
@@ -371,6 +444,23 @@ int pe_stream_pool_join_timed(pe_engine* e, const int64_t* ids, const int64_t* o
     to_noise(noise, nz);
     pe::TimingIn t;
     e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames, to_timing(timing, t));
+  });
+}
+
+int pe_stream_pool_join_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                               const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                               const pe_timing* timing, const pe_seeds* seeds) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_require();
+    if (!ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, n, 4096);
+    pe::NoiseIn nz;
+    to_noise(noise, nz);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames, to_timing(timing, t),
+                             to_seeds(seeds, s));
   });
 }
 
@@ -987,11 +1077,13 @@ pe_engine* pe_group_engine(pe_group* g, int32_t i) {
 
 }  // extern "C"
 
-// pe_group_synthesize_batch(_scaled): scales = one triple for the whole call, or (per_utt) [batch][3]
+// pe_group_synthesize_batch(_scaled, _seeded): scales = one triple for the whole call, or (per_utt) [batch][3]; seeds = the
+// caller's pe_seeds or null
 static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
-                            bool per_utt, const int64_t* sids, pe_result* result) {
+                            bool per_utt, const int64_t* sids, pe_result* result, const pe_seeds* seeds = nullptr) {
   return guard([&] {
     if (!g || !ids || !offsets || (!per_utt && !scales)) throw std::runtime_error("null argument");
+    if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
     const int n = (int)g->eng.size();
     if (per_utt) check_scales(scales, batch, (int64_t)4096 * n);
     // the offsets are the caller's: check them BEFORE they size a copy (the same rules and messages as Engine::upload,
@@ -1036,6 +1128,8 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
     struct Work {
       std::vector<int64_t> ids, off, sids;
       std::vector<float> scales;                // [shard][3] (per-utterance calls)
+      std::vector<uint64_t> seed;               // [shard] (seeded calls), and whether each utterance uses its seed
+      std::vector<uint8_t> use;
       pe_result res{};
       int rc = 0;
       std::string err;
@@ -1050,6 +1144,10 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
         w.off.push_back((int64_t)w.ids.size());
         if (sids) w.sids.push_back(sids[u]);
         if (per_utt) w.scales.insert(w.scales.end(), scales + (size_t)u * 3, scales + (size_t)u * 3 + 3);
+        if (seeds) {
+          w.seed.push_back(seeds->seed[u]);
+          w.use.push_back(seeds->use ? seeds->use[u] : (uint8_t)1);
+        }
       }
     }
     // a shard = upload + device pipeline + int16 PCM to the host; the float waveform stays on the device (the group
@@ -1059,8 +1157,9 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
       if (shard[i].empty()) return;
       try {
         pe::Engine* e = g->eng[i]->eng;
+        const pe::SeedsIn sd{w.seed.data(), w.use.data()};
         e->upload(w.ids.data(), w.off.data(), (int)shard[i].size(), per_utt ? w.scales.data() : scales,
-                  sids ? w.sids.data() : nullptr, nullptr, per_utt);
+                  sids ? w.sids.data() : nullptr, nullptr, per_utt, nullptr, seeds ? &sd : nullptr);
         e->run();
         e->download(false, true);
         fill_result(g->eng[i], &w.res, 0.0);
@@ -1131,6 +1230,11 @@ int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int6
   return group_synthesize(g, ids, offsets, batch, scales, true, sids, result);
 }
 
+int pe_group_synthesize_batch_seeded(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                     const float* scales, const int64_t* sids, pe_result* result, const pe_seeds* seeds) {
+  return group_synthesize(g, ids, offsets, batch, scales, true, sids, result, seeds);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // pe_coalescer_*: concurrent single-utterance requests of many caller threads as batched engine calls (include/piper_hip.h)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1143,6 +1247,7 @@ int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int6
 struct pe_coalescer {
   struct Req {
     const int64_t* ids; int64_t n; float scales[3]; int64_t sid;
+    bool seeded = false; uint64_t seed = 0;      // pe_coalescer_synthesize_seeded with a seed
     int16_t* pcm = nullptr; int64_t samples = 0; int32_t frames = 0; double secs = 0; int32_t batch = 0;
     int state = 0;            // 0 queued, 1 taken by a leader, 2 done, 3 failed
     std::string err;
@@ -1202,6 +1307,12 @@ int pe_coalescer_stats(pe_coalescer* c, int64_t* engine_calls, int64_t* requests
 
 int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                             int16_t** pcm, int64_t* n_samples, int32_t* frames, double* infer_seconds, int32_t* batch_size) {
+  return pe_coalescer_synthesize_seeded(c, ids, n_ids, scales, sid, nullptr, pcm, n_samples, frames, infer_seconds, batch_size);
+}
+
+int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                                   const uint64_t* seed, int16_t** pcm, int64_t* n_samples, int32_t* frames,
+                                   double* infer_seconds, int32_t* batch_size) {
   return guard([&] {
     if (!c || !ids || !scales || !pcm || !n_samples) throw std::runtime_error("null argument");
     if (n_ids <= 0) throw std::runtime_error("empty phoneme id sequence");
@@ -1210,6 +1321,7 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
     pe_coalescer::Req me;
     me.ids = ids; me.n = n_ids; me.sid = sid;
     memcpy(me.scales, scales, sizeof(me.scales));
+    if (seed) { me.seeded = true; me.seed = *seed; }
     std::unique_lock<std::mutex> lk(c->m);
     // Whatever ends this call -- also an exception between taking the lead and the engine call (std::bad_alloc of the
     // batch vector) -- `me` must leave the queue, a lead must be given up, and requests this thread had taken must fail
@@ -1266,7 +1378,14 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
         try {
           std::vector<int64_t> cat, off{0}, sids;
           std::vector<float> sc;
+          // seeded and unseeded requests share the call: one key and one flag per request (no seeded request: the plain call)
+          std::vector<uint64_t> seed;
+          std::vector<uint8_t> use;
+          bool any_seed = false;
           for (auto* r : take) {
+            seed.push_back(r->seed);
+            use.push_back(r->seeded ? 1 : 0);
+            any_seed = any_seed || r->seeded;
             cat.insert(cat.end(), r->ids, r->ids + r->n);
             off.push_back((int64_t)cat.size());
             sids.push_back(r->sid < 0 ? 0 : r->sid);
@@ -1274,7 +1393,9 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
           }
           const auto t0 = std::chrono::steady_clock::now();
           pe::Engine* e = c->eng->eng;
-          e->upload(cat.data(), off.data(), (int)take.size(), sc.data(), sids.data(), nullptr, true);   // one triple per request
+          const pe::SeedsIn sd{seed.data(), use.data()};
+          e->upload(cat.data(), off.data(), (int)take.size(), sc.data(), sids.data(), nullptr, true, nullptr,
+                    any_seed ? &sd : nullptr);            // one triple per request
           e->run();
           e->download(false, true);
           const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

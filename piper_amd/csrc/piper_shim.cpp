@@ -378,6 +378,20 @@ static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) 
   }
 }
 
+// pe_upload, or with SynthesisConfig::seed pe_upload_seeded: utterance k of the call gets seed + first + k (wrapping)
+static int upload_utterances(pe_engine* engine, const PhonemeId* ids, const int64_t* offsets, int32_t batch, const float scales[3],
+                             const int64_t* sids, const std::optional<uint64_t>& seed, uint64_t first) {
+  if (!seed) return pe_upload(engine, ids, offsets, batch, scales, sids, nullptr);
+  std::vector<float> per((size_t)batch * 3);
+  std::vector<uint64_t> keys((size_t)batch);
+  for (int32_t k = 0; k < batch; ++k) {
+    for (int j = 0; j < 3; ++j) per[(size_t)k * 3 + j] = scales[j];
+    keys[(size_t)k] = *seed + first + (uint64_t)k;
+  }
+  const pe_seeds s{keys.data(), nullptr};
+  return pe_upload_seeded(engine, ids, offsets, batch, per.data(), sids, nullptr, nullptr, &s);
+}
+
 void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisConfig, ModelSession& session,
                 std::vector<int16_t>& audioBuffer, SynthesisResult& result) {
   if (!session.engine) throw std::runtime_error("voice model is not loaded");
@@ -391,7 +405,7 @@ void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisCo
   // memory, result available in host memory = upload + device pipeline + fetch. The copy into the caller's vector
   // is outside, like the reference's conversion loops (:410-431; the int16 conversion itself runs on the GPU).
   const auto t0 = std::chrono::steady_clock::now();
-  check(pe_upload(session.engine, phonemeIds.data(), offsets, 1, scales, sids, nullptr));
+  check(upload_utterances(session.engine, phonemeIds.data(), offsets, 1, scales, sids, synthesisConfig.seed, 0));
   check(pe_run(session.engine));
   pe_result r;
   check(pe_fetch(session.engine, 0, 1, &r));
@@ -418,8 +432,8 @@ void synthesizeBatch(std::vector<std::vector<PhonemeId>>& phonemeIdLists, Synthe
     offsets.push_back((int64_t)flat.size());
   }
   const auto t0 = std::chrono::steady_clock::now();     // same span as synthesize(): upload + pipeline + fetch
-  check(pe_upload(session.engine, flat.data(), offsets.data(), nb, scales,
-                  synthesisConfig.speakerId ? sids.data() : nullptr, nullptr));
+  check(upload_utterances(session.engine, flat.data(), offsets.data(), nb, scales,
+                          synthesisConfig.speakerId ? sids.data() : nullptr, synthesisConfig.seed, 0));
   check(pe_run(session.engine));
   pe_result r;
   check(pe_fetch(session.engine, 0, 1, &r));
@@ -557,8 +571,9 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
       offsets.push_back((int64_t)flat.size());
     }
     const auto t0 = std::chrono::steady_clock::now();
-    check(pe_upload(voice.session.engine, flat.data(), offsets.data(), (int32_t)(g.p1 - g.p0), scales,
-                    sc.speakerId ? sids.data() : nullptr, nullptr));
+    // (with SynthesisConfig::seed phrase k of the whole text gets seed + k, whatever group it lands in)
+    check(upload_utterances(voice.session.engine, flat.data(), offsets.data(), (int32_t)(g.p1 - g.p0), scales,
+                            sc.speakerId ? sids.data() : nullptr, sc.seed, (uint64_t)g.p0));
     check(pe_run(voice.session.engine));
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   };

@@ -83,6 +83,25 @@ class Timing:
         return C.byref(t)
 
 
+def pack_seeds(seeds, batch: int, keep: list):
+    """The C struct (by reference) for per-utterance noise seeds (include/piper_hip.h: pe_seeds), or None for ``seeds`` None.
+    ``seeds``: one entry per utterance, an int (any value, taken modulo 2^64) or None for an utterance that draws from the
+    engine's own stream. The arrays it points to are appended to ``keep``."""
+    if seeds is None:
+        return None
+    seeds = list(seeds)
+    if len(seeds) != batch:
+        raise ValueError(f"seeds: {len(seeds)} entries for {batch} utterances")
+    val = np.array([0 if s is None else int(s) % (1 << 64) for s in seeds], np.uint64).reshape(-1)
+    use = np.array([0 if s is None else 1 for s in seeds], np.uint8).reshape(-1)
+    val, use = np.ascontiguousarray(val), np.ascontiguousarray(use)
+    s = L.PeSeeds()
+    s.seed = val.ctypes.data_as(C.POINTER(C.c_uint64))
+    s.use = use.ctypes.data_as(C.POINTER(C.c_uint8))
+    keep.extend([val, use, s])
+    return C.byref(s)
+
+
 def _tiled_scales(scales, batch: int):
     per = per_utterance_scales(scales, batch)
     if per is None:
@@ -196,17 +215,22 @@ class Engine:
 
     # ---- API
     def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-                         timing: Optional[Timing] = None) -> Synthesis:
+                         timing: Optional[Timing] = None, seeds=None) -> Synthesis:
         """``scales``: one (noise_scale, length_scale, noise_w) triple for every utterance, or a (B, 3) array with one
-        triple per utterance (pe_synthesize_batch_scaled). ``timing``: a ``Timing`` plan (pe_synthesize_batch_timed)."""
+        triple per utterance (pe_synthesize_batch_scaled). ``timing``: a ``Timing`` plan (pe_synthesize_batch_timed).
+        ``seeds``: one int or None per utterance (pe_synthesize_batch_seeded): a seeded utterance's noise, and with it its
+        audio, depends on its seed alone -- not on the handle, the calls before or the rest of the batch."""
         ids, offs = self._pack(id_lists)
-        per = per_utterance_scales(scales, len(id_lists)) if timing is None else _tiled_scales(scales, len(id_lists))
+        plain = timing is None and seeds is None
+        per = per_utterance_scales(scales, len(id_lists)) if plain else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_synthesize_batch if per is None else self._lib.pe_synthesize_batch_scaled
         keep: list = [per]
         extra = ()
         if timing is not None:
             entry, extra = self._lib.pe_synthesize_batch_timed, (timing.pack(id_lists, keep),)
+        if seeds is not None:
+            entry, extra = self._lib.pe_synthesize_batch_seeded, (extra[0] if extra else None, pack_seeds(seeds, len(id_lists), keep))
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -219,23 +243,28 @@ class Engine:
             len(id_lists), sc, sid_arr, nz, C.byref(res), *extra))
         return self._collect(res)
 
-    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid=None, noise_w=None, noise_z=None) -> Synthesis:
+    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid=None, noise_w=None, noise_z=None, seed=None) -> Synthesis:
         nw = None if noise_w is None else np.asarray(noise_w, np.float32)[None]
         nz = None if noise_z is None else np.asarray(noise_z, np.float32)[None]
-        return self.synthesize_batch([ids], scales, None if sid is None else [sid], nw, nz)
+        return self.synthesize_batch([ids], scales, None if sid is None else [sid], nw, nz,
+                                     seeds=None if seed is None else [seed])
 
     def upload(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-               timing: Optional[Timing] = None):
+               timing: Optional[Timing] = None, seeds=None):
         """``scales``: one triple, or a (B, 3) array of per-utterance triples (pe_upload_scaled). ``timing``: a ``Timing``
-        plan (pe_upload_timed); every ``run()`` on the upload follows it."""
+        plan (pe_upload_timed); every ``run()`` on the upload follows it. ``seeds``: one int or None per utterance
+        (pe_upload_seeded); every ``run()`` on the upload draws the same noise again."""
         ids, offs = self._pack(id_lists)
-        per = per_utterance_scales(scales, len(id_lists)) if timing is None else _tiled_scales(scales, len(id_lists))
+        plain = timing is None and seeds is None
+        per = per_utterance_scales(scales, len(id_lists)) if plain else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_upload if per is None else self._lib.pe_upload_scaled
         keep: list = [per]
         extra = ()
         if timing is not None:
             entry, extra = self._lib.pe_upload_timed, (timing.pack(id_lists, keep),)
+        if seeds is not None:
+            entry, extra = self._lib.pe_upload_seeded, (extra[0] if extra else None, pack_seeds(seeds, len(id_lists), keep))
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -285,11 +314,11 @@ class Engine:
         self._check(self._lib.pe_fetch(self._h, int(want_audio), int(want_pcm), C.byref(res)))
         return res
 
-    def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None):
+    def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None, seed=None):
         """Generator over (float_audio, int16_pcm) chunks of one utterance: encoder/flow once, then the
         vocoder on exact-halo windows of `chunk_frames` frames (reference default 45). Concatenating
         the float chunks gives exactly the unchunked waveform; pcm is peak-normalised per chunk, or follows
-        the level set by ``set_stream_gain``."""
+        the level set by ``set_stream_gain``. ``seed``: the utterance's noise seed (pe_stream_begin_seeded)."""
         ids_np = np.ascontiguousarray(ids, np.int64)
         sc = (C.c_float * 3)(*[float(s) for s in scales])
         keep: list = []
@@ -297,8 +326,11 @@ class Engine:
         nz = None if noise_z is None else np.asarray(noise_z, np.float32)[None]
         nref = self._noise(nw, nz, keep)
         frames, halo = C.c_int32(), C.c_int32()
-        self._check(self._lib.pe_stream_begin(self._h, ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, sc,
-                                              -1 if sid is None else int(sid), nref, C.byref(frames), C.byref(halo)))
+        entry, extra = self._lib.pe_stream_begin, ()
+        if seed is not None:
+            entry, extra = self._lib.pe_stream_begin_seeded, (None, pack_seeds([seed], 1, keep))
+        self._check(entry(self._h, ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, sc,
+                          -1 if sid is None else int(sid), nref, C.byref(frames), C.byref(halo), *extra))
         self.stream_frames, self.stream_halo = frames.value, halo.value
         while True:
             a, p, n = C.POINTER(C.c_float)(), C.POINTER(C.c_int16)(), C.c_int64()
@@ -308,14 +340,14 @@ class Engine:
             yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
 
     def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
-                     want_audio: bool = True, timing: Optional[Timing] = None):
+                     want_audio: bool = True, timing: Optional[Timing] = None, seeds=None):
         """Generator over the chunks of B utterances streamed in lock step (pe_stream_begin_batch / pe_stream_next_batch):
         text encoder, durations and flow for the whole batch once, then one batched vocoder pass per chunk. Every item
         is a list of B ``(float chunk or None, int16 chunk)`` pairs -- empty arrays for utterances that are finished;
         chunk k of utterance b is what ``stream`` yields for that utterance alone, in every ``set_stream_gain`` mode (each
         utterance carries its own level). ``chunk_frames``: an int, or a
-        callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales`` and ``timing`` as in
-        ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
+        callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales``, ``timing`` and
+        ``seeds`` as in ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
         B = len(id_lists)
         ids, offs = self._pack(id_lists)
         per = per_utterance_scales(scales, B)
@@ -332,6 +364,8 @@ class Engine:
         entry, extra = self._lib.pe_stream_begin_batch, ()
         if timing is not None:
             entry, extra = self._lib.pe_stream_begin_batch_timed, (timing.pack(id_lists, keep),)
+        if seeds is not None:
+            entry, extra = self._lib.pe_stream_begin_batch_seeded, (extra[0] if extra else None, pack_seeds(seeds, B, keep))
         self._check(entry(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, frames.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -753,11 +787,11 @@ class StreamPool:
         return [int(s) for s in np.flatnonzero(self._state()[2] == 0)]
 
     def join(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-             timing: Optional[Timing] = None) -> list:
+             timing: Optional[Timing] = None, seeds=None) -> list:
         """Begin the utterances of ``id_lists`` and give each a free slot, lowest first, in input order; returns the slots.
         ``scales``: one triple, or a (B, 3) array of per-utterance triples. Fails as a whole, the pool unchanged, when
         there are too few free slots or an utterance has more than ``max_frames`` frames. ``timing``: a ``Timing`` plan
-        (pe_stream_pool_join_timed)."""
+        (pe_stream_pool_join_timed). ``seeds``: one int or None per newcomer (pe_stream_pool_join_seeded)."""
         eng, n = self._eng, len(id_lists)
         ids, offs = eng._pack(id_lists)
         per = per_utterance_scales(scales, n)
@@ -774,6 +808,8 @@ class StreamPool:
         entry, extra = eng._lib.pe_stream_pool_join, ()
         if timing is not None:
             entry, extra = eng._lib.pe_stream_pool_join_timed, (timing.pack(id_lists, keep),)
+        if seeds is not None:
+            entry, extra = eng._lib.pe_stream_pool_join_seeded, (extra[0] if extra else None, pack_seeds(seeds, n, keep))
         eng._check(entry(
             eng._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, slot_of.ctypes.data_as(C.POINTER(C.c_int32)),

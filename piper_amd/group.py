@@ -55,22 +55,33 @@ class EngineGroup:
             self.engine(i).set_loudness(target_lufs, ceiling_db, true_peak=true_peak, limiter=limiter, limiter_ms=limiter_ms)
 
     def synthesize_batch(self, id_lists: Sequence[Sequence[int]], scales=(0.667, 1.0, 0.8),
-                         sids: Optional[Sequence[int]] = None) -> Synthesis:
-        """``scales``: one triple for every utterance, or a (B, 3) array with one triple per utterance."""
+                         sids: Optional[Sequence[int]] = None, seeds=None) -> Synthesis:
+        """``scales``: one triple for every utterance, or a (B, 3) array with one triple per utterance. ``seeds``: one int
+        or None per utterance (pe_group_synthesize_batch_seeded): each member takes its utterances' seeds along with
+        their ids, so a seeded utterance's audio does not depend on the member that ran it."""
         if len(id_lists) == 0:
             raise EngineError("empty batch")
         per = per_utterance_scales(scales, len(id_lists))
+        keep: list = []
+        extra = ()
+        if seeds is not None:
+            from .engine import pack_seeds
+            if per is None:
+                per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (len(id_lists), 1)))
+            extra = (pack_seeds(seeds, len(id_lists), keep),)
         ids = np.concatenate([np.asarray(x, dtype=np.int64) for x in id_lists])
         off = np.zeros(len(id_lists) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(x) for x in id_lists])
         sc = np.asarray(scales, dtype=np.float32) if per is None else per
         entry = self._lib.pe_group_synthesize_batch if per is None else self._lib.pe_group_synthesize_batch_scaled
+        if seeds is not None:
+            entry = self._lib.pe_group_synthesize_batch_seeded
         sid = None if sids is None else np.ascontiguousarray(sids, dtype=np.int64)
         i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
         res = L.PeResult()
         self._check(entry(
             self._h, ids.ctypes.data_as(i64p), off.ctypes.data_as(i64p), len(id_lists), sc.ctypes.data_as(f32p),
-            None if sid is None else sid.ctypes.data_as(i64p), C.byref(res)))
+            None if sid is None else sid.ctypes.data_as(i64p), C.byref(res), *extra))
         B = res.batch
         so = np.ctypeslib.as_array(res.sample_offsets, shape=(B + 1,)).copy()
         frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
@@ -112,14 +123,17 @@ class Coalescer:
         if create(engine._h, int(max_batch), int(max_wait_us), C.byref(self._h)):
             raise EngineError(self._lib.pe_last_error().decode(errors="replace"))
 
-    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid: Optional[int] = None):
-        """-> (int16 PCM, frames, seconds of the engine call that served the request, utterances in that call)"""
+    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid: Optional[int] = None, seed: Optional[int] = None):
+        """-> (int16 PCM, frames, seconds of the engine call that served the request, utterances in that call).
+        ``seed``: the request's noise seed (pe_coalescer_synthesize_seeded): it gets the noise of its own seeded B=1 call
+        whatever it is merged with; None: the engine's own stream."""
         a = np.ascontiguousarray(ids, dtype=np.int64)
         sc = (C.c_float * 3)(*[float(v) for v in scales])
         pcm, n, fr, secs, bs = C.POINTER(C.c_int16)(), C.c_int64(), C.c_int32(), C.c_double(), C.c_int32()
-        rc = self._lib.pe_coalescer_synthesize(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, sc,
-                                               -1 if sid is None else int(sid), C.byref(pcm), C.byref(n), C.byref(fr),
-                                               C.byref(secs), C.byref(bs))
+        sd = None if seed is None else C.byref(C.c_uint64(int(seed) % (1 << 64)))
+        rc = self._lib.pe_coalescer_synthesize_seeded(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, sc,
+                                                      -1 if sid is None else int(sid), sd, C.byref(pcm), C.byref(n),
+                                                      C.byref(fr), C.byref(secs), C.byref(bs))
         if rc:
             raise EngineError(self._lib.pe_last_error().decode(errors="replace"))
         try:

@@ -8,7 +8,10 @@ it belongs to still runs as one call (one scale triple per utterance). ``--outpu
 resampled on the GPU from ``--sample-rate`` (the voice's own rate); the WAV headers then say R. A line may also carry
 ``durations`` (one int per id: >= 0 that id's frames, -1 predicted), ``rate`` (one multiplier per id) and / or
 ``target_seconds`` (the utterance's exact length, converted to frames with ``--sample-rate`` and the voice's hop) (new): a
-group with such a line runs as one timed call; a group without is the call it always was.
+group with such a line runs as one timed call; a group without is the call it always was. ``--seed N`` gives the utterance
+of line k (the index that names its WAV) the noise seed ``N + k``, and a line's own ``seed`` overrides it (new): a seeded
+line's audio depends on the voice, the line and its seed alone -- not on ``--batch``, the lines around it or the run -- and
+lines without a seed draw from the engine's own stream in the same call.
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -75,6 +78,22 @@ def read_timing(lines: Iterable[str]) -> List[Optional[dict]]:
     return out
 
 
+def read_seeds(lines: Iterable[str], base: Optional[int]) -> List[Optional[int]]:
+    """Per non-empty line (the order of read_utterances): its noise seed modulo 2^64 -- the line's own ``seed``, else
+    ``base`` + the line's index -- or None where there is neither."""
+    out: List[Optional[int]] = []
+    for i, line in enumerate(lines):
+        line = line.strip()
+        if not line:
+            continue
+        obj = json.loads(line)
+        if obj.get("seed") is not None:
+            out.append(int(obj["seed"]) % (1 << 64))
+        else:
+            out.append(None if base is None else (int(base) + i) % (1 << 64))
+    return out
+
+
 def group_timing(own: List[Optional[dict]], native_rate: int, hop: int) -> Optional[Timing]:
     """The plan of a group of lines, or None when no line of it carries a timing key."""
     if all(t is None for t in own):
@@ -113,7 +132,8 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     parser.add_argument("--length-scale", type=float, default=1.0)
     parser.add_argument("--batch", type=int, default=1, help="utterances per GPU call")
     parser.add_argument("--device", type=int, default=0)
-    parser.add_argument("--seed", type=int, default=None, help="seed of the engine's noise generator")
+    parser.add_argument("--seed", type=int, default=None,
+                        help="noise seed: line k gets seed + k, whatever --batch; a line's own \"seed\" overrides it")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG)
 
@@ -121,8 +141,6 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     out_dir.mkdir(parents=True, exist_ok=True)
     engine = Engine(onnx_path=str(args.model), device=args.device, lib=lib)
     _LOGGER.info("Loaded model from %s", args.model)
-    if args.seed is not None:
-        engine.set_seed(args.seed)
     wav_rate = args.sample_rate
     if args.output_rate:
         engine.set_output_rate(args.output_rate, native=args.sample_rate)
@@ -137,6 +155,7 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     utts = read_utterances(lines)
     line_scales = read_scales(lines, scales)
     line_timing = read_timing(lines)
+    line_seeds = read_seeds(lines, args.seed)
     step = max(1, args.batch)
     for k in range(0, len(utts), step):
         group = utts[k:k + step]
@@ -147,6 +166,9 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
         t0 = time.perf_counter()
         timing = group_timing(line_timing[k:k + step], args.sample_rate, engine.hop)
         extra = {} if timing is None else {"timing": timing}
+        seeds = line_seeds[k:k + step]
+        if any(s is not None for s in seeds):
+            extra["seeds"] = seeds
         res = engine.synthesize_batch([u[1] for u in group], call_scales,
                                       sids=None if all(s is None for s in sids) else [s or 0 for s in sids], **extra)
         infer_sec = time.perf_counter() - t0

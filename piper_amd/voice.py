@@ -120,27 +120,30 @@ class PiperVoice:
 
     def synthesize(self, text: str, wav_file: wave.Wave_write, speaker_id: Optional[int] = None,
                    length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
-                   noise_w: Optional[float] = None, sentence_silence: float = 0.0):
-        """Synthesize WAV audio from text."""
+                   noise_w: Optional[float] = None, sentence_silence: float = 0.0, seed: Optional[int] = None):
+        """Synthesize WAV audio from text. ``seed``: as in synthesize_stream_raw."""
         wav_file.setframerate(self.sample_rate)
         wav_file.setsampwidth(2)
         wav_file.setnchannels(1)
         for audio_bytes in self.synthesize_stream_raw(text, speaker_id=speaker_id, length_scale=length_scale,
                                                       noise_scale=noise_scale, noise_w=noise_w,
-                                                      sentence_silence=sentence_silence):
+                                                      sentence_silence=sentence_silence, seed=seed):
             wav_file.writeframes(audio_bytes)
 
     def synthesize_stream_raw(self, text: str, speaker_id: Optional[int] = None,
                               length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
-                              noise_w: Optional[float] = None, sentence_silence: float = 0.0) -> Iterable[bytes]:
-        """Synthesize raw audio per sentence from text."""
+                              noise_w: Optional[float] = None, sentence_silence: float = 0.0,
+                              seed: Optional[int] = None) -> Iterable[bytes]:
+        """Synthesize raw audio per sentence from text. ``seed``: sentence k of the text gets the noise seed ``seed + k``
+        (wrapping at 2^64), so that the same text with the same settings gives the same audio on any handle."""
         sentence_phonemes = self.phonemize(text)
         num_silence_samples = int(sentence_silence * self.sample_rate)
         silence_bytes = bytes(num_silence_samples * 2)
-        for phonemes in sentence_phonemes:
+        for k, phonemes in enumerate(sentence_phonemes):
             phoneme_ids = self.phonemes_to_ids(phonemes)
             yield self.synthesize_ids_to_raw(phoneme_ids, speaker_id=speaker_id, length_scale=length_scale,
-                                             noise_scale=noise_scale, noise_w=noise_w) + silence_bytes
+                                             noise_scale=noise_scale, noise_w=noise_w,
+                                             seed=None if seed is None else (int(seed) + k) % (1 << 64)) + silence_bytes
 
     def _scales(self, length_scale, noise_scale, noise_w):
         if length_scale is None:
@@ -173,31 +176,35 @@ class PiperVoice:
     def synthesize_ids_to_raw(self, phoneme_ids: List[int], speaker_id: Optional[int] = None,
                               length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                               noise_w: Optional[float] = None, durations=None, rate=None,
-                              target_seconds: Optional[float] = None) -> bytes:
+                              target_seconds: Optional[float] = None, seed: Optional[int] = None) -> bytes:
         """Synthesize raw 16-bit mono audio from phoneme ids (voice.py:140-185). New, all optional (Engine's ``Timing``):
         ``durations`` -- one int per id, >= 0 = that id lasts exactly so many frames, -1 = predicted; ``rate`` -- one
         multiplier of the predicted duration per id; ``target_seconds`` -- the utterance lasts
-        round(seconds * native rate / hop) frames exactly (the byte count follows from the output rate)."""
+        round(seconds * native rate / hop) frames exactly (the byte count follows from the output rate); ``seed`` -- the
+        utterance's noise seed (Engine's ``seeds``): its audio then depends on the voice, the ids, the settings and the seed
+        alone, not on what the handle served before."""
         timing = self._timing(None if durations is None else [durations], None if rate is None else [rate],
                               None if target_seconds is None else [target_seconds])
-        if timing is None:
+        if timing is None and seed is None:
             r = self.session.synthesize(phoneme_ids, self._scales(length_scale, noise_scale, noise_w),
                                         sid=self._speaker(speaker_id))
         else:
             sid = self._speaker(speaker_id)
             r = self.session.synthesize_batch([phoneme_ids], self._scales(length_scale, noise_scale, noise_w),
-                                              sids=None if sid is None else [sid], timing=timing)
+                                              sids=None if sid is None else [sid], timing=timing,
+                                              seeds=None if seed is None else [seed])
         return r.pcm[0].tobytes()
 
     def synthesize_ids_batch_to_raw(self, phoneme_id_lists: List[List[int]], speaker_ids=None,
                                     length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                                     noise_w: Optional[float] = None, durations=None, rate=None,
-                                    target_seconds=None) -> List[bytes]:
+                                    target_seconds=None, seeds=None) -> List[bytes]:
         """Batched extension: several utterances in one GPU call, each identical to its own
         synthesize_ids_to_raw() (same noise stream aside). ``length_scale`` / ``noise_scale`` / ``noise_w`` may each be
         one value for every utterance or a list with one value per utterance (None entries: the voice's default).
         ``durations`` / ``rate`` / ``target_seconds``: lists with one entry per utterance as in synthesize_ids_to_raw
-        (None entries: nothing of that kind for that utterance)."""
+        (None entries: nothing of that kind for that utterance). ``seeds``: one noise seed or None per utterance; a seeded
+        utterance is then identical to its own seeded synthesize_ids_to_raw(), noise included."""
         sids = None
         n = len(phoneme_id_lists)
         if self.config.num_speakers > 1:
@@ -214,8 +221,8 @@ class PiperVoice:
         else:
             scales = self._scales(length_scale, noise_scale, noise_w)
         timing = self._timing(durations, rate, target_seconds)
-        if timing is None:
+        if timing is None and seeds is None:
             r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
         else:
-            r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids, timing=timing)
+            r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids, timing=timing, seeds=seeds)
         return [p.tobytes() for p in r.pcm]
