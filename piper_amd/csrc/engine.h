@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "pe_rt.h"
+#include "engine_buffers.h"
 #include "kernels/params.h"
 #include "policy.h"
 #include "weights.h"
@@ -263,8 +264,8 @@ class Engine {
 
   int batch() const { return B_; }
   const std::vector<int64_t>& sample_offsets() { finish_run(); return sample_off_; }
-  const float* audio_host() const { return h_audio_; }
-  const int16_t* pcm_host() const { return pcm_zc_live_ ? h_pcm_zc_ : h_pcm_; }
+  const float* audio_host() const { return h_audio_.get(); }
+  const int16_t* pcm_host() const { return pcm_zc_live_ ? h_pcm_zc_.get() : h_pcm_.get(); }
   const std::vector<int32_t>& durations_host();   // concatenated per id, same offsets as ids
   const std::vector<int32_t>& frames_host() { finish_run(); return frames_h_; }
   void debug_tensor(const std::string& name, int b, std::vector<float>& out, int* rows, int* cols);
@@ -312,6 +313,12 @@ class Engine {
   PackedConv pack_matrix(const std::vector<float>& W, int rows, int Cin, int ntaps,
                          const std::vector<float>* bias, int nbias, int dil, int padl, bool gate, int split);
   DdsW load_dds(const WeightSet& ws, const std::string& prefix);
+  // A side buffer (engine_buffers.h) replaced by one of exactly n elements, then filled. idle: first wait for the stream
+  // and, where the buffer exists -- its address may sit inside a captured graph --, drop the graphs; false: the caller has
+  // seen to both. what / what_bytes: Buffer::grow's out-of-memory text. (engine_internal.h)
+  enum Fill { FILL_NONE, FILL_ZERO, FILL_POISON, FILL_POISON_OR_ZERO };      // POISON: under LaunchPolicy::debug_poison only
+  template <class Buf>
+  void side_alloc(Buf& b, size_t n, bool idle, Fill fill, const char* what = nullptr, size_t what_bytes = 0);
   void ensure_stage_a(int B, int Tmax);
   void ensure_stage_b(int Fmax, int batch = 0);
 
@@ -365,7 +372,7 @@ class Engine {
   // fused path ping-pongs x_ / y_: lngemm4_kernel must not write LN(y) over the residual other parts still read)
   const float* pack_ffn1(const WeightSet& ws, const std::string& wname);
   const float* pack_ffn2(const WeightSet& ws, const std::string& wname);
-  float* ffn_parts_ = nullptr;
+  DevBuf<float> ffn_parts_;
   bool stage_a_ffn_fused() const;
   float* stage_a_enc_out() const;
   const float* w4_of(const float* w16) const { auto it = w4_of_.find(w16); return it == w4_of_.end() ? nullptr : it->second; }
@@ -552,7 +559,7 @@ class Engine {
   // the plan. A timed call runs as A, frame-count read-back, B; it neither reads nor feeds the speculative sizing.
   bool plan_on_ = false, plan_skip_ = false;      // skip: every id is forced, stage A leaves the duration predictor out
   int* d_plan_ = nullptr; float* plan_w_ = nullptr;
-  int* h_plan_ = nullptr; size_t h_plan_cap_ = 0;
+  PinBuf<int> h_plan_;
   // throws the refusal; returns whether every id of the call is forced
   static bool check_timing(const TimingIn& t, const int64_t* offsets, int B);
   void plan_params(PlanP& pp, const DurP& dp) const;
@@ -571,8 +578,7 @@ class Engine {
   bool capB_exact_ = false;      // stage B was last sized for exactly one call (memory pressure): it stays while calls fit
   size_t ws_budget_ = 0;             // bytes a stage's workspace may take (a third of the device's memory)
   size_t ws_budget();
-  char* wsA_ = nullptr; size_t wsA_bytes_ = 0;
-  char* wsB_ = nullptr; size_t wsB_bytes_ = 0;
+  DevBuf<char> wsA_, wsB_;
   int *d_ids_ = nullptr, *d_tlens_ = nullptr, *d_sids_ = nullptr, *d_dur_ = nullptr, *d_cum_ = nullptr,
       *d_frames_ = nullptr;
   float* d_scales_ = nullptr;        // [B][3] per-utterance {noise_scale, length_scale, noise_w}, part of the input block
@@ -590,7 +596,7 @@ class Engine {
   // The small inputs of a call -- {seed, call}, seeds, lengths, speaker ids, scales, phoneme ids -- are one contiguous block in the stage-A
   // workspace (d_in_) mirrored by a pinned host block (h_in_): upload() fills the host block and enqueues ONE copy, no
   // synchronisation (the pinned block outlives the copy; the call's final synchronisation covers it)
-  char* d_in_ = nullptr; char* h_in_ = nullptr; size_t in_bytes_ = 0, h_in_cap_ = 0;
+  char* d_in_ = nullptr; PinBuf<char> h_in_; size_t in_bytes_ = 0;
   // short calls: no copy at all -- embed_kernel reads the pinned block in place (policy.h: ids_from_host)
   bool ids_zc_ = false;
   unsigned long long upload_serial_ = 0;
@@ -610,7 +616,7 @@ class Engine {
   float* hb_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipStream_t ls_ = nullptr;       // stream conv()/layer launches go to
   // per-resblock buffers of the grouped sibling schedule (one-utterance calls)
-  float* side_[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf<float> side_[9];
   size_t side_floats_ = 0;
   float* zwin_ = nullptr;          // streaming: current window of z, [C][Fs]
   int* d_win_ = nullptr;           // streaming: {start, length} of the window in frames
@@ -625,19 +631,18 @@ class Engine {
   struct ChunkRows {
     char stage;                                    // dispatch_stage's letter, first character of the graph keys
     int cap = 0;                                   // rows the blocks are sized for (even)
-    int* host = nullptr; int* dev = nullptr;       // state blocks
-    int* gctl = nullptr; int* gdev = nullptr;      // gain control (pinned) and gain state (device) blocks
+    PinBuf<int> host; DevBuf<int> dev;             // state blocks
+    PinBuf<int> gctl; DevBuf<int> gdev;            // gain control (pinned) and gain state (device) blocks
     std::vector<char> gfirst;                      // per row: nothing delivered yet (its level starts afresh)
     std::vector<int32_t> pos;                      // frames delivered per row; its size is the number of rows
     std::vector<int64_t> off;                      // sample offsets of the current chunk
-    int16_t* pcm = nullptr; float* audio = nullptr;     // pinned host output of the current chunk
-    size_t pcm_cap = 0, audio_cap = 0;
+    PinBuf<int16_t> pcm; PinBuf<float> audio;      // pinned host output of the current chunk
     int wg = 0;                                    // window bucket of the current chunk
     // what the stage reads the rows from: the latents [row][C][src_cs] and the decoder's conditioning rows (null: cond_)
     const float* src = nullptr; long src_bs = 0; int src_cs = 0;
     const float* cond = nullptr; int cond_bs = 0;
   };
-  void rows_free(ChunkRows& r);
+  void rows_free(ChunkRows& r);                    // the blocks released, the state that pointed into them reset
   // one chunk of every row that has frames left (live: null = all rows are) and the positions advanced: row b goes on by
   // per_row[b] where that is > 0, else by `chunk`, at most `clamp` frames. False, with nothing run, when no row delivers.
   bool rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live, int chunk, const int32_t* per_row, int clamp,
@@ -655,8 +660,7 @@ class Engine {
   int gain_mode_ = GAIN_CHUNK, gain_ramp_ = 0;
   float gain_peak_ = 0.f;
   float s_gain_r_ = 0.01f; bool s_gain_first_ = true;
-  void gain_blocks_alloc(int cap, int** ctl, int** dev);
-  void gain_blocks_free(int** ctl, int** dev);
+  void gain_blocks_alloc(ChunkRows& r, int cap);   // r's gain blocks for cap rows, zero-filled
   void gain_prepare(int* ctl, int cap, const std::vector<char>& first, int n);
   // after a chunk call over n rows with sample offsets off[n + 1]: the report, and the flags of the rows that delivered.
   // Default mode: the peaks stay on the device (`peaks`, one word per row) and are fetched when the report is asked for.
@@ -675,8 +679,8 @@ class Engine {
   // join block (params.h: sj_*). Workspace growth, which frees and poisons both workspaces and drops every graph, does not
   // touch them. stream_pool_close destroys the 'P' graphs.
   int sp_slots_ = 0, sp_fcap_ = 0, sp_maxf_ = 0;           // slots, row width, max_frames
-  float* sp_z_ = nullptr; float* sp_cond_ = nullptr;
-  int* sp_join_ = nullptr;
+  DevBuf<float> sp_z_, sp_cond_;
+  PinBuf<int> sp_join_;
   std::vector<int32_t> sp_frames_, sp_live_;
   ChunkRows pool_rows_{'P'};
   void stream_pool_free();
@@ -685,18 +689,17 @@ class Engine {
   // graphs, so (re)allocating them drops every graph. So_ is the row stride of what is delivered: Ss_ at the native rate.
   bool rs_on_ = false;
   int rs_native_ = 0, rs_out_ = 0, rs_L_ = 1, rs_M_ = 1, rs_K_ = 0, rs_Tp_ = 0, rs_tile_ = RS_TILE;
-  float* rs_coef_ = nullptr;
-  float* raudio_ = nullptr; int16_t* rpcm_ = nullptr; size_t rs_buf_elems_ = 0;
+  DevBuf<float> rs_coef_;
+  DevBuf<float> raudio_; DevBuf<int16_t> rpcm_;
   long So_ = 0;
-  int* rs_host_ = nullptr; int* rs_dev_ = nullptr; int rs_cap_ = 0;
+  PinBuf<int> rs_host_; DevBuf<int> rs_dev_; int rs_cap_ = 0;
   void ensure_resample();                       // after ensure_stage_b sized the workspace
-  void rs_free();
   // rows + resample launches on B rows of x (row stride x_bs, x_cap valid-capacity per row) into raudio_; hst: the pinned
   // row block, or null with lens: whole utterances; max_out bounds every row's output count (grid)
   void issue_resample(int B, const float* x, long x_bs, const int* hst, const int* lens, long max_out, double native_samples);
   void rs_host_row(int b, int64_t n0, int64_t org, int count, int vlen);
-  const unsigned* rs_peaks() const { return reinterpret_cast<const unsigned*>(rs_dev_) + rs_o_peak(rs_cap_); }
-  const int* rs_counts() const { return rs_dev_ + rs_o_count(rs_cap_); }
+  const unsigned* rs_peaks() const { return reinterpret_cast<const unsigned*>(rs_dev_.get()) + rs_o_peak(rs_cap_); }
+  const int* rs_counts() const { return rs_dev_.get() + rs_o_count(rs_cap_); }
   // target loudness. The filter block, the segment sums [rows][ld_nseg_cap_] and the control / gain blocks (params.h: ld_*,
   // pinned host + device) are allocations of their own, outside both workspaces; their addresses are kernel arguments inside
   // the graphs, so (re)allocating them drops every graph. h / W / R follow the delivered rate, which only set_output_rate
@@ -704,9 +707,9 @@ class Engine {
   bool ld_on_ = false;
   float ld_T_ = -23.f, ld_cdb_ = -1.f;
   int ld_fs_ = 0, ld_h_ = 0, ld_W_ = 0, ld_R_ = 0;
-  double* ld_coef_ = nullptr;
-  double* ld_seg_ = nullptr; size_t ld_seg_rows_ = 0; int ld_nseg_cap_ = 0;
-  int* ld_ctl_ = nullptr; int* ld_dev_ = nullptr; int ld_cap_ = 0;
+  DevBuf<double> ld_coef_;
+  DevBuf<double> ld_seg_; size_t ld_seg_rows_ = 0; int ld_nseg_cap_ = 0;
+  PinBuf<int> ld_ctl_; DevBuf<int> ld_dev_; int ld_cap_ = 0;
   std::vector<float> ll_lufs_, ll_scale_, ll_peak_;
   std::vector<int32_t> ll_flags_;
   int ll_n_ = -1;                               // utterances of the last fetched call's report (-1: none yet)
@@ -714,8 +717,8 @@ class Engine {
   // allocations of their own next to the loudness blocks (ensure_loudness; kernel arguments inside the PEAK_TRUE graphs)
   int ld_kind_ = PEAK_SAMPLE;
   bool tp_on() const { return ld_on_ && ld_kind_ == PEAK_TRUE; }
-  float* tp_coef_ = nullptr; int tp_fs_ = 0, tp_Q_ = 0;
-  unsigned* tp_words_ = nullptr; int tp_cap_ = 0;
+  DevBuf<float> tp_coef_; int tp_fs_ = 0, tp_Q_ = 0;
+  DevBuf<unsigned> tp_words_;
   std::vector<float> ll_tpeak_;
   int ll_tn_ = 0;
   static void tp_check_rate(int fs);            // throws the refusal
@@ -725,10 +728,10 @@ class Engine {
   // the limiter's graphs). The report travels with the call's samples: download enqueues the copy in front of its wait.
   bool lim_on_ = false;
   float lim_ms_ = 5.f;
-  float* lim_h_ = nullptr; int lim_fs_ = 0, lim_W_ = 0; float lim_h_ms_ = 0.f;
-  int* lim_rep_ = nullptr; int* lim_host_ = nullptr; int lim_cap_ = 0;
+  DevBuf<float> lim_h_; int lim_fs_ = 0, lim_W_ = 0; float lim_h_ms_ = 0.f;
+  DevBuf<int> lim_rep_; PinBuf<int> lim_host_; int lim_cap_ = 0;
   // true-peak ceiling with the limiter: the per-position maxima v and the shaped floats z, [rows][lim_zv_bs_] each
-  float* lim_v_ = nullptr; float* lim_z_ = nullptr; size_t lim_zv_floats_ = 0;
+  DevBuf<float> lim_v_, lim_z_;
   // whether the run that is fetched next went through the limiter: noted where a run's graph key is formed and where the
   // stage is issued, so that a setting made between run and fetch does not relabel the report
   mutable bool run_lim_ = false;
@@ -743,14 +746,35 @@ class Engine {
     if (lim_on_) return ld_kind_ == PEAK_TRUE ? "|l4" : "|l3";
     return ld_kind_ == PEAK_TRUE ? "|l2" : "|l1";
   }
-  static void lim_check(int kind, bool on, float window_ms);      // throws the refusal
+  static void lim_check(bool on, float window_ms);                // throws the refusal
+  // the delivery chain's other refusals and small formulas, each written once (engine_deliver.cpp)
+  static void check_target(float target_lufs);
+  static void check_ceiling(float ceiling_db);
+  static void check_ceiling_kind(int kind);
+  static void check_limiter_window_at(float window_ms, int fs);   // "limiter window ... ms is more than LIM_MAXW samples at fs Hz"
+  static int check_row_lengths(const int32_t* valid, int batch, int64_t stride);      // all within [0, stride]; the largest
+  static void to_f32(const std::vector<double>& exact, float* out);                 // an f64 filter table rounded once
+  int row_block_cap() const;                    // rows of the resampler's / loudness's row blocks: even, >= 64, >= both batch capacities
+  // staging of the debug hooks: `batch` host rows of `stride` elements <-> device rows of padded stride xs, on stream_;
+  // count: elements of each row that come back (null: stride)
+  template <typename T> void rows_to_device(T* dst, long xs, const T* src, int batch, int64_t stride);
+  template <typename T> void rows_to_host(T* dst, int64_t stride, const T* src, long xs, int batch, const int32_t* count = nullptr);
+  // The limiter's launches behind the gain (kernels/limiter.h): limiter_kernel; or, with the true-peak ceiling,
+  // limiter_true_kernel, true_peak_kernel on z and pcm16_trim_kernel. Shared by issue_loudness and debug_limiter.
+  struct LimTail {
+    const float* x; long x_bs; const int* lens; int len_mul; long x_cap;      // the row view
+    int* gq; int gcap; int* ctl; int* rep; int rcap;                          // gain / control / report blocks
+    const float* h; int W;                                                    // the window
+    float* v; float* z; const float* tp_coef; int Q;                          // true-peak ceiling (v null: sample peak)
+    int16_t* pcm; int16_t* zc; float* env;                                    // outputs (zc, env: or null)
+  };
+  void issue_limiter_tail(const LimTail& t, int B, long max_n, double samples, bool profile_rows);
   void lim_upload_window(int fs);
   void lim_enqueue_report();                    // device report words -> lim_host_, on stream_
   static void loud_check_rate(int fs);          // throws the refusal
   void loud_upload_filter(int fs);              // h / W / R and the filter block for rate fs
   void loud_write_ctl();
   void ensure_loudness();                       // after ensure_stage_b sized the workspace (and ensure_resample the rows)
-  void loud_free();
   void loud_collect();                          // the pinned report of the call just synchronised -> ll_*
   // segment sums, gain and the int16 conversion of B delivered rows x (stride x_bs, lengths lens[b] * len_mul, peak words
   // `peaks`); max_n bounds every row's length (grid)
@@ -761,14 +785,14 @@ class Engine {
   unsigned* absmax_ = nullptr;
   long Ss_ = 0;
   // host pinned
-  float* h_audio_ = nullptr; size_t h_audio_cap_ = 0;
-  int16_t* h_pcm_ = nullptr; size_t h_pcm_cap_ = 0;
+  PinBuf<float> h_audio_;
+  PinBuf<int16_t> h_pcm_;
   // pcm16_kernel also writes the samples straight into this pinned host buffer (zero-copy), utterances packed back to
   // back: delivering the PCM costs no copy launches behind the graph (one per utterance before: 1.3 ms at B=64) -- the
   // call ends with one stream synchronisation.
-  int16_t* h_pcm_zc_ = nullptr; size_t h_pcm_zc_cap_ = 0;
+  PinBuf<int16_t> h_pcm_zc_;
   bool pcm_zc_live_ = false;                // the last run's PCM is in h_pcm_zc_
-  int* h_frames_ = nullptr;
+  PinBuf<int> h_frames_;
 
   // profiling
   bool prof_on_ = false;

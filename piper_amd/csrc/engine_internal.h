@@ -1,4 +1,6 @@
 // Internals shared by the engine's translation units (engine.cpp: life cycle, workspaces, graphs, the synthesis call;
+// engine_stream.cpp: the one-utterance stream, the batch stream, the pool, the stream gain; engine_deliver.cpp: what lies
+// behind the generator -- output rate, target loudness, true peak, limiter -- with its filters, setters, buffers and hooks;
 // engine_pack.cpp: voice -> packed weight arena; engine_launch.cpp: one launcher per kernel family; engine_issue.cpp: the
 // kernel sequence of the pipeline stages). Not part of any interface.
 #pragma once
@@ -36,6 +38,46 @@ struct EntryLock {
 };
 
 static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
+
+// PIPER_HIP_DEBUG_POISON: a freshly allocated workspace is filled with NaN bit patterns so that a kernel relying on memory
+// it never wrote shows up in the result. The fill runs on the null stream and is asynchronous to the host, while the
+// engine's stream does not synchronise with the null stream: without the wait below the fill could land AFTER the first
+// copies / launches into the new buffer (seen as NaNs in the first injected noise row, profiles/r05_notes.md, call 31-35).
+static inline void poison(void* p, size_t bytes) {
+  PE_HIP(hipMemset(p, 0xFF, bytes));
+  PE_HIP(hipDeviceSynchronize());
+}
+
+template <class Buf>
+void Engine::side_alloc(Buf& b, size_t n, bool idle, Fill fill, const char* what, size_t what_bytes) {
+  if (idle) {
+    PE_HIP(hipStreamSynchronize(stream_));
+    if (b) drop_graphs();
+  }
+  b.reset();
+  b.grow(n, what, what_bytes);
+  if (fill == FILL_ZERO || (fill == FILL_POISON_OR_ZERO && !pol_.debug_poison)) b.zero();
+  else if (fill != FILL_NONE && pol_.debug_poison) poison(b.get(), b.bytes());
+}
+
+// A pinned host buffer of at least n elements: grown with half as much again on top, its content not kept.
+template <typename T>
+static inline void grow_pinned(PinBuf<T>& b, size_t n) {
+  if (n > b.size()) b.grow(n + n / 2);
+}
+
+template <typename T>
+void Engine::rows_to_device(T* dst, long xs, const T* src, int batch, int64_t stride) {
+  for (int b = 0; b < batch && stride > 0; ++b)
+    PE_HIP(hipMemcpyAsync(dst + (size_t)b * xs, src + (size_t)b * stride, (size_t)stride * sizeof(T), hipMemcpyHostToDevice, stream_));
+}
+template <typename T>
+void Engine::rows_to_host(T* dst, int64_t stride, const T* src, long xs, int batch, const int32_t* count) {
+  for (int b = 0; b < batch; ++b) {
+    const size_t n = count ? (size_t)count[b] : (size_t)stride;
+    if (n > 0) PE_HIP(hipMemcpyAsync(dst + (size_t)b * stride, src + (size_t)b * xs, n * sizeof(T), hipMemcpyDeviceToHost, stream_));
+  }
+}
 
 // tile configurations of conv_mfma_kernel: {WM, WN, MT, NT}
 enum { CFG_A = 0, CFG_B = 1, CFG_C = 2, CFG_S = 3, CFG_G = 4, CFG_C2 = 5, CFG_B2 = 6 };

@@ -53,15 +53,15 @@ void Engine::issue_stage_a() {
     ep.out = x_; ep.o_bs = (long)H_ * Ts; ep.o_cs = Ts; ep.rng = d_rng_;
     if (ids_zc_) {
       const size_t Bc = capA_B_;
-      ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in_);
-      ep.h_lens = reinterpret_cast<const int*>(h_in_ + in_head_bytes(Bc));
+      ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in_.get());
+      ep.h_lens = reinterpret_cast<const int*>(h_in_.get() + in_head_bytes(Bc));
       ep.h_sids = ep.h_lens + Bc;
       ep.h_scales = reinterpret_cast<const float*>(ep.h_sids + Bc);
       ep.h_ids = ep.h_sids + Bc + in_scale_slots(Bc);
       ep.d_lens = d_tlens_; ep.d_sids = d_sids_; ep.d_scales = d_scales_;
       if (seeded_) {
-        ep.h_keys = reinterpret_cast<const unsigned long long*>(h_in_ + 32);
-        ep.h_use = reinterpret_cast<const int*>(h_in_ + 32 + 8 * Bc);
+        ep.h_keys = reinterpret_cast<const unsigned long long*>(h_in_.get() + 32);
+        ep.h_use = reinterpret_cast<const int*>(h_in_.get() + 32 + 8 * Bc);
       }
     }
     if (seeded_) { ep.keys = d_keys_; ep.use = d_use_; }
@@ -109,7 +109,7 @@ void Engine::issue_stage_a() {
     kt_on_ = attn4_for(e) != nullptr;
     kt_valid_ = false;
     if (pg && pend_bias) {
-      lngemm(x, pg, pb, y, e.qkv16, e.qkv.bias, 3 * H_, qkv, T, 2.0 * tsum * e.qkv.macs_per_col, ffn_parts_, nsl, pend_bias);
+      lngemm(x, pg, pb, y, e.qkv16, e.qkv.bias, 3 * H_, qkv, T, 2.0 * tsum * e.qkv.macs_per_col, ffn_parts_.get(), nsl, pend_bias);
       std::swap(x, y);
     } else if (pg) lngemm(y, pg, pb, x, e.qkv16, e.qkv.bias, 3 * H_, qkv, T, 2.0 * tsum * e.qkv.macs_per_col);
     else if (!(chain_q && conv1x1_col4(e.qkv16, e.qkv.bias, 3 * H_, x, qkv, d_tlens_, B, T, 2.0 * tsum * e.qkv.macs_per_col)))
@@ -193,7 +193,7 @@ void Engine::issue_stage_a() {
       const int Tp = rup(T, 4);
       fp.x = x.p; fp.x_bs = x.bs; fp.x_cs = x.cs;
       fp.w1p = e.f1p; fp.b1 = e.f1.bias; fp.w2p = e.f2p;
-      fp.parts = ffn_parts_; fp.nslices = nsl; fp.p_bs = (long)nsl * H_ * Tp;
+      fp.parts = ffn_parts_.get(); fp.nslices = nsl; fp.p_bs = (long)nsl * H_ * Tp;
       fp.lens = d_tlens_;
       const int khf = kbegin(prof_level_ >= 2 ? krow("ffn_kernel") : 0, 2.0 * tsum * (e.f1.macs_per_col + e.f2.macs_per_col),
                              4.0 * (tsum * (1.0 + nsl) * H_ + e.f1.macs_per_col + e.f2.macs_per_col));
@@ -222,7 +222,7 @@ void Engine::issue_stage_a() {
   const int pj_rows = stacked ? projpre_split_ + dp_pre_.rows : enc_proj_.rows;
   const double pj_flops = 2.0 * tsum * (enc_proj_.macs_per_col + (stacked ? dp_pre_.macs_per_col : 0));
   if (pg && pend_bias) {
-    lngemm(x, pg, pb, y, enc_proj16_, pj_bias, pj_rows, stats, T, pj_flops, ffn_parts_, nsl, pend_bias, stacked ? &sec : nullptr);
+    lngemm(x, pg, pb, y, enc_proj16_, pj_bias, pj_rows, stats, T, pj_flops, ffn_parts_.get(), nsl, pend_bias, stacked ? &sec : nullptr);
     std::swap(x, y);
   } else if (pg) lngemm(y, pg, pb, x, enc_proj16_, pj_bias, pj_rows, stats, T, pj_flops, nullptr, 0, nullptr, stacked ? &sec : nullptr);
   else conv(enc_proj_, x, stats, d_tlens_, 1, T, EPI_STORE);
@@ -238,7 +238,7 @@ void Engine::issue_stage_a() {
     // plan alone
     DurP dp{};
     dp.scales = d_scales_; dp.lens = d_tlens_; dp.dur = d_dur_; dp.cum = d_cum_; dp.d_bs = Ts; dp.frames = d_frames_;
-    dp.frames_host = h_frames_; dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
+    dp.frames_host = h_frames_.get(); dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
     PlanP pp{};
     plan_params(pp, dp);
     PE_LAUNCH_KB("duration_plan_kernel", 4.0 * 4.0 * tsum, launch::duration_plan(dim3(B), stream_, pp));
@@ -299,7 +299,7 @@ void Engine::issue_stage_a() {
     DurP dp{};
     dp.z0 = z2_ + (long)c0 * Ts; dp.z_bs = (long)2 * Ts; dp.m0 = ea_m0_; dp.es0 = ea_es0_; dp.scales = d_scales_;
     dp.lens = d_tlens_; dp.dur = d_dur_; dp.cum = d_cum_; dp.d_bs = Ts; dp.frames = d_frames_; dp.logw_out = logw_;
-    dp.frames_host = h_frames_; dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
+    dp.frames_host = h_frames_.get(); dp.frames_clamped = d_framesc_; dp.frame_cap = std::max(Fs_, 1);
     // the whole utterance as one graph: regulate_kernel, first launch of stage B, computes the durations itself
     fold_dp_ = dp;
     if (plan_on_) {
@@ -435,94 +435,7 @@ void Engine::issue_window() {
   PE_LAUNCH_K("window_copy_kernel", launch::window_copy(dim3((s_wg_ + 63) / 64, C_), stream_, zp_, Fs_, d_win_, zwin_, Fs_, C_));
   issue_decoder(zwin_, d_win_ + 1, s_wg_, (double)s_wg_, true);
   // converted rate: the chunk is resampled out of the window's waveform (row 0 of the pinned row block)
-  if (rs_on_) issue_resample(1, audio_, Ss_, rs_host_, nullptr, out_samples((long)s_wg_ * hop_) + 1, (double)s_wg_ * hop_);
-}
-
-// Output-rate conversion of B rows of x into raudio_: the row block (from the pinned block `hst`, or whole utterances of
-// lens[b] * hop native samples), then resample_kernel on tiles of rs_tile_ outputs; max_out bounds every row's count.
-void Engine::issue_resample(int B, const float* x, long x_bs, const int* hst, const int* lens, long max_out, double native_samples) {
-  if (B > rs_cap_ || !raudio_ || !rs_coef_) throw std::runtime_error("resampling buffers are not sized for this call");
-  max_out = std::max<long>(1, std::min<long>(max_out, So_));
-  PE_LAUNCH_K("resample_rows_kernel",
-              launch::resample_rows(stream_, hst, lens, hop_, rs_dev_, rs_cap_, B, std::min<long>(x_bs, Ss_), So_, rs_L_, rs_M_));
-  RsP p{};
-  p.x = x; p.x_bs = x_bs; p.y = raudio_; p.y_bs = So_;
-  p.coef = rs_coef_; p.L = rs_L_; p.M = rs_M_; p.K = rs_K_; p.Tp = rs_Tp_;
-  p.rows = rs_dev_; p.cap = rs_cap_; p.tile = rs_tile_;
-  // algorithmic bytes: every native sample in once, every output out once (the table stays in cache)
-  PE_LAUNCH_KB("resample_kernel", 4.0 * native_samples * (1.0 + (double)rs_L_ / rs_M_),
-               launch::resample(dim3((unsigned)((max_out + rs_tile_ - 1) / rs_tile_), B), stream_, p));
-}
-
-// Target loudness of B delivered rows (whole utterances): the segment sums of the K-weighted rows, the gated loudness and
-// the scale per row, and the int16 conversion with that scale in pcm16_kernel's place (kernels/loudness.h).
-// The floats are only read, so it does not matter which kernel wrote them (conv_post, the fused stage tail, the resampler).
-void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, int len_mul, const unsigned* peaks, long max_n,
-                            int16_t* pcm, int16_t* zc, double samples) {
-  if (!ld_coef_ || !ld_seg_ || !ld_ctl_ || !ld_dev_ || B > ld_cap_ || (size_t)B > ld_seg_rows_ || ld_h_ < 1)
-    throw std::runtime_error("loudness buffers are not sized for this call");
-  max_n = std::max<long>(1, std::min<long>(max_n, x_bs));
-  LoudP p{};
-  p.x = x; p.x_bs = x_bs; p.lens = lens; p.len_mul = len_mul; p.x_cap = x_bs;
-  p.coef = ld_coef_; p.h = ld_h_; p.W = ld_W_; p.R = ld_R_;
-  p.seg = ld_seg_; p.nseg_cap = ld_nseg_cap_;
-  const bool tp = ld_kind_ == PEAK_TRUE;
-  if (tp && (!tp_coef_ || !tp_words_ || B > tp_cap_ || tp_fs_ != output_rate()))
-    throw std::runtime_error("true-peak buffers are not sized for this call");
-  p.tpeak = tp ? tp_words_ : nullptr;
-  const bool lim = lim_on_;
-  run_lim_ = lim;
-  if (lim && tp && (!lim_z_ || !lim_v_ || (size_t)B * (size_t)x_bs > lim_zv_floats_))
-    throw std::runtime_error("limiter buffers are not sized for this call");
-  if (lim && (!lim_h_ || !lim_rep_ || B > lim_cap_ || lim_fs_ != output_rate() || lim_h_ms_ != lim_ms_))
-    throw std::runtime_error("limiter buffers are not sized for this call");
-  p.limrep = lim ? lim_rep_ : nullptr; p.limcap = lim ? lim_cap_ : 0;
-  const int nseg = (int)std::min<long>((max_n + ld_h_ - 1) / ld_h_, ld_nseg_cap_);
-  // algorithmic bytes: every delivered sample in once (the warm-up is read again out of the caches)
-  PE_LAUNCH_KB("loudness_seg_kernel", 4.0 * samples, launch::loudness_seg(dim3((unsigned)nseg, B), stream_, p));
-  if (tp) {
-    // true-peak ceiling: max |x interpolated tp_Q_ times| per row, into the words loudness_seg_kernel cleared
-    TpP q{};
-    q.x = x; q.x_bs = x_bs; q.lens = lens; q.len_mul = len_mul; q.x_cap = x_bs;
-    q.coef = tp_coef_; q.Q = tp_Q_; q.tpeak = tp_words_;
-    if (lim) {      // (the limiter's envelope wants the per-position maxima as well)
-      q.v = lim_v_;
-      PE_LAUNCH_KB("true_peak_v_kernel", 8.0 * samples, launch::true_peak_v(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, q));
-    } else
-    PE_LAUNCH_KB("true_peak_kernel", 4.0 * samples, launch::true_peak(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, q));
-  }
-  PE_LAUNCH_K("loudness_gain_kernel",
-              launch::loudness_gain(stream_, B, ld_seg_, ld_nseg_cap_, lens, len_mul, x_bs, ld_h_, peaks, tp ? tp_words_ : nullptr,
-                                    ld_ctl_, ld_dev_, ld_cap_, lim ? 1 : 0));
-  if (lim) {
-    // look-ahead limiter: the conversion, with the rows loudness_gain_kernel marked SHAPED turned down around their peaks
-    LimP q{};
-    q.x = x; q.x_bs = x_bs; q.lens = lens; q.len_mul = len_mul; q.x_cap = x_bs;
-    q.gq = ld_dev_; q.gcap = ld_cap_; q.ctl = ld_ctl_; q.h = lim_h_; q.W = lim_W_;
-    q.pcm = pcm; q.p_bs = x_bs; q.host = zc; q.rep = lim_rep_; q.rcap = lim_cap_;
-    if (tp) {
-      // true-peak ceiling: z = x e and max |z|, the true peak of z into its word, then the conversion with the trimmed scale
-      q.v = lim_v_; q.z = lim_z_;
-      PE_LAUNCH_KB("limiter_true_kernel", 12.0 * samples,
-                   launch::limiter_true(dim3((unsigned)((max_n + LIM_TILE - 1) / LIM_TILE), B), stream_, q));
-      TpP t{};
-      t.x = lim_z_; t.x_bs = x_bs; t.lens = lens; t.len_mul = len_mul; t.x_cap = x_bs;
-      t.coef = tp_coef_; t.Q = tp_Q_; t.tpeak = reinterpret_cast<unsigned*>(lim_rep_) + lim_o_tz(lim_cap_);
-      PE_LAUNCH_KB("true_peak_kernel", 4.0 * samples, launch::true_peak(dim3((unsigned)((max_n + TP_TILE - 1) / TP_TILE), B), stream_, t));
-      TrimP r{};
-      r.z = lim_z_; r.z_bs = x_bs; r.lens = lens; r.len_mul = len_mul; r.gq = ld_dev_; r.gcap = ld_cap_; r.ctl = ld_ctl_;
-      r.rep = lim_rep_; r.rcap = lim_cap_; r.pcm = pcm; r.p_bs = x_bs; r.host = zc;
-      PE_LAUNCH_KB("pcm16_trim_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
-                   launch::pcm16_trim(dim3((unsigned)((max_n + 255) / 256), B), stream_, r));
-      return;
-    }
-    PE_LAUNCH_KB("limiter_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
-                 launch::limiter(dim3((unsigned)((max_n + LIM_TILE - 1) / LIM_TILE), B), stream_, q));
-    return;
-  }
-  PE_LAUNCH_KB("pcm16_gain_kernel", samples * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
-               launch::pcm16_gain(dim3((unsigned)((max_n + 255) / 256), B), stream_, x, x_bs, ld_dev_, ld_cap_, lens, len_mul, pcm,
-                                  x_bs, zc));
+  if (rs_on_) issue_resample(1, audio_, Ss_, rs_host_.get(), nullptr, out_samples((long)s_wg_ * hop_) + 1, (double)s_wg_ * hop_);
 }
 
 // Lock-step window stage of a row set (the batch stream's utterances, the pool's slots): every row's window of its latent ->
@@ -532,7 +445,7 @@ void Engine::issue_loudness(int B, const float* x, long x_bs, const int* lens, i
 // exactly the launches it always did.
 void Engine::issue_window_rows(const ChunkRows& r) {
   const int B = (int)r.pos.size(), cap = r.cap, wg = r.wg;
-  int *const dst = r.dev, *const gctl = r.gctl, *const gdev = r.gdev;
+  int *const dst = r.dev.get(), *const gctl = r.gctl.get(), *const gdev = r.gdev.get();
   // the stage is issued as a call of B utterances, whatever the handle's last upload was (the pool's slots); that call's
   // batch size comes back whichever way the stage is left
   struct Restore { int& b; int b0; ~Restore() { b = b0; } } restore{B_, B_};
@@ -540,7 +453,7 @@ void Engine::issue_window_rows(const ChunkRows& r) {
   const int gm = gain_mode_;
   if (gm != GAIN_CHUNK && (!gctl || !gdev || B > cap)) throw std::runtime_error("stream gain blocks are not sized for this call");
   PE_LAUNCH_KB("window_gather_kernel", 8.0 * B * C_ * wg,
-               launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, r.src, r.src_bs, r.src_cs, r.host, dst, cap,
+               launch::window_gather(dim3((wg + 63) / 64, C_, B), stream_, r.src, r.src_bs, r.src_cs, r.host.get(), dst, cap,
                                      noise_z_, (long)C_ * Fs_, Fs_, wg));
   // what the cost models see (window geometry of the stage kernels, profile rows): the window bucket for every utterance --
   // a function of the graph's key, whatever the utterances' real lengths are
@@ -557,16 +470,16 @@ void Engine::issue_window_rows(const ChunkRows& r) {
     // converted rate: every chunk is resampled out of its window (rows in the pinned row block); the peak the kernel folds
     // is the chunk's own, so the delivery is the conversion alone
     const long max_out = out_samples((long)wg * hop_) + 1;
-    issue_resample(B, audio_, Ss_, rs_host_, nullptr, max_out, (double)B * wg * hop_);
+    issue_resample(B, audio_, Ss_, rs_host_.get(), nullptr, max_out, (double)B * wg * hop_);
     const int rsteps = std::max(1, (int)((max_out + CHUNK_SPB - 1) / CHUNK_SPB));
     if (gm != GAIN_CHUNK) {
-      PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, rs_dev_, rs_cap_, So_));
+      PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, rs_dev_.get(), rs_cap_, So_));
       PE_LAUNCH_KB("chunk_pcm_rs_gain_kernel", 10.0 * B * (double)max_out,
-                   launch::chunk_pcm_rs_gain(dim3(rsteps, B), stream_, raudio_, So_, rs_dev_, rs_cap_, dst, cap, gdev));
+                   launch::chunk_pcm_rs_gain(dim3(rsteps, B), stream_, raudio_.get(), So_, rs_dev_.get(), rs_cap_, dst, cap, gdev));
       return;
     }
     PE_LAUNCH_KB("chunk_pcm_rs_kernel", 10.0 * B * (double)max_out,
-                 launch::chunk_pcm_rs(dim3(rsteps, B), stream_, raudio_, So_, rs_dev_, rs_cap_, dst, cap));
+                 launch::chunk_pcm_rs(dim3(rsteps, B), stream_, raudio_.get(), So_, rs_dev_.get(), rs_cap_, dst, cap));
     return;
   }
   const int steps = std::max(1, (int)(((long)wg * hop_ + CHUNK_SPB - 1) / CHUNK_SPB));
@@ -674,7 +587,7 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
         }
       } else if (sched.form != STAGE_CHAIN) {
         // step d of every resblock in one grouped launch; each resblock keeps its own buffers, one pass sums them
-        auto SV = [&](int k) { return View{side_[k], (long)st.ch * Ls, (int)Ls}; };
+        auto SV = [&](int k) { return View{side_[k].get(), (long)st.ch * Ls, (int)Ls}; };
         View xin[3] = {u, u, u};
         bool summed = false;
         const int nsteps = (int)st.rb[0].size();
@@ -704,7 +617,7 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
           }
         }
         if (!summed)
-          PE_LAUNCH_K("mrf_sum_kernel", launch::mrf_sum(dim3((Lmax + 255) / 256, st.ch, B), stream_, side_[8], side_[3], nk == 3 ? side_[7] : (const float*)nullptr, xs.p, xs.bs, xs.cs, lens, mult, inv_nk));
+          PE_LAUNCH_K("mrf_sum_kernel", launch::mrf_sum(dim3((Lmax + 255) / 256, st.ch, B), stream_, side_[8].get(), side_[3].get(), nk == 3 ? side_[7].get() : (const float*)nullptr, xs.p, xs.bs, xs.cs, lens, mult, inv_nk));
       } else {
         for (int j = 0; j < nk; ++j) {
           const int accmode = nk == 1 ? 3 : (j == 0 ? 0 : (j == nk - 1 ? 2 : 1));
@@ -722,18 +635,18 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
     if (!tail_done)
       PE_LAUNCH_KB("conv_post_kernel", 4.0 * fsum * hop_ * (post_cin_ + 1.0), launch::conv_post(dim3((Lmax + POST_SPB - 1) / POST_SPB, B), stream_, cur.p, cur.bs, cur.cs, post_w_, post_cin_, 0.01f, lens, hop_, audio_, Ss_, absmax_));
     // (the streaming window path delivers per chunk from the device buffer)
-    int16_t* zc = (pol_.pcm_zc && !zero_absmax && h_pcm_zc_cap_ >= (size_t)B * (size_t)So_) ? h_pcm_zc_ : nullptr;
+    int16_t* zc = (pol_.pcm_zc && !zero_absmax && h_pcm_zc_.size() >= (size_t)B * (size_t)So_) ? h_pcm_zc_.get() : nullptr;
     if (rs_on_ && !zero_absmax) {
       // converted rate, whole utterances: resample, then the int16 conversion on output lengths with the peak of the
       // RESAMPLED waveform (a band-limited interpolation can overshoot the native peak)
       const long max_out = out_samples((long)Lmax);
       issue_resample(B, audio_, Ss_, nullptr, lens, max_out, fsum * hop_);
       if (ld_on_)
-        issue_loudness(B, raudio_, So_, rs_counts(), 1, rs_peaks(), max_out, rpcm_, zc, fsum * hop_ * ((double)rs_L_ / rs_M_));
+        issue_loudness(B, raudio_.get(), So_, rs_counts(), 1, rs_peaks(), max_out, rpcm_.get(), zc, fsum * hop_ * ((double)rs_L_ / rs_M_));
       else
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * ((double)rs_L_ / rs_M_) * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
-                   launch::pcm16(dim3((unsigned)((max_out + 255) / 256), B), stream_, raudio_, So_, rs_peaks(), rs_counts(), 1,
-                                 rpcm_, So_, zc));
+                   launch::pcm16(dim3((unsigned)((max_out + 255) / 256), B), stream_, raudio_.get(), So_, rs_peaks(), rs_counts(), 1,
+                                 rpcm_.get(), So_, zc));
     } else if (with_pcm16 && ld_on_ && !zero_absmax)
       issue_loudness(B, audio_, Ss_, lens, hop_, absmax_, Lmax, pcm_, zc, fsum * hop_);
     else if (with_pcm16)

@@ -660,7 +660,7 @@ void Engine::init(const WeightSet& ws) {
   for (auto n : rows) prof_.push_back(ProfileRow{n});
   PE_HIP(hipEventCreate(&ev0_));
   PE_HIP(hipEventCreate(&ev1_));
-  PE_HIP(hipHostMalloc((void**)&h_frames_, 4096 * sizeof(int)));
+  h_frames_.grow(4096);
 }
 
 // Fused MRF stage (kernels/mrf.h): flattens the resblocks of a <= 64-channel stage into phases (one per conv) and writes

@@ -275,7 +275,8 @@ def test_launch_policy_table_is_exported_and_documented(lib):
     documented = set(re.findall(r"`(PIPER_HIP_[A-Z0-9_]+)`", sec))
     assert documented - {"PIPER_HIP_MATRIX", "PIPER_HIP_GROUP_BCAST", "PIPER_HIP_GROUP_COALESCE"} == set(envs)
     # no other translation unit of the engine reads a PIPER_HIP_* integer on its own
-    for fn in ("engine.cpp", "engine_pack.cpp", "engine_launch.cpp", "engine_issue.cpp", "pe_api.cpp"):
+    for fn in ("engine.cpp", "engine_stream.cpp", "engine_deliver.cpp", "engine_pack.cpp", "engine_launch.cpp", "engine_issue.cpp",
+               "pe_api.cpp"):
         path = os.path.join(ROOT, "piper_amd", "csrc", fn)
         if os.path.exists(path):
             reads = set(re.findall(r'getenv\("(PIPER_HIP_[A-Z0-9_]+)"\)', open(path).read()))
