@@ -23,6 +23,7 @@
 #include <optional>
 #include <ostream>
 #include <string>
+#include <utility>
 #include <vector>
 
 struct pe_engine;
@@ -118,6 +119,15 @@ struct SynthesisConfig {
   // with another seed. synthesize uses it as it is; utterance k of synthesizeBatch and phrase k of a textToAudio call,
   // counted over the whole text, get seed + k (wrapping at 2^64). Unset, the default: the engine's own stream.
   std::optional<uint64_t> seed;
+
+  // Speaker blend and caller-supplied speaker vector (piper_hip.h: pe_blend). speakerBlend: up to 8 (speaker id, weight)
+  // components; every phrase is spoken with g = w_0 * emb[s_0], then g = fma(w_k, emb[s_k], g) in the order given -- the
+  // weights as they are, not normalised, negative or above 1 allowed. speakerVector: gin values used as the speaker embedding
+  // itself (pe_get_speaker_dim, pe_get_speaker_embedding). Both are honoured by synthesize, synthesizeBatch and textToAudio,
+  // for every phrase. Setting both, or either one together with speakerId, throws (loadVoice sets speakerId for a
+  // multi-speaker voice: reset() it first).
+  std::vector<std::pair<SpeakerId, float>> speakerBlend;
+  std::vector<float> speakerVector;
 
   // Extra silence
   float sentenceSilenceSeconds = 0.2f;

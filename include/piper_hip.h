@@ -161,6 +161,50 @@ int pe_upload_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, i
 int pe_synthesize_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                                const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing,
                                const pe_seeds* seeds);
+/* Blend speakers: weighted embedding mixes and caller-supplied vectors. Host pointers.
+ * The law. Every utterance of a call gets one speaker vector g_b[gin]. The choice depends on a per-utterance count:
+ *   - count[b] == 0: g_b = emb_g[sids[b]], as ever.
+ *   - count[b] == n, with n in 1..8:
+ *     - The components (s_0, a_0) .. (s_{n-1}, a_{n-1}) are speaker ids and f32 weights, taken in the order given.
+ *     - Per element i, g = a_0 * e_{s_0}[i] as one f32 product.
+ *     - Then g = fmaf(a_k, e_{s_k}[i], g) for k = 1 .. n-1.
+ *     - The weights are used as given. They are not normalised anywhere, and they may be negative or exceed 1.
+ *     - A repeated id is allowed.
+ *   - count[b] == -1: g_b is row b of a caller-supplied vector[batch][gin], bit for bit.
+ * Everything behind g_b is unchanged: out[b][r] = W[r][:] . g_b + bias[r], with the summation order cond_kernel has today.
+ * Two consequences hold bit for bit, audio and durations alike: the blend {(s, 1.0f)} gives what the plain call with
+ * sids[b] = s gives, and the vector emb_g[s] gives what the plain call with sids[b] = s gives.
+ * An utterance's g_b depends on nothing else: not its components' neighbours, not its row in the batch, the batch size, a
+ * shape bucket, the entry point, a group member or a pool slot.
+ * sids[b] of an utterance whose count is not 0 is not read. The _blended entry points are the _seeded calls they are named
+ * after plus the blend; with a NULL blend they are exactly those calls. pe_run repeated on a blended upload keeps the
+ * blend; the next upload of any kind drops it. The blend's values are call inputs like the ids: no captured graph depends
+ * on them (whether a call carries a blend at all is part of the graph keys). A call without a blend issues exactly the
+ * launches it always did; a blended call issues one more (speaker_blend_kernel).
+ * Refused, with a message that names the utterance and the component, before anything of the engine changes (a live stream
+ * goes on): a blend on a single-speaker voice; a count outside [-1, 8]; a component id outside [0, num_speakers); a weight
+ * or vector element that is not finite; count -1 with a NULL `vector`; NULL `sid` or `weight` while some count is > 0. */
+enum { PE_BLEND_MAX = 8 };
+typedef struct pe_blend {
+  const int32_t* count;   /* [batch]: 0 plain sid, 1..8 components, -1 row b of `vector` */
+  const int64_t* sid;     /* components of all utterances, concatenated in utterance order */
+  const float*   weight;  /* alike */
+  const float*   vector;  /* [batch][gin], may be NULL when no count is -1 */
+} pe_blend;
+int pe_upload_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                      const int64_t* sids, const pe_noise* noise, const pe_timing* timing, const pe_seeds* seeds,
+                      const pe_blend* blend);
+int pe_synthesize_batch_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing,
+                                const pe_seeds* seeds, const pe_blend* blend);
+/* gin, the length of a speaker vector (0 for a single-speaker voice), and row `sid` of the speaker table: callers who do
+ * their own arithmetic read rows here and come back with a vector (count -1) */
+int pe_get_speaker_dim(pe_engine* e, int32_t* gin);
+int pe_get_speaker_embedding(pe_engine* e, int64_t sid, float* out, int64_t capacity);
+/* test hook: speaker_blend_kernel alone -- out[batch][gin] for the blend and the plain ids (sids, NULL: all 0) of a call,
+ * no synthesis. pe_debug_tensor knows the name "g": the [gin] vector utterance b used in the last call (the table row for
+ * a plain one). */
+int pe_debug_blend(pe_engine* e, const pe_blend* blend, int32_t batch, const int64_t* sids, float* out);
 int pe_run(pe_engine* e);
 int pe_fetch(pe_engine* e, int want_audio, int want_pcm, pe_result* result);
 
@@ -177,6 +221,10 @@ int pe_stream_begin(pe_engine* e, const int64_t* ids, int64_t n_ids, const float
 int pe_stream_begin_seeded(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                            const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames, const pe_timing* timing,
                            const pe_seeds* seeds);
+/* ... and with the utterance's speaker blend or vector (pe_blend above, batch = 1) */
+int pe_stream_begin_blended(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                            const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames, const pe_timing* timing,
+                            const pe_seeds* seeds, const pe_blend* blend);
 int pe_stream_next(pe_engine* e, int32_t chunk_frames, const float** audio, const int16_t** pcm, int64_t* n_samples);
 
 /* Streaming decode of a whole batch in lock step: B listeners get their first chunk after the text encoder, the duration
@@ -197,6 +245,10 @@ int pe_stream_begin_batch_timed(pe_engine* e, const int64_t* ids, const int64_t*
 int pe_stream_begin_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
                                  const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
                                  const pe_timing* timing, const pe_seeds* seeds);
+/* ... and with per-utterance speaker blends (pe_blend above) */
+int pe_stream_begin_batch_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                  const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                  const pe_timing* timing, const pe_seeds* seeds, const pe_blend* blend);
 
 typedef struct pe_stream_chunk {
   int32_t batch;
@@ -254,6 +306,11 @@ int pe_stream_pool_join_timed(pe_engine* e, const int64_t* ids, const int64_t* o
 int pe_stream_pool_join_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
                                const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
                                const pe_timing* timing, const pe_seeds* seeds);
+/* ... and with per-utterance speaker blends (pe_blend above): a slot's conditioning row is copied from the newcomer's own, so
+ * a slot taken by a blended newcomer and later by a plain one inherits nothing */
+int pe_stream_pool_join_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                                const pe_timing* timing, const pe_seeds* seeds, const pe_blend* blend);
 int pe_stream_pool_next(pe_engine* e, int32_t chunk_frames, const int32_t* chunk_frames_per_slot, int want_audio,
                         pe_stream_chunk* out);
 int pe_stream_pool_leave(pe_engine* e, int32_t slot);
@@ -561,6 +618,11 @@ int pe_group_synthesize_batch_scaled(pe_group* g, const int64_t* ids, const int6
  * along with their ids, so a seeded utterance's audio does not depend on the member that ran it */
 int pe_group_synthesize_batch_seeded(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
                                      const float* scales, const int64_t* sids, pe_result* result, const pe_seeds* seeds);
+/* ... and with per-utterance speaker blends (pe_blend above; NULL: exactly the _seeded call): each shard takes its
+ * utterances' blends along with their ids */
+int pe_group_synthesize_batch_blended(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                      const float* scales, const int64_t* sids, pe_result* result, const pe_seeds* seeds,
+                                      const pe_blend* blend);
 /* which engine (index into the group) ran utterance i of the last call */
 int pe_group_assignment(pe_group* g, int32_t* engine_index, int64_t capacity);
 void pe_group_destroy(pe_group* g);
@@ -590,6 +652,13 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
 int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                                    const uint64_t* seed, int16_t** pcm, int64_t* n_samples, int32_t* frames,
                                    double* infer_seconds, int32_t* batch_size);
+/* ... with the request's speaker blend or vector: `blend` is ONE request's count[1], sid, weight, vector[gin] (pe_blend
+ * above), NULL for a plain request: exactly the call above. Both kinds of coalescer merge blended and plain requests into
+ * one engine call; a blended request gets what its own B = 1 blended call computes. A blend the law refuses fails its own
+ * request before it is queued. */
+int pe_coalescer_synthesize_blended(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                                    const uint64_t* seed, const pe_blend* blend, int16_t** pcm, int64_t* n_samples,
+                                    int32_t* frames, double* infer_seconds, int32_t* batch_size);
 int pe_coalescer_stats(pe_coalescer* c, int64_t* engine_calls, int64_t* requests);
 void pe_coalescer_destroy(pe_coalescer* c);
 

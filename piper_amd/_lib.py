@@ -21,6 +21,9 @@ SYMBOLS = [
     "pe_upload_timed", "pe_synthesize_batch_timed", "pe_stream_begin_batch_timed", "pe_stream_pool_join_timed", "pe_debug_timing",
     "pe_upload_seeded", "pe_synthesize_batch_seeded", "pe_stream_begin_seeded", "pe_stream_begin_batch_seeded",
     "pe_stream_pool_join_seeded", "pe_group_synthesize_batch_seeded", "pe_coalescer_synthesize_seeded",
+    "pe_upload_blended", "pe_synthesize_batch_blended", "pe_stream_begin_blended", "pe_stream_begin_batch_blended",
+    "pe_stream_pool_join_blended", "pe_group_synthesize_batch_blended", "pe_coalescer_synthesize_blended",
+    "pe_get_speaker_dim", "pe_get_speaker_embedding", "pe_debug_blend",
     "pe_get_durations", "pe_get_info", "pe_set_output_rate", "pe_get_output_rate", "pe_debug_resample",
     "pe_set_stream_gain", "pe_get_stream_gain", "pe_stream_last_gains",
     "pe_set_loudness", "pe_get_loudness", "pe_last_loudness", "pe_loudness_filter", "pe_debug_loudness",
@@ -46,6 +49,11 @@ class PeTiming(C.Structure):
 
 class PeSeeds(C.Structure):
     _fields_ = [("seed", C.POINTER(C.c_uint64)), ("use", C.POINTER(C.c_uint8))]
+
+
+class PeBlend(C.Structure):
+    _fields_ = [("count", C.POINTER(C.c_int32)), ("sid", C.POINTER(C.c_int64)), ("weight", C.POINTER(C.c_float)),
+                ("vector", C.POINTER(C.c_float))]
 
 
 class PeResult(C.Structure):
@@ -90,19 +98,28 @@ def bind(path: str) -> C.CDLL:
     sp = C.POINTER(PeSeeds)
     lib.pe_upload_seeded.argtypes = lib.pe_upload_timed.argtypes + [sp]
     lib.pe_synthesize_batch_seeded.argtypes = lib.pe_synthesize_batch_timed.argtypes + [sp]
+    bp = C.POINTER(PeBlend)
+    lib.pe_upload_blended.argtypes = lib.pe_upload_seeded.argtypes + [bp]
+    lib.pe_synthesize_batch_blended.argtypes = lib.pe_synthesize_batch_seeded.argtypes + [bp]
+    lib.pe_get_speaker_dim.argtypes = [vp, i32p]
+    lib.pe_get_speaker_embedding.argtypes = [vp, C.c_int64, f32p, C.c_int64]
+    lib.pe_debug_blend.argtypes = [vp, bp, C.c_int32, i64p, f32p]
     lib.pe_run.argtypes = [vp]
     lib.pe_fetch.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PeResult)]
     lib.pe_stream_begin.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_begin_seeded.argtypes = lib.pe_stream_begin.argtypes + [tp, sp]
+    lib.pe_stream_begin_blended.argtypes = lib.pe_stream_begin_seeded.argtypes + [bp]
     lib.pe_stream_next.argtypes = [vp, C.c_int32, C.POINTER(f32p), C.POINTER(C.POINTER(C.c_int16)), i64p]
     lib.pe_stream_begin_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_begin_batch_timed.argtypes = lib.pe_stream_begin_batch.argtypes + [tp]
     lib.pe_stream_begin_batch_seeded.argtypes = lib.pe_stream_begin_batch_timed.argtypes + [sp]
+    lib.pe_stream_begin_batch_blended.argtypes = lib.pe_stream_begin_batch_seeded.argtypes + [bp]
     lib.pe_stream_next_batch.argtypes = [vp, C.c_int32, C.c_int, C.POINTER(PeStreamChunk)]
     lib.pe_stream_pool_open.argtypes = [vp, C.c_int32, C.c_int32, i32p]
     lib.pe_stream_pool_join.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeNoise), i32p, i32p]
     lib.pe_stream_pool_join_timed.argtypes = lib.pe_stream_pool_join.argtypes + [tp]
     lib.pe_stream_pool_join_seeded.argtypes = lib.pe_stream_pool_join_timed.argtypes + [sp]
+    lib.pe_stream_pool_join_blended.argtypes = lib.pe_stream_pool_join_seeded.argtypes + [bp]
     lib.pe_debug_timing.argtypes = [vp, f32p, i64p, C.c_int32, f32p, tp, i32p, i32p, f32p]
     lib.pe_stream_pool_next.argtypes = [vp, C.c_int32, i32p, C.c_int, C.POINTER(PeStreamChunk)]
     lib.pe_stream_pool_leave.argtypes = [vp, C.c_int32]
@@ -165,6 +182,7 @@ def bind(path: str) -> C.CDLL:
     lib.pe_group_synthesize_batch.argtypes = [vp, i64p, i64p, C.c_int32, f32p, i64p, C.POINTER(PeResult)]
     lib.pe_group_synthesize_batch_scaled.argtypes = lib.pe_group_synthesize_batch.argtypes
     lib.pe_group_synthesize_batch_seeded.argtypes = lib.pe_group_synthesize_batch.argtypes + [sp]
+    lib.pe_group_synthesize_batch_blended.argtypes = lib.pe_group_synthesize_batch_seeded.argtypes + [bp]
     lib.pe_group_assignment.argtypes = [vp, i32p, C.c_int64]
     lib.pe_group_destroy.argtypes = [vp]
     lib.pe_group_destroy.restype = None
@@ -174,6 +192,8 @@ def bind(path: str) -> C.CDLL:
                                             i32p, C.POINTER(C.c_double), i32p]
     lib.pe_coalescer_synthesize_seeded.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(C.c_uint64),
                                                    C.POINTER(C.POINTER(C.c_int16)), i64p, i32p, C.POINTER(C.c_double), i32p]
+    lib.pe_coalescer_synthesize_blended.argtypes = [vp, i64p, C.c_int64, f32p, C.c_int64, C.POINTER(C.c_uint64), bp,
+                                                    C.POINTER(C.POINTER(C.c_int16)), i64p, i32p, C.POINTER(C.c_double), i32p]
     lib.pe_coalescer_stats.argtypes = [vp, i64p, i64p]
     lib.pe_coalescer_destroy.argtypes = [vp]
     lib.pe_coalescer_destroy.restype = None

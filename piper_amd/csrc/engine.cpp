@@ -148,8 +148,10 @@ void Engine::ensure_stage_a(int B, int Tmax) {
     Carver c(base);
     // input block: [rng 4 x u64 | seed keys Bc x u64, use flags Bc (padded to 16 bytes) | lengths Bc | speaker ids Bc |
     // scales Bc x 3 (padded to 4) | ids Bc x T] (contiguous, copied as one piece by upload())
-    const size_t ns = in_scale_slots(Bc), head = in_head_bytes(Bc);
-    d_in_ = c.take<char>(head + (2 * Bc + ns + Bc * T) * sizeof(int));
+    // In front of it, in the same allocation, the blend area of a multi-speaker voice (engine.h: in_blend_bytes).
+    const size_t ns = in_scale_slots(Bc), head = in_head_bytes(Bc), bl = in_blend_bytes(Bc);
+    d_blend_ = c.take<char>(bl + head + (2 * Bc + ns + Bc * T) * sizeof(int));
+    d_in_ = base ? d_blend_ + bl : nullptr;
     d_rng_ = reinterpret_cast<unsigned long long*>(d_in_);
     d_keys_ = reinterpret_cast<unsigned long long*>(d_in_ + 32);
     d_use_ = reinterpret_cast<int*>(d_in_ + 32 + 8 * Bc);
@@ -180,6 +182,9 @@ void Engine::ensure_stage_a(int B, int Tmax) {
     logw_ = c.take<float>(Bc * T);
     noise_w_ = c.take<float>(Bc * 2 * T);
     cond_ = c.take<float>(Bc * (size_t)std::max(cond_bs_, 1));
+    // speaker vectors of a blended call and cond_kernel's row index into them (speaker_blend_kernel)
+    g_tab_ = nspk_ > 1 ? c.take<float>(Bc * (size_t)gin_) : nullptr;
+    g_rows_ = nspk_ > 1 ? c.take<int>(Bc) : nullptr;
     plan_w_ = c.take<float>(Bc * T);               // timing plan (kernels/timing.h): w per id, and the plan block
     d_plan_ = c.take<int>(plan_words(Bc, T));
     // utterances whose attention score slab does not fit LDS: [utterance][head][query block][32][SP] in global memory
@@ -216,7 +221,7 @@ void Engine::ensure_stage_a(int B, int Tmax) {
     if (pol_.debug_poison) poison(wsA_.get(), wsA_.bytes());
     carve(wsA_.get(), capA_B_, capA_T_);
     PE_HIP(hipMemsetAsync(d_in_, 0, 32, stream_));        // generator state: "no upload ingested yet" (embed_kernel)
-    h_in_.grow(in_bytes_);
+    h_in_.grow(in_blend_bytes(capA_B_) + in_bytes_);
   }
   Ts_ = (int)capA_T_;
   carve(wsA_.get(), capA_B_, capA_T_);
@@ -317,11 +322,13 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
 // ------------------------------------------------------------------------------------------------
 
 void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
-                    const int64_t* sids, const NoiseIn* noise, bool per_utt, const TimingIn* timing, const SeedsIn* seeds) {
+                    const int64_t* sids, const NoiseIn* noise, bool per_utt, const TimingIn* timing, const SeedsIn* seeds,
+                    const BlendIn* blend) {
   EntryLock entry_lock;
   if (B <= 0 || B > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
   if (!scales) throw std::runtime_error("null scales");
   if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
+  if (blend) check_blend(*blend, B);                                               // (throws before anything changes)
   const bool all_forced = timing ? check_timing(*timing, offsets, B) : false;      // (throws before anything changes)
   PE_HIP(hipSetDevice(device_));
   sb_active_ = false;               // new inputs end a batch stream: its latent and its window state go with them
@@ -345,7 +352,7 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   // the pinned mirror of the input block; a copy of the previous call that might still read it ended with that call's
   // final synchronisation (an abandoned upload is simply overwritten)
   const size_t Bc = capA_B_;
-  char* const h_in = h_in_.get();
+  char* const h_in = this->h_in();
   unsigned long long* hr = reinterpret_cast<unsigned long long*>(h_in);
   int* htl = reinterpret_cast<int*>(h_in + in_head_bytes(Bc));
   int* hsid = htl + Bc;
@@ -367,7 +374,8 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
   }
   if (nspk_ > 1)
     for (int b = 0; b < B; ++b) {
-      const int64_t sp = sids ? sids[b] : 0;
+      // (an utterance with components or a vector of its own has no speaker id: whatever stands there is not read)
+      const int64_t sp = (sids && !(blend && blend->count[b] != 0)) ? sids[b] : 0;
       if (sp < 0 || sp >= nspk_) throw std::runtime_error("speaker id outside [0, num_speakers)");
       hsid[b] = (int)sp;
     }
@@ -399,10 +407,33 @@ void Engine::upload(const int64_t* ids, const int64_t* offsets, int B, const flo
       hu[b] = (!seeds->use || seeds->use[b]) ? 1 : 0;
     }
   }
+  // speaker blends: counts, components in fixed rows of BLEND_MAX, vectors, in the area in front of the block
+  blended_ = blend != nullptr;
+  const size_t bl = in_blend_bytes(Bc);
+  if (blended_) {
+    char* const area = h_in - bl;
+    int* hc = reinterpret_cast<int*>(area);
+    int* hs = hc + Bc;
+    float* hw = reinterpret_cast<float*>(hs + Bc * BLEND_MAX);
+    float* hv = hw + Bc * BLEND_MAX;
+    size_t at = 0;
+    for (int b = 0; b < B; ++b) {
+      const int n = blend->count[b];
+      hc[b] = n;
+      for (int k = 0; k < BLEND_MAX; ++k) {
+        hs[(size_t)b * BLEND_MAX + k] = k < n ? (int)blend->sid[at + k] : 0;
+        hw[(size_t)b * BLEND_MAX + k] = k < n ? blend->weight[at + k] : 0.f;
+      }
+      if (n > 0) at += (size_t)n;
+      if (n < 0) memcpy(hv + (size_t)b * gin_, blend->vector + (size_t)b * gin_, (size_t)gin_ * sizeof(float));
+    }
+  }
   ids_zc_ = pol_.ids_from_host((long)B * Ts);
-  if (!ids_zc_)
-    PE_HIP(hipMemcpyAsync(d_in_, h_in, in_head_bytes(Bc) + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int),
-                          hipMemcpyHostToDevice, stream_));
+  if (!ids_zc_) {
+    const size_t bytes = in_head_bytes(Bc) + (2 * Bc + in_scale_slots(Bc) + (size_t)B * Ts) * sizeof(int);
+    if (blended_) PE_HIP(hipMemcpyAsync(d_blend_, h_in - bl, bl + bytes, hipMemcpyHostToDevice, stream_));
+    else PE_HIP(hipMemcpyAsync(d_in_, h_in, bytes, hipMemcpyHostToDevice, stream_));
+  }
   plan_on_ = timing != nullptr;
   plan_skip_ = all_forced;
   if (timing) {
@@ -633,7 +664,7 @@ void Engine::run() {
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
     // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key(), seed_key());
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key(), seed_key(), blend_key());
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -669,8 +700,8 @@ void Engine::run() {
 // plan is present, the duration predictor is left out -- and nothing of the plan's values.
 std::string Engine::stage_a_key(int B) const {
   char key[200];
-  if (plan_on_) snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d|p%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, (int)plan_skip_, seed_key());
-  else snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, seed_key());
+  if (plan_on_) snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d|p%d%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, (int)plan_skip_, seed_key(), blend_key());
+  else snprintf(key, sizeof(key), "A|%d|%d|%d|%d|%d%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, seed_key(), blend_key());
   return key;
 }
 
@@ -887,6 +918,105 @@ void Engine::debug_timing(const float* logw, const int64_t* offsets, int batch, 
   }
 }
 
+// ---- speaker blends
+
+void Engine::check_blend(const BlendIn& blend, int B) const {
+  if (nspk_ <= 1) throw std::runtime_error("speaker blend on a single-speaker voice");
+  if (!blend.count) throw std::runtime_error("blend without a count array (pe_blend.count is null)");
+  size_t at = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = blend.count[b];
+    const std::string utt = "utterance " + std::to_string(b);
+    if (n < -1 || n > BLEND_MAX)
+      throw std::runtime_error(utt + ": blend count " + std::to_string(n) + " outside [-1, " + std::to_string(BLEND_MAX) + "]");
+    if (n < 0) {
+      if (!blend.vector) throw std::runtime_error(utt + ": count -1 without speaker vectors (pe_blend.vector is null)");
+      for (int i = 0; i < gin_; ++i)
+        if (!std::isfinite(blend.vector[(size_t)b * gin_ + i]))
+          throw std::runtime_error(utt + ": speaker vector element " + std::to_string(i) + " is not finite");
+    }
+    if (n > 0) {
+      if (!blend.sid || !blend.weight)
+        throw std::runtime_error(utt + ": " + std::to_string(n) + " blend components without " +
+                                 (blend.sid ? "weights (pe_blend.weight is null)" : "ids (pe_blend.sid is null)"));
+      for (int k = 0; k < n; ++k) {
+        const int64_t s = blend.sid[at + k];
+        if (s < 0 || s >= nspk_)
+          throw std::runtime_error(utt + ", blend component " + std::to_string(k) + ": speaker id " + std::to_string(s) +
+                                   " outside [0, num_speakers)");
+        if (!std::isfinite(blend.weight[at + k]))
+          throw std::runtime_error(utt + ", blend component " + std::to_string(k) + ": weight is not finite");
+      }
+      at += (size_t)n;
+    }
+  }
+}
+
+// speaker_blend_kernel's arguments for a blend area at `area` (host or device) laid out for capacity Bc
+BlendP Engine::blend_params(const char* area, size_t Bc) const {
+  BlendP p{};
+  p.emb_g = emb_g_; p.gin = gin_; p.sids = d_sids_;
+  p.count = reinterpret_cast<const int*>(area);
+  p.csid = p.count + Bc;
+  p.cw = reinterpret_cast<const float*>(p.csid + Bc * BLEND_MAX);
+  p.vec = p.cw + Bc * BLEND_MAX;
+  p.g = g_tab_; p.rows = g_rows_;
+  return p;
+}
+
+void Engine::speaker_embedding(int64_t sid, float* out, int64_t capacity) {
+  EntryLock entry_lock;
+  if (nspk_ <= 1) throw std::runtime_error("speaker embedding of a single-speaker voice");
+  if (sid < 0 || sid >= nspk_) throw std::runtime_error("speaker id outside [0, num_speakers)");
+  if (!out || capacity < gin_) throw std::runtime_error("speaker embedding: output holds fewer than gin values");
+  PE_HIP(hipSetDevice(device_));
+  PE_HIP(hipMemcpy(out, emb_g_ + (size_t)sid * gin_, (size_t)gin_ * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_blend(const BlendIn& blend, int batch, const int64_t* sids, float* out) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!out) throw std::runtime_error("null argument");
+  check_blend(blend, batch);
+  for (int b = 0; b < batch; ++b)
+    if (blend.count[b] == 0 && sids && (sids[b] < 0 || sids[b] >= nspk_))
+      throw std::runtime_error("utterance " + std::to_string(b) + ": speaker id outside [0, num_speakers)");
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  // one host image, one device block: [sids B | count B | component ids 8 B | weights 8 B | vectors B x gin | g B x gin]
+  const size_t B = (size_t)batch, G = (size_t)gin_, words = B * (18 + 2 * G);
+  std::vector<int> h(words, 0);
+  float* hf = reinterpret_cast<float*>(h.data());
+  size_t at = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const int n = blend.count[b];
+    h[b] = (n == 0 && sids) ? (int)sids[b] : 0;
+    h[B + b] = n;
+    for (int k = 0; k < n; ++k) {
+      h[2 * B + b * BLEND_MAX + k] = (int)blend.sid[at + k];
+      hf[10 * B + b * BLEND_MAX + k] = blend.weight[at + k];
+    }
+    if (n > 0) at += (size_t)n;
+    if (n < 0) memcpy(hf + 18 * B + b * G, blend.vector + b * G, G * sizeof(float));
+  }
+  DevBuf<int> dbuf;
+  dbuf.grow(words);
+  int* const dv = dbuf.get();
+  try {
+    PE_HIP(hipMemcpyAsync(dv, h.data(), words * sizeof(int), hipMemcpyHostToDevice, stream_));
+    BlendP p = blend_params(reinterpret_cast<const char*>(dv + B), B);
+    p.sids = dv;
+    p.g = reinterpret_cast<float*>(dv) + B * (18 + G);
+    p.rows = nullptr;
+    launch::speaker_blend(stream_, batch, p);
+    PE_HIP(hipMemcpyAsync(out, p.g, B * G * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)
+    throw;
+  }
+}
+
 const std::vector<int32_t>& Engine::durations_host() {
   EntryLock entry_lock;
   finish_run();
@@ -948,6 +1078,18 @@ void Engine::debug_tensor(const std::string& name, int b, std::vector<float>& ou
   else if (name == "noise_z") {
     if (sb_active_) throw std::runtime_error("noise_z is not available during a batch stream (its buffer holds the windows)");
     src = noise_z_ + (size_t)b * C_ * Fs_; R = C_; Cn = frames_h_[b]; stride = Fs_;
+  }
+  else if (name == "g") {
+    // the speaker vector utterance b used: its row of the blended call's table, else the table row of its id
+    if (nspk_ <= 1) throw std::runtime_error("g is only available for a multi-speaker voice");
+    if (b < 0 || b >= B_) throw std::runtime_error("utterance outside [0, batch)");
+    if (blended_) src = g_tab_ + (size_t)b * gin_;
+    else {
+      int sid = 0;
+      PE_HIP(hipMemcpy(&sid, d_sids_ + b, sizeof(int), hipMemcpyDeviceToHost));
+      src = emb_g_ + (size_t)sid * gin_;
+    }
+    R = 1; Cn = gin_; stride = gin_;
   }
   else if (name == "audio") { src = audio_ + (size_t)b * Ss_; R = 1; Cn = frames_h_[b] * hop_; stride = Ss_; }
   else if (name == "pool_z" || name == "pool_cond") {

@@ -71,6 +71,15 @@ struct SeedsIn {
   const uint8_t* use = nullptr;
 };
 
+// Per-utterance speaker blends and caller-supplied speaker vectors (include/piper_hip.h: pe_blend). Host
+// pointers: count[B]; sid / weight, the components of all utterances concatenated in utterance order; vector[B][gin].
+struct BlendIn {
+  const int32_t* count = nullptr;
+  const int64_t* sid = nullptr;
+  const float* weight = nullptr;
+  const float* vector = nullptr;
+};
+
 // Where the packed voice weights live. Default: one device allocation owned by the engine. A caller-provided arena
 // (multi-GPU: a device buffer the host framework can hand to RCCL) receives them instead; with `skeleton` the engine only
 // lays the arena out (same offsets as on the packing rank, derived from tensor shapes alone) and waits for its content
@@ -97,11 +106,22 @@ class Engine {
   // stays with the uploaded inputs -- every run() on them follows it -- and goes with the next upload.
   // seeds: per-utterance noise seeds, checked like the plan. They stay with the uploaded inputs -- every run() on them draws
   // the same noise again -- and go with the next upload of any kind.
+  // blend: per-utterance speaker blends / vectors, checked like the plan (check_blend); they stay with the uploaded inputs
+  // and go with the next upload of any kind.
   void upload(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
               const int64_t* sids, const NoiseIn* noise, bool per_utt = false, const TimingIn* timing = nullptr,
-              const SeedsIn* seeds = nullptr);
+              const SeedsIn* seeds = nullptr, const BlendIn* blend = nullptr);
   bool timed() const { return plan_on_; }
   bool seeded() const { return seeded_; }
+  bool blended() const { return blended_; }
+  // Refuses a blend the law does not cover -- a single-speaker voice, a count outside [-1, PE_BLEND_MAX], a component id
+  // outside [0, num_speakers), a weight or vector element that is not finite, a missing array -- naming the utterance and
+  // the component. Changes nothing of the engine.
+  void check_blend(const BlendIn& blend, int B) const;
+  int speaker_dim() const { return nspk_ > 1 ? gin_ : 0; }
+  void speaker_embedding(int64_t sid, float* out, int64_t capacity);
+  // test hook: speaker_blend_kernel alone, out[batch][gin] (sids may be null: 0)
+  void debug_blend(const BlendIn& blend, int batch, const int64_t* sids, float* out);
   // test hook: duration_plan_kernel alone on caller-given logw rows (concatenated like ids, offsets[batch + 1]) with one
   // scales triple per utterance: the durations and w (concatenated) and the frame counts
   void debug_timing(const float* logw, const int64_t* offsets, int batch, const float* scales, const TimingIn* timing,
@@ -117,7 +137,7 @@ class Engine {
   // with the generator's exact receptive half-width, so the concatenated chunks equal the unchunked
   // waveform (the reference pads by a heuristic 5-10 frames and does not). Returns false when done.
   int stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise,
-                   const TimingIn* timing = nullptr, const SeedsIn* seeds = nullptr);
+                   const TimingIn* timing = nullptr, const SeedsIn* seeds = nullptr, const BlendIn* blend = nullptr);
   bool stream_next(int chunk_frames, const float** audio, const int16_t** pcm, int64_t* nsamples);
   // halo of a stream window in frames: the generator's receptive half-width, plus one frame while an output rate is set
   // (the resampler needs exact native samples up to K <= hop beyond a chunk's edges)
@@ -238,7 +258,7 @@ class Engine {
   };
   const std::vector<int32_t>& stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
                                                  const int64_t* sids, const NoiseIn* noise, const TimingIn* timing = nullptr,
-                                                 const SeedsIn* seeds = nullptr);
+                                                 const SeedsIn* seeds = nullptr, const BlendIn* blend = nullptr);
   void stream_next_batch(int chunk_frames, bool want_audio, StreamChunk& out);
 
   // Stream pool: a fixed number of slots whose latents and decoder conditioning rows live in storage OWNED BY THE POOL,
@@ -254,7 +274,7 @@ class Engine {
   int stream_pool_open(int slots, int max_frames);                 // returns the halo in frames
   void stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
                         const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing = nullptr,
-                        const SeedsIn* seeds = nullptr);
+                        const SeedsIn* seeds = nullptr, const BlendIn* blend = nullptr);
   void stream_pool_next(int chunk_frames, const int32_t* per_slot, bool want_audio, StreamChunk& out);   // out.batch == slots
   void stream_pool_leave(int slot);
   void stream_pool_close();
@@ -597,6 +617,20 @@ class Engine {
   // workspace (d_in_) mirrored by a pinned host block (h_in_): upload() fills the host block and enqueues ONE copy, no
   // synchronisation (the pinned block outlives the copy; the call's final synchronisation covers it)
   char* d_in_ = nullptr; PinBuf<char> h_in_; size_t in_bytes_ = 0;
+  // Speaker blends of the uploaded inputs lie IN FRONT of that block, in the same allocation and in the same
+  // pinned mirror: [count Bc | component ids Bc x 8 | weights Bc x 8 | vectors Bc x gin], padded to 256 bytes, then d_in_
+  // (h_in()). A copied call that carries a blend starts its one copy at the area, every other call at d_in_ as ever; a
+  // zero-copy call's speaker_blend_kernel reads the pinned area in place. 68 + 4 gin bytes per utterance of the capacity
+  // bucket, nothing for a single-speaker voice. The kernel writes g_tab_ [Bc][gin] and g_rows_ [Bc] (rows[b] = b), which
+  // cond_kernel reads in place of the table and the ids. The VALUES are data; whether the call carries a blend at all
+  // adds a launch and is part of the graph keys (blend_key), so a plain call's graphs are what they always were.
+  size_t in_blend_bytes(size_t Bc) const { return nspk_ > 1 ? (Bc * (68 + 4 * (size_t)gin_) + 255) & ~(size_t)255 : 0; }
+  char* h_in() const { return h_in_.get() + in_blend_bytes(capA_B_); }
+  char* d_blend_ = nullptr;
+  float* g_tab_ = nullptr; int* g_rows_ = nullptr;
+  bool blended_ = false;
+  const char* blend_key() const { return blended_ ? "|g" : ""; }
+  BlendP blend_params(const char* area, size_t Bc) const;
   // short calls: no copy at all -- embed_kernel reads the pinned block in place (policy.h: ids_from_host)
   bool ids_zc_ = false;
   unsigned long long upload_serial_ = 0;

@@ -53,15 +53,15 @@ void Engine::issue_stage_a() {
     ep.out = x_; ep.o_bs = (long)H_ * Ts; ep.o_cs = Ts; ep.rng = d_rng_;
     if (ids_zc_) {
       const size_t Bc = capA_B_;
-      ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in_.get());
-      ep.h_lens = reinterpret_cast<const int*>(h_in_.get() + in_head_bytes(Bc));
+      ep.h_rng = reinterpret_cast<const unsigned long long*>(h_in());
+      ep.h_lens = reinterpret_cast<const int*>(h_in() + in_head_bytes(Bc));
       ep.h_sids = ep.h_lens + Bc;
       ep.h_scales = reinterpret_cast<const float*>(ep.h_sids + Bc);
       ep.h_ids = ep.h_sids + Bc + in_scale_slots(Bc);
       ep.d_lens = d_tlens_; ep.d_sids = d_sids_; ep.d_scales = d_scales_;
       if (seeded_) {
-        ep.h_keys = reinterpret_cast<const unsigned long long*>(h_in_.get() + 32);
-        ep.h_use = reinterpret_cast<const int*>(h_in_.get() + 32 + 8 * Bc);
+        ep.h_keys = reinterpret_cast<const unsigned long long*>(h_in() + 32);
+        ep.h_use = reinterpret_cast<const int*>(h_in() + 32 + 8 * Bc);
       }
     }
     if (seeded_) { ep.keys = d_keys_; ep.use = d_use_; }
@@ -75,8 +75,19 @@ void Engine::issue_stage_a() {
   // ================= speaker conditioning vectors
   const float* cb_dp = nullptr;
   if (nspk_ > 1) {
+    // a call that carries a blend: its speaker vectors g[B][gin] first (one launch), which the cond launches then read with
+    // the row index in place of the speaker id -- their arithmetic is the plain call's. The blend's values lie where the
+    // input block lies: read in place from the pinned block by a zero-copy call, from its device copy otherwise.
+    const float* gtab = emb_g_;
+    const int* grow = d_sids_;
+    if (blended_) {
+      const size_t Bc = capA_B_;
+      const BlendP bp = blend_params(ids_zc_ ? h_in() - in_blend_bytes(Bc) : d_blend_, Bc);
+      PE_LAUNCH_K("speaker_blend_kernel", launch::speaker_blend(stream_, B, bp));
+      gtab = g_tab_; grow = g_rows_;
+    }
     auto cond = [&](const CondW& c, int off) {
-      PE_LAUNCH_K("cond_kernel", launch::cond(dim3((c.rows + 127) / 128, B), stream_, emb_g_, gin_, d_sids_, c.w, c.b, c.rows, cond_ + off, cond_bs_));
+      PE_LAUNCH_K("cond_kernel", launch::cond(dim3((c.rows + 127) / 128, B), stream_, gtab, gin_, grow, c.w, c.b, c.rows, cond_ + off, cond_bs_));
     };
     cond(cond_dp_, cond_off_dp_);
     for (size_t i = 0; i < cond_wn_.size(); ++i) cond(cond_wn_[i], cond_off_wn_[i]);

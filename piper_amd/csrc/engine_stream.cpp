@@ -5,11 +5,11 @@
 namespace pe {
 
 int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise,
-                         const TimingIn* timing, const SeedsIn* seeds) {
+                         const TimingIn* timing, const SeedsIn* seeds, const BlendIn* blend) {
   EntryLock entry_lock;
   const int64_t offs[2] = {0, n};
   const int64_t sids[1] = {sid < 0 ? 0 : sid};
-  upload(ids, offs, 1, scales, sids, noise, false, timing, seeds);
+  upload(ids, offs, 1, scales, sids, noise, false, timing, seeds, blend);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   stream_front(1, 0);
@@ -144,9 +144,9 @@ void Engine::stream_front(int B, int max_frames) {
 
 const std::vector<int32_t>& Engine::stream_begin_batch(const int64_t* ids, const int64_t* offsets, int B, const float* scales,
                                                        const int64_t* sids, const NoiseIn* noise, const TimingIn* timing,
-                                                       const SeedsIn* seeds) {
+                                                       const SeedsIn* seeds, const BlendIn* blend) {
   EntryLock entry_lock;
-  upload(ids, offsets, B, scales, sids, noise, true, timing, seeds);
+  upload(ids, offsets, B, scales, sids, noise, true, timing, seeds, blend);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent too)
@@ -332,10 +332,11 @@ void Engine::stream_pool_leave(int slot) {
 
 void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n, const float* scales, const int64_t* sids,
                               const NoiseIn* noise, int32_t* slot_of, int32_t* total_frames, const TimingIn* timing,
-                              const SeedsIn* seeds) {
+                              const SeedsIn* seeds, const BlendIn* blend) {
   EntryLock entry_lock;
   stream_pool_require();
   if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
+  if (blend) check_blend(*blend, n);
   if (n < 1) throw std::runtime_error("batch size must be in [1, 4096]");
   std::vector<int> take;
   for (int s = 0; s < sp_slots_ && (int)take.size() < n; ++s)
@@ -353,7 +354,7 @@ void Engine::stream_pool_join(const int64_t* ids, const int64_t* offsets, int n,
       if (timing->target[j] > sp_maxf_)
         throw std::runtime_error("utterance " + std::to_string(j) + " has a target of " + std::to_string(timing->target[j]) +
                                  " frames, the stream pool holds at most " + std::to_string(sp_maxf_) + " (max_frames)");
-  upload(ids, offsets, n, scales, sids, noise, true, timing, seeds);
+  upload(ids, offsets, n, scales, sids, noise, true, timing, seeds, blend);
   PE_HIP(hipSetDevice(device_));
   spec_pending_ = false;
   s_active_ = false;                                   // (a one-utterance stream on this handle loses its latent)

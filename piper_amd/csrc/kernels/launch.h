@@ -64,6 +64,8 @@ void regulate(dim3 grid, hipStream_t stream, const RegP& p);
 void xcc_probe(hipStream_t stream, int* out64);       // 64 workgroups, out64[i] = XCC id of workgroup i
 void cond(dim3 grid, hipStream_t stream, const float* emb_g, int gin, const int* sids, const float* w, const float* bias,
           int rows, float* out, int o_bs);
+// g[batch][gin] of a call that carries a blend (glue.h): 64 lanes along gin per workgroup, one grid row per utterance
+void speaker_blend(hipStream_t stream, int batch, const BlendP& p);
 
 // ---- vocoder stage kernels and the generator tail (launch_tail.cpp)
 void init_tail();

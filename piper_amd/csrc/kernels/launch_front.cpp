@@ -121,6 +121,10 @@ void cond(dim3 grid, hipStream_t stream, const float* emb_g, int gin, const int*
   PE_LAUNCH(cond_kernel, grid, dim3(128), 0, stream, emb_g, gin, sids, w, bias, rows, out, o_bs);
 }
 
+void speaker_blend(hipStream_t stream, int batch, const BlendP& p) {
+  PE_LAUNCH(speaker_blend_kernel, dim3((unsigned)((p.gin + 63) / 64), (unsigned)batch), dim3(64), 0, stream, p);
+}
+
 }  // namespace launch
 }  // namespace pe
 

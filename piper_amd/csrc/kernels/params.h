@@ -203,6 +203,18 @@ struct EmbedP {
   const unsigned long long* h_keys; const int* h_use;
 };
 
+// ---- speaker vectors of a blended call (glue.h: speaker_blend_kernel)
+static constexpr int BLEND_MAX = 8;            // components per utterance (include/piper_hip.h: PE_BLEND_MAX)
+struct BlendP {
+  const float* emb_g; int gin;                 // the speaker table [num_speakers][gin]
+  const int* sids;                             // [B] device speaker ids (count 0)
+  const int* count;                            // [B]  0 plain id, 1..BLEND_MAX components, -1 row b of vec
+  const int* csid; const float* cw;            // [B][BLEND_MAX] components, the first count[b] of a row are used
+  const float* vec;                            // [B][gin] caller-supplied vectors
+  float* g;                                    // out [B][gin]
+  int* rows;                                   // out [B] rows[b] = b: cond_kernel's index into g (null: not written)
+};
+
 // ---- durations, N(0,1) generator, length regulator (duration.h)
 static constexpr int MAX_FRAMES = 60000;      // per-utterance activations stay below the 2 GiB descriptor range
 struct DurP {

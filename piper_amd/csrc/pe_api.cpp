@@ -76,6 +76,12 @@ static const pe::SeedsIn* to_seeds(const pe_seeds* s, pe::SeedsIn& out) {
   return &out;
 }
 
+static const pe::BlendIn* to_blend(const pe_blend* b, pe::BlendIn& out) {
+  if (!b) return nullptr;
+  out.count = b->count; out.sid = b->sid; out.weight = b->weight; out.vector = b->vector;
+  return &out;
+}
+
 extern "C" {
 
 const char* pe_last_error(void) { return g_err.c_str(); }
@@ -218,6 +224,44 @@ int pe_upload_seeded(pe_engine* e, const int64_t* ids, const int64_t* offsets, i
   });
 }
 
+int pe_upload_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                      const int64_t* sids, const pe_noise* noise, const pe_timing* timing, const pe_seeds* seeds,
+                      const pe_blend* blend) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    pe::BlendIn bl;
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t), to_seeds(seeds, s),
+                   to_blend(blend, bl));
+  });
+}
+
+int pe_get_speaker_dim(pe_engine* e, int32_t* gin) {
+  return guard([&] {
+    if (!e || !gin) throw std::runtime_error("null argument");
+    *gin = e->eng->speaker_dim();
+  });
+}
+
+int pe_get_speaker_embedding(pe_engine* e, int64_t sid, float* out, int64_t capacity) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->speaker_embedding(sid, out, capacity);
+  });
+}
+
+int pe_debug_blend(pe_engine* e, const pe_blend* blend, int32_t batch, const int64_t* sids, float* out) {
+  return guard([&] {
+    if (!e || !blend) throw std::runtime_error("null argument");
+    pe::BlendIn bl;
+    e->eng->debug_blend(*to_blend(blend, bl), batch, sids, out);
+  });
+}
+
 int pe_run(pe_engine* e) {
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
@@ -304,6 +348,27 @@ int pe_synthesize_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t* 
   });
 }
 
+int pe_synthesize_batch_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, pe_result* result, const pe_timing* timing,
+                                const pe_seeds* seeds, const pe_blend* blend) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    pe::BlendIn bl;
+    const pe::SeedsIn* sp = to_seeds(seeds, s);
+    const auto t0 = std::chrono::steady_clock::now();
+    e->eng->upload(ids, offsets, batch, scales, sids, noise ? &n : nullptr, true, to_timing(timing, t), sp, to_blend(blend, bl));
+    e->eng->run();
+    e->eng->download(true, true);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fill_result(e, result, secs);
+  });
+}
+
 int pe_synthesize(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                   const pe_noise* noise, pe_result* result) {
   if (!e) {
@@ -340,6 +405,23 @@ int pe_stream_begin_seeded(pe_engine* e, const int64_t* ids, int64_t n_ids, cons
     pe::TimingIn t;
     pe::SeedsIn s;
     const int f = e->eng->stream_begin(ids, n_ids, scales, sid, noise ? &n : nullptr, to_timing(timing, t), to_seeds(seeds, s));
+    if (total_frames) *total_frames = f;
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
+int pe_stream_begin_blended(pe_engine* e, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                            const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames, const pe_timing* timing,
+                            const pe_seeds* seeds, const pe_blend* blend) {
+  return guard([&] {
+    if (!e || !ids || !scales) throw std::runtime_error("null argument");
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    pe::BlendIn bl;
+    const int f = e->eng->stream_begin(ids, n_ids, scales, sid, noise ? &n : nullptr, to_timing(timing, t), to_seeds(seeds, s),
+                                       to_blend(blend, bl));
     if (total_frames) *total_frames = f;
     if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
   });
@@ -393,6 +475,24 @@ int pe_stream_begin_batch_seeded(pe_engine* e, const int64_t* ids, const int64_t
     pe::SeedsIn s;
     const std::vector<int32_t>& f = e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr,
                                                                to_timing(timing, t), to_seeds(seeds, s));
+    if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
+    if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
+  });
+}
+
+int pe_stream_begin_batch_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
+                                  const int64_t* sids, const pe_noise* noise, int32_t* total_frames, int32_t* halo_frames,
+                                  const pe_timing* timing, const pe_seeds* seeds, const pe_blend* blend) {
+  return guard([&] {
+    if (!e || !ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, batch, 4096);
+    pe::NoiseIn n;
+    to_noise(noise, n);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    pe::BlendIn bl;
+    const std::vector<int32_t>& f = e->eng->stream_begin_batch(ids, offsets, batch, scales, sids, noise ? &n : nullptr,
+                                                               to_timing(timing, t), to_seeds(seeds, s), to_blend(blend, bl));
     if (total_frames) memcpy(total_frames, f.data(), (size_t)batch * sizeof(int32_t));
     if (halo_frames) *halo_frames = e->eng->decoder_halo_frames();
   });
@@ -461,6 +561,24 @@ int pe_stream_pool_join_seeded(pe_engine* e, const int64_t* ids, const int64_t* 
     pe::SeedsIn s;
     e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames, to_timing(timing, t),
                              to_seeds(seeds, s));
+  });
+}
+
+int pe_stream_pool_join_blended(pe_engine* e, const int64_t* ids, const int64_t* offsets, int32_t n, const float* scales,
+                                const int64_t* sids, const pe_noise* noise, int32_t* slot_of, int32_t* total_frames,
+                                const pe_timing* timing, const pe_seeds* seeds, const pe_blend* blend) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->stream_pool_require();
+    if (!ids || !offsets) throw std::runtime_error("null argument");
+    check_scales(scales, n, 4096);
+    pe::NoiseIn nz;
+    to_noise(noise, nz);
+    pe::TimingIn t;
+    pe::SeedsIn s;
+    pe::BlendIn bl;
+    e->eng->stream_pool_join(ids, offsets, n, scales, sids, noise ? &nz : nullptr, slot_of, total_frames, to_timing(timing, t),
+                             to_seeds(seeds, s), to_blend(blend, bl));
   });
 }
 
@@ -1080,12 +1198,22 @@ pe_engine* pe_group_engine(pe_group* g, int32_t i) {
 // pe_group_synthesize_batch(_scaled, _seeded): scales = one triple for the whole call, or (per_utt) [batch][3]; seeds = the
 // caller's pe_seeds or null
 static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch, const float* scales,
-                            bool per_utt, const int64_t* sids, pe_result* result, const pe_seeds* seeds = nullptr) {
+                            bool per_utt, const int64_t* sids, pe_result* result, const pe_seeds* seeds = nullptr,
+                            const pe_blend* blend = nullptr) {
   return guard([&] {
     if (!g || !ids || !offsets || (!per_utt && !scales)) throw std::runtime_error("null argument");
     if (seeds && !seeds->seed) throw std::runtime_error("seeds without a seed array (pe_seeds.seed is null)");
     const int n = (int)g->eng.size();
     if (per_utt) check_scales(scales, batch, (int64_t)4096 * n);
+    // (a blend is checked as a whole, with the caller's utterance numbers, before the deal; the members share one voice)
+    std::vector<size_t> blend_at;                 // first component of utterance u
+    if (blend) {
+      if (batch < 1 || (int64_t)batch > (int64_t)4096 * n) throw std::runtime_error("batch size must be in [1, 4096 per engine]");
+      pe::BlendIn bl;
+      g->eng[0]->eng->check_blend(*to_blend(blend, bl), batch);
+      blend_at.assign((size_t)batch + 1, 0);
+      for (int u = 0; u < batch; ++u) blend_at[u + 1] = blend_at[u] + (size_t)std::max(blend->count[u], 0);
+    }
     // the offsets are the caller's: check them BEFORE they size a copy (the same rules and messages as Engine::upload,
     // which would only see them after the deal)
     if (batch < 1 || (int64_t)batch > (int64_t)4096 * n)
@@ -1130,6 +1258,9 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
       std::vector<float> scales;                // [shard][3] (per-utterance calls)
       std::vector<uint64_t> seed;               // [shard] (seeded calls), and whether each utterance uses its seed
       std::vector<uint8_t> use;
+      std::vector<int32_t> bcount;              // [shard] (blended calls): counts, components, vectors of its utterances
+      std::vector<int64_t> bsid;
+      std::vector<float> bweight, bvector;
       pe_result res{};
       int rc = 0;
       std::string err;
@@ -1148,6 +1279,17 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
           w.seed.push_back(seeds->seed[u]);
           w.use.push_back(seeds->use ? seeds->use[u] : (uint8_t)1);
         }
+        if (blend) {
+          const int gin = g->eng[0]->eng->speaker_dim();
+          const int c = blend->count[u];
+          w.bcount.push_back(c);
+          for (int k = 0; k < c; ++k) {
+            w.bsid.push_back(blend->sid[blend_at[u] + k]);
+            w.bweight.push_back(blend->weight[blend_at[u] + k]);
+          }
+          if (c < 0) w.bvector.insert(w.bvector.end(), blend->vector + (size_t)u * gin, blend->vector + (size_t)(u + 1) * gin);
+          else w.bvector.insert(w.bvector.end(), (size_t)gin, 0.f);
+        }
       }
     }
     // a shard = upload + device pipeline + int16 PCM to the host; the float waveform stays on the device (the group
@@ -1158,8 +1300,9 @@ static int group_synthesize(pe_group* g, const int64_t* ids, const int64_t* offs
       try {
         pe::Engine* e = g->eng[i]->eng;
         const pe::SeedsIn sd{w.seed.data(), w.use.data()};
+        const pe::BlendIn bd{w.bcount.data(), w.bsid.data(), w.bweight.data(), w.bvector.data()};
         e->upload(w.ids.data(), w.off.data(), (int)shard[i].size(), per_utt ? w.scales.data() : scales,
-                  sids ? w.sids.data() : nullptr, nullptr, per_utt, nullptr, seeds ? &sd : nullptr);
+                  sids ? w.sids.data() : nullptr, nullptr, per_utt, nullptr, seeds ? &sd : nullptr, blend ? &bd : nullptr);
         e->run();
         e->download(false, true);
         fill_result(g->eng[i], &w.res, 0.0);
@@ -1235,6 +1378,12 @@ int pe_group_synthesize_batch_seeded(pe_group* g, const int64_t* ids, const int6
   return group_synthesize(g, ids, offsets, batch, scales, true, sids, result, seeds);
 }
 
+int pe_group_synthesize_batch_blended(pe_group* g, const int64_t* ids, const int64_t* offsets, int32_t batch,
+                                      const float* scales, const int64_t* sids, pe_result* result, const pe_seeds* seeds,
+                                      const pe_blend* blend) {
+  return group_synthesize(g, ids, offsets, batch, scales, true, sids, result, seeds, blend);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // pe_coalescer_*: concurrent single-utterance requests of many caller threads as batched engine calls (include/piper_hip.h)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1248,6 +1397,8 @@ struct pe_coalescer {
   struct Req {
     const int64_t* ids; int64_t n; float scales[3]; int64_t sid;
     bool seeded = false; uint64_t seed = 0;      // pe_coalescer_synthesize_seeded with a seed
+    // pe_coalescer_synthesize_blended with a blend: the request's count and its own copies of components or vector
+    int32_t bcount = 0; std::vector<int64_t> bsid; std::vector<float> bweight, bvector;
     int16_t* pcm = nullptr; int64_t samples = 0; int32_t frames = 0; double secs = 0; int32_t batch = 0;
     int state = 0;            // 0 queued, 1 taken by a leader, 2 done, 3 failed
     std::string err;
@@ -1313,6 +1464,13 @@ int pe_coalescer_synthesize(pe_coalescer* c, const int64_t* ids, int64_t n_ids, 
 int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
                                    const uint64_t* seed, int16_t** pcm, int64_t* n_samples, int32_t* frames,
                                    double* infer_seconds, int32_t* batch_size) {
+  return pe_coalescer_synthesize_blended(c, ids, n_ids, scales, sid, seed, nullptr, pcm, n_samples, frames, infer_seconds,
+                                         batch_size);
+}
+
+int pe_coalescer_synthesize_blended(pe_coalescer* c, const int64_t* ids, int64_t n_ids, const float scales[3], int64_t sid,
+                                    const uint64_t* seed, const pe_blend* blend, int16_t** pcm, int64_t* n_samples,
+                                    int32_t* frames, double* infer_seconds, int32_t* batch_size) {
   return guard([&] {
     if (!c || !ids || !scales || !pcm || !n_samples) throw std::runtime_error("null argument");
     if (n_ids <= 0) throw std::runtime_error("empty phoneme id sequence");
@@ -1322,6 +1480,18 @@ int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t 
     me.ids = ids; me.n = n_ids; me.sid = sid;
     memcpy(me.scales, scales, sizeof(me.scales));
     if (seed) { me.seeded = true; me.seed = *seed; }
+    if (blend) {
+      // (refused here, as the request's own utterance 0, before it is queued: a merged call must not fail for one member)
+      pe::BlendIn bl;
+      pe::Engine* eng = c->eng->eng;
+      eng->check_blend(*to_blend(blend, bl), 1);
+      me.bcount = blend->count[0];
+      if (me.bcount > 0) {
+        me.bsid.assign(blend->sid, blend->sid + me.bcount);
+        me.bweight.assign(blend->weight, blend->weight + me.bcount);
+      }
+      if (me.bcount < 0) me.bvector.assign(blend->vector, blend->vector + eng->speaker_dim());
+    }
     std::unique_lock<std::mutex> lk(c->m);
     // Whatever ends this call -- also an exception between taking the lead and the engine call (std::bad_alloc of the
     // batch vector) -- `me` must leave the queue, a lead must be given up, and requests this thread had taken must fail
@@ -1382,7 +1552,19 @@ int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t 
           std::vector<uint64_t> seed;
           std::vector<uint8_t> use;
           bool any_seed = false;
+          // blended and plain requests share the call too (no blended request: the plain call)
+          std::vector<int32_t> bcount;
+          std::vector<int64_t> bsid;
+          std::vector<float> bweight, bvector;
+          bool any_blend = false;
+          const size_t gin = (size_t)c->eng->eng->speaker_dim();
           for (auto* r : take) {
+            bcount.push_back(r->bcount);
+            bsid.insert(bsid.end(), r->bsid.begin(), r->bsid.end());
+            bweight.insert(bweight.end(), r->bweight.begin(), r->bweight.end());
+            if (r->bcount < 0) bvector.insert(bvector.end(), r->bvector.begin(), r->bvector.end());
+            else bvector.insert(bvector.end(), gin, 0.f);
+            any_blend = any_blend || r->bcount != 0;
             seed.push_back(r->seed);
             use.push_back(r->seeded ? 1 : 0);
             any_seed = any_seed || r->seeded;
@@ -1394,8 +1576,9 @@ int pe_coalescer_synthesize_seeded(pe_coalescer* c, const int64_t* ids, int64_t 
           const auto t0 = std::chrono::steady_clock::now();
           pe::Engine* e = c->eng->eng;
           const pe::SeedsIn sd{seed.data(), use.data()};
+          const pe::BlendIn bd{bcount.data(), bsid.data(), bweight.data(), bvector.data()};
           e->upload(cat.data(), off.data(), (int)take.size(), sc.data(), sids.data(), nullptr, true, nullptr,
-                    any_seed ? &sd : nullptr);            // one triple per request
+                    any_seed ? &sd : nullptr, any_blend ? &bd : nullptr);            // one triple per request
           e->run();
           e->download(false, true);
           const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

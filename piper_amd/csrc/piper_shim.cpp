@@ -378,18 +378,39 @@ static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) 
   }
 }
 
-// pe_upload, or with SynthesisConfig::seed pe_upload_seeded: utterance k of the call gets seed + first + k (wrapping)
+// pe_upload, or with SynthesisConfig::seed pe_upload_seeded: utterance k of the call gets seed + first + k (wrapping); with
+// SynthesisConfig::speakerBlend / ::speakerVector pe_upload_blended: every utterance of the call gets that blend or vector
 static int upload_utterances(pe_engine* engine, const PhonemeId* ids, const int64_t* offsets, int32_t batch, const float scales[3],
-                             const int64_t* sids, const std::optional<uint64_t>& seed, uint64_t first) {
-  if (!seed) return pe_upload(engine, ids, offsets, batch, scales, sids, nullptr);
+                             const int64_t* sids, const SynthesisConfig& sc, uint64_t first) {
+  const std::optional<uint64_t>& seed = sc.seed;
+  const bool blend = !sc.speakerBlend.empty(), vec = !sc.speakerVector.empty();
+  if (blend && vec) throw std::runtime_error("SynthesisConfig: speakerBlend and speakerVector are both set");
+  if ((blend || vec) && sc.speakerId) throw std::runtime_error("SynthesisConfig: speakerId is set beside a speaker blend or vector");
+  if (!seed && !blend && !vec) return pe_upload(engine, ids, offsets, batch, scales, sids, nullptr);
   std::vector<float> per((size_t)batch * 3);
   std::vector<uint64_t> keys((size_t)batch);
   for (int32_t k = 0; k < batch; ++k) {
     for (int j = 0; j < 3; ++j) per[(size_t)k * 3 + j] = scales[j];
-    keys[(size_t)k] = *seed + first + (uint64_t)k;
+    if (seed) keys[(size_t)k] = *seed + first + (uint64_t)k;
   }
   const pe_seeds s{keys.data(), nullptr};
-  return pe_upload_seeded(engine, ids, offsets, batch, per.data(), sids, nullptr, nullptr, &s);
+  if (!blend && !vec) return pe_upload_seeded(engine, ids, offsets, batch, per.data(), sids, nullptr, nullptr, &s);
+  if (blend && sc.speakerBlend.size() > (size_t)PE_BLEND_MAX)
+    throw std::runtime_error("SynthesisConfig: speakerBlend has more than " + std::to_string((int)PE_BLEND_MAX) + " components");
+  int32_t gin = 0;
+  check(pe_get_speaker_dim(engine, &gin));
+  if (vec && (int64_t)sc.speakerVector.size() != (int64_t)gin)
+    throw std::runtime_error("SynthesisConfig: speakerVector has " + std::to_string(sc.speakerVector.size()) + " values, the voice's speaker vectors have " +
+                             std::to_string(gin));
+  std::vector<int32_t> count((size_t)batch, blend ? (int32_t)sc.speakerBlend.size() : -1);
+  std::vector<int64_t> bsid;
+  std::vector<float> bweight, bvector;
+  for (int32_t k = 0; k < batch; ++k) {
+    for (auto& c : sc.speakerBlend) { bsid.push_back((int64_t)c.first); bweight.push_back(c.second); }
+    bvector.insert(bvector.end(), sc.speakerVector.begin(), sc.speakerVector.end());
+  }
+  const pe_blend b{count.data(), bsid.data(), bweight.data(), vec ? bvector.data() : nullptr};
+  return pe_upload_blended(engine, ids, offsets, batch, per.data(), nullptr, nullptr, nullptr, seed ? &s : nullptr, &b);
 }
 
 void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisConfig, ModelSession& session,
@@ -405,7 +426,7 @@ void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisCo
   // memory, result available in host memory = upload + device pipeline + fetch. The copy into the caller's vector
   // is outside, like the reference's conversion loops (:410-431; the int16 conversion itself runs on the GPU).
   const auto t0 = std::chrono::steady_clock::now();
-  check(upload_utterances(session.engine, phonemeIds.data(), offsets, 1, scales, sids, synthesisConfig.seed, 0));
+  check(upload_utterances(session.engine, phonemeIds.data(), offsets, 1, scales, sids, synthesisConfig, 0));
   check(pe_run(session.engine));
   pe_result r;
   check(pe_fetch(session.engine, 0, 1, &r));
@@ -433,7 +454,7 @@ void synthesizeBatch(std::vector<std::vector<PhonemeId>>& phonemeIdLists, Synthe
   }
   const auto t0 = std::chrono::steady_clock::now();     // same span as synthesize(): upload + pipeline + fetch
   check(upload_utterances(session.engine, flat.data(), offsets.data(), nb, scales,
-                          synthesisConfig.speakerId ? sids.data() : nullptr, synthesisConfig.seed, 0));
+                          synthesisConfig.speakerId ? sids.data() : nullptr, synthesisConfig, 0));
   check(pe_run(session.engine));
   pe_result r;
   check(pe_fetch(session.engine, 0, 1, &r));
@@ -573,7 +594,7 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
     const auto t0 = std::chrono::steady_clock::now();
     // (with SynthesisConfig::seed phrase k of the whole text gets seed + k, whatever group it lands in)
     check(upload_utterances(voice.session.engine, flat.data(), offsets.data(), (int32_t)(g.p1 - g.p0), scales,
-                            sc.speakerId ? sids.data() : nullptr, sc.seed, (uint64_t)g.p0));
+                            sc.speakerId ? sids.data() : nullptr, sc, (uint64_t)g.p0));
     check(pe_run(voice.session.engine));
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   };

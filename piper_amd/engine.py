@@ -102,6 +102,66 @@ def pack_seeds(seeds, batch: int, keep: list):
     return C.byref(s)
 
 
+def pack_speakers(speakers, sids, batch: int, gin: int, keep: list):
+    """-> (sids, blend): the plain speaker ids of a call and the C struct (by reference) of its speaker blends
+    (include/piper_hip.h: pe_blend), or ``(sids, None)`` as given when no utterance carries a blend or a vector.
+    ``speakers``: one entry per utterance -- None or an int, a plain id like ``sids``; a mapping ``{sid: weight}`` or a
+    sequence of ``(sid, weight)`` pairs, a blend whose components keep their order (a dict's insertion order); a 1-D float
+    array of ``gin`` values, a speaker vector. An utterance may not have both a ``sids`` entry and a ``speakers`` entry."""
+    if speakers is None:
+        return sids, None
+    speakers = list(speakers)
+    if len(speakers) != batch:
+        raise ValueError(f"speakers: {len(speakers)} entries for {batch} utterances")
+    if sids is not None and len(sids) != batch:
+        raise ValueError(f"sids: {len(sids)} entries for {batch} utterances")
+    plain = [0] * batch
+    count = np.zeros(batch, np.int32)
+    comp_s, comp_w = [], []
+    vec = None
+    for b, sp in enumerate(speakers):
+        given = sids is not None and sids[b] is not None
+        if sp is None:
+            plain[b] = int(sids[b]) if given else 0
+            continue
+        if given:
+            raise ValueError(f"utterance {b}: both sids and speakers are given")
+        if isinstance(sp, (int, np.integer)):
+            plain[b] = int(sp)
+            continue
+        if isinstance(sp, dict):
+            pairs = list(sp.items())
+        elif isinstance(sp, np.ndarray) or (len(sp) > 0 and not isinstance(sp[0], (tuple, list))):
+            v = np.asarray(sp, np.float32)
+            if v.ndim != 1 or v.size != gin:
+                raise ValueError(f"utterance {b}: a speaker vector has {gin} values (1-D), got shape {v.shape}")
+            if vec is None:
+                vec = np.zeros((batch, max(gin, 1)), np.float32)
+            vec[b, :gin] = v
+            count[b] = -1
+            continue
+        else:
+            pairs = [tuple(q) for q in sp]
+        if len(pairs) == 0:
+            raise ValueError(f"utterance {b}: an empty speaker blend")
+        count[b] = len(pairs)
+        comp_s += [int(q[0]) for q in pairs]
+        comp_w += [float(q[1]) for q in pairs]
+    if not count.any():
+        return (None if sids is None and not any(plain) else plain), None
+    bs = np.ascontiguousarray(comp_s, np.int64).reshape(-1)
+    bw = np.ascontiguousarray(comp_w, np.float32).reshape(-1)
+    bl = L.PeBlend()
+    bl.count = count.ctypes.data_as(C.POINTER(C.c_int32))
+    if bs.size:
+        bl.sid = bs.ctypes.data_as(C.POINTER(C.c_int64))
+        bl.weight = bw.ctypes.data_as(C.POINTER(C.c_float))
+    if vec is not None:
+        bl.vector = vec.ctypes.data_as(C.POINTER(C.c_float))
+    keep.extend([count, bs, bw, vec, bl])
+    return plain, C.byref(bl)
+
+
 def _tiled_scales(scales, batch: int):
     per = per_utterance_scales(scales, batch)
     if per is None:
@@ -134,6 +194,37 @@ class Engine:
                                           C.byref(wb)))
         self.sample_rate, self.hop, self.num_speakers, self.num_symbols = sr.value, hop.value, nspk.value, nsym.value
         self.weight_bytes = wb.value
+        self.speaker_dim = self._speaker_dim()
+
+    def _speaker_dim(self) -> int:
+        gin = C.c_int32()
+        self._check(self._lib.pe_get_speaker_dim(self._h, C.byref(gin)))
+        return gin.value
+
+    def speaker_embedding(self, sid: int) -> np.ndarray:
+        """Row ``sid`` of the voice's speaker table, ``speaker_dim`` float32 values (pe_get_speaker_embedding): for callers
+        who do their own arithmetic and come back with a vector (``speakers=[vector]``)."""
+        out = np.zeros(max(self.speaker_dim, 1), np.float32)
+        self._check(self._lib.pe_get_speaker_embedding(self._h, int(sid), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out[:self.speaker_dim]
+
+    def debug_blend(self, speakers, sids=None) -> np.ndarray:
+        """Test hook (pe_debug_blend): the speaker vectors ``[batch][speaker_dim]`` the mixing kernel forms for ``speakers``
+        (as in ``synthesize_batch``), no synthesis."""
+        keep: list = []
+        n = len(speakers)
+        plain, bl = pack_speakers(speakers, sids, n, self.speaker_dim, keep)
+        if bl is None:
+            count = np.zeros(n, np.int32)
+            b = L.PeBlend()
+            b.count = count.ctypes.data_as(C.POINTER(C.c_int32))
+            keep.extend([count, b])
+            bl = C.byref(b)
+        sid_np = None if plain is None else np.ascontiguousarray(plain, np.int64)
+        out = np.zeros((n, self.speaker_dim), np.float32)
+        self._check(self._lib.pe_debug_blend(self._h, bl, n, None if sid_np is None else sid_np.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     @classmethod
     def borrowed(cls, lib: C.CDLL, handle: int) -> "Engine":
@@ -144,6 +235,7 @@ class Engine:
         self._check(lib.pe_get_info(self._h, C.byref(sr), C.byref(hop), C.byref(nspk), C.byref(nsym), C.byref(wb)))
         self.sample_rate, self.hop, self.num_speakers, self.num_symbols = sr.value, hop.value, nspk.value, nsym.value
         self.weight_bytes = wb.value
+        self.speaker_dim = self._speaker_dim()
         return self
 
     def weights_used(self) -> int:
@@ -215,13 +307,17 @@ class Engine:
 
     # ---- API
     def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-                         timing: Optional[Timing] = None, seeds=None) -> Synthesis:
+                         timing: Optional[Timing] = None, seeds=None, speakers=None) -> Synthesis:
         """``scales``: one (noise_scale, length_scale, noise_w) triple for every utterance, or a (B, 3) array with one
         triple per utterance (pe_synthesize_batch_scaled). ``timing``: a ``Timing`` plan (pe_synthesize_batch_timed).
         ``seeds``: one int or None per utterance (pe_synthesize_batch_seeded): a seeded utterance's noise, and with it its
-        audio, depends on its seed alone -- not on the handle, the calls before or the rest of the batch."""
+        audio, depends on its seed alone -- not on the handle, the calls before or the rest of the batch.
+        ``speakers``: one entry per utterance (pe_synthesize_batch_blended) -- None or an int, a plain id; ``{sid: weight}`` or
+        ``(sid, weight)`` pairs, a blend of table rows in that order; a 1-D array of ``speaker_dim`` floats, a vector."""
         ids, offs = self._pack(id_lists)
-        plain = timing is None and seeds is None
+        keep0: list = []
+        sids, blend = pack_speakers(speakers, sids, len(id_lists), self.speaker_dim, keep0)
+        plain = timing is None and seeds is None and blend is None
         per = per_utterance_scales(scales, len(id_lists)) if plain else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_synthesize_batch if per is None else self._lib.pe_synthesize_batch_scaled
@@ -231,6 +327,9 @@ class Engine:
             entry, extra = self._lib.pe_synthesize_batch_timed, (timing.pack(id_lists, keep),)
         if seeds is not None:
             entry, extra = self._lib.pe_synthesize_batch_seeded, (extra[0] if extra else None, pack_seeds(seeds, len(id_lists), keep))
+        if blend is not None:
+            keep += keep0
+            entry, extra = self._lib.pe_synthesize_batch_blended, ((extra + (None, None))[0], (extra + (None, None))[1], blend)
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -243,19 +342,24 @@ class Engine:
             len(id_lists), sc, sid_arr, nz, C.byref(res), *extra))
         return self._collect(res)
 
-    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid=None, noise_w=None, noise_z=None, seed=None) -> Synthesis:
+    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid=None, noise_w=None, noise_z=None, seed=None,
+                   speaker=None) -> Synthesis:
         nw = None if noise_w is None else np.asarray(noise_w, np.float32)[None]
         nz = None if noise_z is None else np.asarray(noise_z, np.float32)[None]
         return self.synthesize_batch([ids], scales, None if sid is None else [sid], nw, nz,
-                                     seeds=None if seed is None else [seed])
+                                     seeds=None if seed is None else [seed],
+                                     speakers=None if speaker is None else [speaker])
 
     def upload(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-               timing: Optional[Timing] = None, seeds=None):
+               timing: Optional[Timing] = None, seeds=None, speakers=None):
         """``scales``: one triple, or a (B, 3) array of per-utterance triples (pe_upload_scaled). ``timing``: a ``Timing``
         plan (pe_upload_timed); every ``run()`` on the upload follows it. ``seeds``: one int or None per utterance
-        (pe_upload_seeded); every ``run()`` on the upload draws the same noise again."""
+        (pe_upload_seeded); every ``run()`` on the upload draws the same noise again. ``speakers`` as in
+        ``synthesize_batch`` (pe_upload_blended); every ``run()`` on the upload keeps the blend."""
         ids, offs = self._pack(id_lists)
-        plain = timing is None and seeds is None
+        keep0: list = []
+        sids, blend = pack_speakers(speakers, sids, len(id_lists), self.speaker_dim, keep0)
+        plain = timing is None and seeds is None and blend is None
         per = per_utterance_scales(scales, len(id_lists)) if plain else _tiled_scales(scales, len(id_lists))
         sc = (C.c_float * 3)(*[float(s) for s in scales]) if per is None else per.ctypes.data_as(C.POINTER(C.c_float))
         entry = self._lib.pe_upload if per is None else self._lib.pe_upload_scaled
@@ -265,6 +369,9 @@ class Engine:
             entry, extra = self._lib.pe_upload_timed, (timing.pack(id_lists, keep),)
         if seeds is not None:
             entry, extra = self._lib.pe_upload_seeded, (extra[0] if extra else None, pack_seeds(seeds, len(id_lists), keep))
+        if blend is not None:
+            keep += keep0
+            entry, extra = self._lib.pe_upload_blended, ((extra + (None, None))[0], (extra + (None, None))[1], blend)
         nz = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -314,11 +421,13 @@ class Engine:
         self._check(self._lib.pe_fetch(self._h, int(want_audio), int(want_pcm), C.byref(res)))
         return res
 
-    def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None, seed=None):
+    def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None, seed=None,
+               speaker=None):
         """Generator over (float_audio, int16_pcm) chunks of one utterance: encoder/flow once, then the
         vocoder on exact-halo windows of `chunk_frames` frames (reference default 45). Concatenating
         the float chunks gives exactly the unchunked waveform; pcm is peak-normalised per chunk, or follows
-        the level set by ``set_stream_gain``. ``seed``: the utterance's noise seed (pe_stream_begin_seeded)."""
+        the level set by ``set_stream_gain``. ``seed``: the utterance's noise seed (pe_stream_begin_seeded). ``speaker``: the utterance's
+        entry of ``speakers`` as in ``synthesize_batch`` (pe_stream_begin_blended)."""
         ids_np = np.ascontiguousarray(ids, np.int64)
         sc = (C.c_float * 3)(*[float(s) for s in scales])
         keep: list = []
@@ -329,6 +438,11 @@ class Engine:
         entry, extra = self._lib.pe_stream_begin, ()
         if seed is not None:
             entry, extra = self._lib.pe_stream_begin_seeded, (None, pack_seeds([seed], 1, keep))
+        if speaker is not None:
+            one, blend = pack_speakers([speaker], None if sid is None else [sid], 1, self.speaker_dim, keep)
+            sid = None if one is None else one[0]
+            if blend is not None:
+                entry, extra = self._lib.pe_stream_begin_blended, (None, extra[1] if extra else None, blend)
         self._check(entry(self._h, ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, sc,
                           -1 if sid is None else int(sid), nref, C.byref(frames), C.byref(halo), *extra))
         self.stream_frames, self.stream_halo = frames.value, halo.value
@@ -340,20 +454,21 @@ class Engine:
             yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
 
     def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
-                     want_audio: bool = True, timing: Optional[Timing] = None, seeds=None):
+                     want_audio: bool = True, timing: Optional[Timing] = None, seeds=None, speakers=None):
         """Generator over the chunks of B utterances streamed in lock step (pe_stream_begin_batch / pe_stream_next_batch):
         text encoder, durations and flow for the whole batch once, then one batched vocoder pass per chunk. Every item
         is a list of B ``(float chunk or None, int16 chunk)`` pairs -- empty arrays for utterances that are finished;
         chunk k of utterance b is what ``stream`` yields for that utterance alone, in every ``set_stream_gain`` mode (each
         utterance carries its own level). ``chunk_frames``: an int, or a
         callable ``k -> frames`` of the chunk index (a short first chunk, longer ones after). ``scales``, ``timing`` and
-        ``seeds`` as in ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
+        ``seeds`` and ``speakers`` as in ``synthesize_batch``. Sets ``stream_frames`` (array of B) and ``stream_halo``."""
         B = len(id_lists)
         ids, offs = self._pack(id_lists)
         per = per_utterance_scales(scales, B)
         if per is None:
             per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (B, 1)))
         keep: list = [per]
+        sids, blend = pack_speakers(speakers, sids, B, self.speaker_dim, keep)
         nref = self._noise(noise_w, noise_z, keep)
         sid_arr = None
         if sids is not None:
@@ -366,6 +481,8 @@ class Engine:
             entry, extra = self._lib.pe_stream_begin_batch_timed, (timing.pack(id_lists, keep),)
         if seeds is not None:
             entry, extra = self._lib.pe_stream_begin_batch_seeded, (extra[0] if extra else None, pack_seeds(seeds, B, keep))
+        if blend is not None:
+            entry, extra = self._lib.pe_stream_begin_batch_blended, ((extra + (None, None))[0], (extra + (None, None))[1], blend)
         self._check(entry(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), B,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, frames.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -787,12 +904,15 @@ class StreamPool:
         return [int(s) for s in np.flatnonzero(self._state()[2] == 0)]
 
     def join(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
-             timing: Optional[Timing] = None, seeds=None) -> list:
+             timing: Optional[Timing] = None, seeds=None, speakers=None) -> list:
         """Begin the utterances of ``id_lists`` and give each a free slot, lowest first, in input order; returns the slots.
         ``scales``: one triple, or a (B, 3) array of per-utterance triples. Fails as a whole, the pool unchanged, when
         there are too few free slots or an utterance has more than ``max_frames`` frames. ``timing``: a ``Timing`` plan
-        (pe_stream_pool_join_timed). ``seeds``: one int or None per newcomer (pe_stream_pool_join_seeded)."""
+        (pe_stream_pool_join_timed). ``seeds``: one int or None per newcomer (pe_stream_pool_join_seeded). ``speakers``:
+        one entry per newcomer as in ``Engine.synthesize_batch`` (pe_stream_pool_join_blended)."""
         eng, n = self._eng, len(id_lists)
+        keep0: list = []
+        sids, blend = pack_speakers(speakers, sids, n, eng.speaker_dim, keep0)
         ids, offs = eng._pack(id_lists)
         per = per_utterance_scales(scales, n)
         if per is None:
@@ -810,6 +930,9 @@ class StreamPool:
             entry, extra = eng._lib.pe_stream_pool_join_timed, (timing.pack(id_lists, keep),)
         if seeds is not None:
             entry, extra = eng._lib.pe_stream_pool_join_seeded, (extra[0] if extra else None, pack_seeds(seeds, n, keep))
+        if blend is not None:
+            keep += keep0
+            entry, extra = eng._lib.pe_stream_pool_join_blended, ((extra + (None, None))[0], (extra + (None, None))[1], blend)
         eng._check(entry(
             eng._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), offs.ctypes.data_as(C.POINTER(C.c_int64)), n,
             per.ctypes.data_as(C.POINTER(C.c_float)), sid_arr, nref, slot_of.ctypes.data_as(C.POINTER(C.c_int32)),

@@ -55,15 +55,22 @@ class EngineGroup:
             self.engine(i).set_loudness(target_lufs, ceiling_db, true_peak=true_peak, limiter=limiter, limiter_ms=limiter_ms)
 
     def synthesize_batch(self, id_lists: Sequence[Sequence[int]], scales=(0.667, 1.0, 0.8),
-                         sids: Optional[Sequence[int]] = None, seeds=None) -> Synthesis:
+                         sids: Optional[Sequence[int]] = None, seeds=None, speakers=None) -> Synthesis:
         """``scales``: one triple for every utterance, or a (B, 3) array with one triple per utterance. ``seeds``: one int
         or None per utterance (pe_group_synthesize_batch_seeded): each member takes its utterances' seeds along with
-        their ids, so a seeded utterance's audio does not depend on the member that ran it."""
+        their ids, so a seeded utterance's audio does not depend on the member that ran it. ``speakers``: one entry per
+        utterance as in ``Engine.synthesize_batch`` (pe_group_synthesize_batch_blended): the blends go with the ids too."""
         if len(id_lists) == 0:
             raise EngineError("empty batch")
         per = per_utterance_scales(scales, len(id_lists))
         keep: list = []
         extra = ()
+        blend = None
+        if speakers is not None:
+            from .engine import pack_speakers
+            sids, blend = pack_speakers(speakers, sids, len(id_lists), self.engine(0).speaker_dim, keep)
+            if blend is not None and per is None:
+                per = np.ascontiguousarray(np.tile(np.asarray(scales, np.float32), (len(id_lists), 1)))
         if seeds is not None:
             from .engine import pack_seeds
             if per is None:
@@ -76,6 +83,8 @@ class EngineGroup:
         entry = self._lib.pe_group_synthesize_batch if per is None else self._lib.pe_group_synthesize_batch_scaled
         if seeds is not None:
             entry = self._lib.pe_group_synthesize_batch_seeded
+        if blend is not None:
+            entry, extra = self._lib.pe_group_synthesize_batch_blended, (extra[0] if extra else None, blend)
         sid = None if sids is None else np.ascontiguousarray(sids, dtype=np.int64)
         i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
         res = L.PeResult()
@@ -123,17 +132,24 @@ class Coalescer:
         if create(engine._h, int(max_batch), int(max_wait_us), C.byref(self._h)):
             raise EngineError(self._lib.pe_last_error().decode(errors="replace"))
 
-    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid: Optional[int] = None, seed: Optional[int] = None):
+    def synthesize(self, ids, scales=(0.667, 1.0, 0.8), sid: Optional[int] = None, seed: Optional[int] = None, speaker=None):
         """-> (int16 PCM, frames, seconds of the engine call that served the request, utterances in that call).
         ``seed``: the request's noise seed (pe_coalescer_synthesize_seeded): it gets the noise of its own seeded B=1 call
-        whatever it is merged with; None: the engine's own stream."""
+        whatever it is merged with; None: the engine's own stream. ``speaker``: the request's entry of ``speakers`` as in
+        ``Engine.synthesize_batch`` (pe_coalescer_synthesize_blended): a blended request gets what its own B=1 call computes."""
         a = np.ascontiguousarray(ids, dtype=np.int64)
         sc = (C.c_float * 3)(*[float(v) for v in scales])
         pcm, n, fr, secs, bs = C.POINTER(C.c_int16)(), C.c_int64(), C.c_int32(), C.c_double(), C.c_int32()
         sd = None if seed is None else C.byref(C.c_uint64(int(seed) % (1 << 64)))
-        rc = self._lib.pe_coalescer_synthesize_seeded(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, sc,
-                                                      -1 if sid is None else int(sid), sd, C.byref(pcm), C.byref(n),
-                                                      C.byref(fr), C.byref(secs), C.byref(bs))
+        keep: list = []
+        blend = None
+        if speaker is not None:
+            from .engine import pack_speakers
+            one, blend = pack_speakers([speaker], None if sid is None else [sid], 1, self._engine.speaker_dim, keep)
+            sid = None if one is None else one[0]
+        rc = self._lib.pe_coalescer_synthesize_blended(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, sc,
+                                                       -1 if sid is None else int(sid), sd, blend, C.byref(pcm), C.byref(n),
+                                                       C.byref(fr), C.byref(secs), C.byref(bs))
         if rc:
             raise EngineError(self._lib.pe_last_error().decode(errors="replace"))
         try:

@@ -11,7 +11,11 @@ resampled on the GPU from ``--sample-rate`` (the voice's own rate); the WAV head
 group with such a line runs as one timed call; a group without is the call it always was. ``--seed N`` gives the utterance
 of line k (the index that names its WAV) the noise seed ``N + k``, and a line's own ``seed`` overrides it (new): a seeded
 line's audio depends on the voice, the line and its seed alone -- not on ``--batch``, the lines around it or the run -- and
-lines without a seed draw from the engine's own stream in the same call.
+lines without a seed draw from the engine's own stream in the same call. ``--speaker-blend 1:0.7,3:0.3`` (ids, or names from
+the ``speaker_id_map`` of the ``.json`` beside the model) speaks every line with that weighted mix of speaker embeddings, the
+weights used as given; a line's ``"speaker_blend": {"1": 0.7, "3": 0.3}`` or ``"speaker_vector": [...]`` (the embedding
+itself) or its ``speaker_id`` wins over the option, and ``speaker_id`` beside either key on one line is an error that names
+the line (new).
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -94,6 +98,54 @@ def read_seeds(lines: Iterable[str], base: Optional[int]) -> List[Optional[int]]
     return out
 
 
+def parse_blend(text: str, names: Optional[dict] = None) -> List[Tuple[int, float]]:
+    """``1:0.7,3:0.3`` -> [(1, 0.7), (3, 0.3)], the order kept; a speaker is an id or a name from ``names``."""
+    return blend_pairs([tuple(part.rsplit(":", 1)) for part in text.split(",") if part.strip()], names, "--speaker-blend")
+
+
+def blend_pairs(items, names: Optional[dict], where: str) -> List[Tuple[int, float]]:
+    out = []
+    for item in items:
+        if len(item) != 2:
+            raise ValueError(f"{where}: a blend component is speaker:weight, got {item!r}")
+        who, weight = item
+        who = who.strip() if isinstance(who, str) else who
+        if isinstance(who, str) and names and who in names:
+            who = names[who]
+        try:
+            out.append((int(who), float(weight)))
+        except ValueError:
+            raise ValueError(f"{where}: no speaker {who!r}") from None
+    if not out:
+        raise ValueError(f"{where}: an empty blend")
+    return out
+
+
+def read_speakers(lines: Iterable[str], default: Optional[List[Tuple[int, float]]], names: Optional[dict] = None) -> list:
+    """Per non-empty line (the order of read_utterances): its entry of Engine's ``speakers`` -- the line's own
+    ``speaker_blend`` ({speaker: weight}, the order kept) or ``speaker_vector`` (a list of floats), else its ``speaker_id``,
+    else ``default`` (the --speaker-blend option), else None. ``speaker_id`` beside either key on one line, or both keys, is an
+    error that names the line (counted from 1)."""
+    out = []
+    for i, line in enumerate(lines):
+        line = line.strip()
+        if not line:
+            continue
+        obj = json.loads(line)
+        blend, vector, sid = obj.get("speaker_blend"), obj.get("speaker_vector"), obj.get("speaker_id")
+        if (blend is not None) + (vector is not None) + (sid is not None) > 1:
+            raise ValueError(f"line {i + 1}: give one of speaker_id, speaker_blend and speaker_vector, not several")
+        if blend is not None:
+            out.append(blend_pairs(list(blend.items()), names, f"line {i + 1}"))
+        elif vector is not None:
+            out.append([float(x) for x in vector])
+        elif sid is not None:
+            out.append(int(sid))
+        else:
+            out.append(default)
+    return out
+
+
 def group_timing(own: List[Optional[dict]], native_rate: int, hop: int) -> Optional[Timing]:
     """The plan of a group of lines, or None when no line of it carries a timing key."""
     if all(t is None for t in own):
@@ -134,6 +186,9 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--seed", type=int, default=None,
                         help="noise seed: line k gets seed + k, whatever --batch; a line's own \"seed\" overrides it")
+    parser.add_argument("--speaker-blend", default=None,
+                        help="blend of speakers for every line, e.g. 1:0.7,3:0.3 (ids, or names from the model's .json); "
+                             "a line's own speaker_id, \"speaker_blend\" or \"speaker_vector\" overrides it")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG)
 
@@ -156,6 +211,11 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     line_scales = read_scales(lines, scales)
     line_timing = read_timing(lines)
     line_seeds = read_seeds(lines, args.seed)
+    names = None
+    conf = Path(str(args.model) + ".json")
+    if conf.is_file():
+        names = json.loads(conf.read_text(encoding="utf-8")).get("speaker_id_map") or None
+    line_speakers = read_speakers(lines, None if args.speaker_blend is None else parse_blend(args.speaker_blend, names), names)
     step = max(1, args.batch)
     for k in range(0, len(utts), step):
         group = utts[k:k + step]
@@ -169,6 +229,10 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
         seeds = line_seeds[k:k + step]
         if any(s is not None for s in seeds):
             extra["seeds"] = seeds
+        speakers = line_speakers[k:k + step]
+        if any(isinstance(s, list) for s in speakers):        # a blend or a vector in the group: every speaker goes this way
+            extra["speakers"] = speakers
+            sids = [None] * len(group)
         res = engine.synthesize_batch([u[1] for u in group], call_scales,
                                       sids=None if all(s is None for s in sids) else [s or 0 for s in sids], **extra)
         infer_sec = time.perf_counter() - t0

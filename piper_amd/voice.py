@@ -19,6 +19,8 @@ from dataclasses import dataclass
 from pathlib import Path
 from typing import Iterable, List, Optional, Union
 
+import numpy as np
+
 from .config import PhonemeType, PiperConfig
 from .engine import Engine, Timing
 
@@ -120,22 +122,25 @@ class PiperVoice:
 
     def synthesize(self, text: str, wav_file: wave.Wave_write, speaker_id: Optional[int] = None,
                    length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
-                   noise_w: Optional[float] = None, sentence_silence: float = 0.0, seed: Optional[int] = None):
-        """Synthesize WAV audio from text. ``seed``: as in synthesize_stream_raw."""
+                   noise_w: Optional[float] = None, sentence_silence: float = 0.0, seed: Optional[int] = None,
+                   speaker_blend=None, speaker_vector=None):
+        """Synthesize WAV audio from text. ``seed``, ``speaker_blend`` and ``speaker_vector``: as in synthesize_stream_raw."""
         wav_file.setframerate(self.sample_rate)
         wav_file.setsampwidth(2)
         wav_file.setnchannels(1)
         for audio_bytes in self.synthesize_stream_raw(text, speaker_id=speaker_id, length_scale=length_scale,
                                                       noise_scale=noise_scale, noise_w=noise_w,
-                                                      sentence_silence=sentence_silence, seed=seed):
+                                                      sentence_silence=sentence_silence, seed=seed,
+                                                      speaker_blend=speaker_blend, speaker_vector=speaker_vector):
             wav_file.writeframes(audio_bytes)
 
     def synthesize_stream_raw(self, text: str, speaker_id: Optional[int] = None,
                               length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                               noise_w: Optional[float] = None, sentence_silence: float = 0.0,
-                              seed: Optional[int] = None) -> Iterable[bytes]:
+                              seed: Optional[int] = None, speaker_blend=None, speaker_vector=None) -> Iterable[bytes]:
         """Synthesize raw audio per sentence from text. ``seed``: sentence k of the text gets the noise seed ``seed + k``
-        (wrapping at 2^64), so that the same text with the same settings gives the same audio on any handle."""
+        (wrapping at 2^64), so that the same text with the same settings gives the same audio on any handle.
+        ``speaker_blend`` / ``speaker_vector``: every sentence's speaker, as in synthesize_ids_to_raw."""
         sentence_phonemes = self.phonemize(text)
         num_silence_samples = int(sentence_silence * self.sample_rate)
         silence_bytes = bytes(num_silence_samples * 2)
@@ -143,7 +148,8 @@ class PiperVoice:
             phoneme_ids = self.phonemes_to_ids(phonemes)
             yield self.synthesize_ids_to_raw(phoneme_ids, speaker_id=speaker_id, length_scale=length_scale,
                                              noise_scale=noise_scale, noise_w=noise_w,
-                                             seed=None if seed is None else (int(seed) + k) % (1 << 64)) + silence_bytes
+                                             seed=None if seed is None else (int(seed) + k) % (1 << 64),
+                                             speaker_blend=speaker_blend, speaker_vector=speaker_vector) + silence_bytes
 
     def _scales(self, length_scale, noise_scale, noise_w):
         if length_scale is None:
@@ -158,6 +164,28 @@ class PiperVoice:
         if self.config.num_speakers <= 1:
             return None
         return 0 if speaker_id is None else speaker_id
+
+    def _speaker_entry(self, speaker_id, speaker_blend, speaker_vector):
+        """One utterance's entry of Engine's ``speakers`` from at most one of an id, a blend and a vector, or None when the
+        utterance has a plain id. A blend is a mapping ``{speaker: weight}`` or a sequence of ``(speaker, weight)`` pairs,
+        its order kept; a speaker is an id or a name from the config's ``speaker_id_map``."""
+        if (speaker_id is not None) + (speaker_blend is not None) + (speaker_vector is not None) > 1:
+            raise ValueError("give at most one of speaker_id, speaker_blend and speaker_vector")
+        if speaker_vector is not None:
+            return np.asarray(speaker_vector, np.float32).reshape(-1)
+        if speaker_blend is None:
+            return None
+        names = getattr(self.config, "speaker_id_map", None) or {}
+        out = []
+        for who, weight in (speaker_blend.items() if isinstance(speaker_blend, dict) else speaker_blend):
+            if isinstance(who, str) and who in names:
+                who = names[who]
+            elif isinstance(who, str) and who.lstrip("-").isdigit():
+                who = int(who)
+            elif isinstance(who, str):
+                raise ValueError(f"speaker_blend: no speaker named {who!r} in speaker_id_map")
+            out.append((int(who), float(weight)))
+        return out
 
     def target_frames(self, seconds: Optional[float]) -> int:
         """A length in seconds as spectrogram frames of this voice: round(seconds * native rate / hop) with the
@@ -176,16 +204,24 @@ class PiperVoice:
     def synthesize_ids_to_raw(self, phoneme_ids: List[int], speaker_id: Optional[int] = None,
                               length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                               noise_w: Optional[float] = None, durations=None, rate=None,
-                              target_seconds: Optional[float] = None, seed: Optional[int] = None) -> bytes:
+                              target_seconds: Optional[float] = None, seed: Optional[int] = None,
+                              speaker_blend=None, speaker_vector=None) -> bytes:
         """Synthesize raw 16-bit mono audio from phoneme ids (voice.py:140-185). New, all optional (Engine's ``Timing``):
         ``durations`` -- one int per id, >= 0 = that id lasts exactly so many frames, -1 = predicted; ``rate`` -- one
         multiplier of the predicted duration per id; ``target_seconds`` -- the utterance lasts
         round(seconds * native rate / hop) frames exactly (the byte count follows from the output rate); ``seed`` -- the
         utterance's noise seed (Engine's ``seeds``): its audio then depends on the voice, the ids, the settings and the seed
-        alone, not on what the handle served before."""
+        alone, not on what the handle served before; ``speaker_blend`` -- ``{speaker: weight}`` or ``(speaker, weight)``
+        pairs, ids or names from ``speaker_id_map``: a weighted mix of speaker embeddings, weights used as given;
+        ``speaker_vector`` -- ``Engine.speaker_dim`` floats used as the speaker embedding itself (Engine's ``speakers``).
+        At most one of ``speaker_id``, ``speaker_blend`` and ``speaker_vector``."""
         timing = self._timing(None if durations is None else [durations], None if rate is None else [rate],
                               None if target_seconds is None else [target_seconds])
-        if timing is None and seed is None:
+        entry = self._speaker_entry(speaker_id, speaker_blend, speaker_vector)
+        if entry is not None:
+            r = self.session.synthesize_batch([phoneme_ids], self._scales(length_scale, noise_scale, noise_w), timing=timing,
+                                              seeds=None if seed is None else [seed], speakers=[entry])
+        elif timing is None and seed is None:
             r = self.session.synthesize(phoneme_ids, self._scales(length_scale, noise_scale, noise_w),
                                         sid=self._speaker(speaker_id))
         else:
@@ -198,17 +234,28 @@ class PiperVoice:
     def synthesize_ids_batch_to_raw(self, phoneme_id_lists: List[List[int]], speaker_ids=None,
                                     length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                                     noise_w: Optional[float] = None, durations=None, rate=None,
-                                    target_seconds=None, seeds=None) -> List[bytes]:
+                                    target_seconds=None, seeds=None, speaker_blend=None, speaker_vector=None) -> List[bytes]:
         """Batched extension: several utterances in one GPU call, each identical to its own
         synthesize_ids_to_raw() (same noise stream aside). ``length_scale`` / ``noise_scale`` / ``noise_w`` may each be
         one value for every utterance or a list with one value per utterance (None entries: the voice's default).
         ``durations`` / ``rate`` / ``target_seconds``: lists with one entry per utterance as in synthesize_ids_to_raw
         (None entries: nothing of that kind for that utterance). ``seeds``: one noise seed or None per utterance; a seeded
-        utterance is then identical to its own seeded synthesize_ids_to_raw(), noise included."""
+        utterance is then identical to its own seeded synthesize_ids_to_raw(), noise included. ``speaker_blend`` /
+        ``speaker_vector``: lists with one entry per utterance as in synthesize_ids_to_raw (None entries: a plain id)."""
         sids = None
         n = len(phoneme_id_lists)
         if self.config.num_speakers > 1:
             sids = [0 if s is None else s for s in (speaker_ids or [None] * n)]
+        speakers = None
+        if speaker_blend is not None or speaker_vector is not None:
+            for what, v in (("speaker_blend", speaker_blend), ("speaker_vector", speaker_vector), ("speaker_ids", speaker_ids)):
+                if v is not None and len(v) != n:
+                    raise ValueError(f"{what}: {len(v)} entries for {n} utterances")
+            speakers = [self._speaker_entry(None if speaker_ids is None else speaker_ids[i],
+                                            None if speaker_blend is None else speaker_blend[i],
+                                            None if speaker_vector is None else speaker_vector[i]) for i in range(n)]
+            speakers = [(sids[i] if sids is not None else None) if e is None else e for i, e in enumerate(speakers)]
+            sids = None
         knobs = (length_scale, noise_scale, noise_w)
         if any(isinstance(v, (list, tuple)) for v in knobs):
             def at(v, i):
@@ -221,7 +268,9 @@ class PiperVoice:
         else:
             scales = self._scales(length_scale, noise_scale, noise_w)
         timing = self._timing(durations, rate, target_seconds)
-        if timing is None and seeds is None:
+        if speakers is not None:
+            r = self.session.synthesize_batch(phoneme_id_lists, scales, timing=timing, seeds=seeds, speakers=speakers)
+        elif timing is None and seeds is None:
             r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
         else:
             r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids, timing=timing, seeds=seeds)
