@@ -405,6 +405,10 @@ class Engine {
                     double flops, const float* bias2 = nullptr, long bias2_bs = 0, const float* w4direct = nullptr, int kin = 192,
                     long max_cols = 0);
   const float* pack4_conv_pad192(const WeightSet& ws, const std::string& wname, int in_rev, int out_rev);
+  struct Rcl;
+  void pack_gate4pre(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r);
+  // the first gate conv of coupling layer `r` with its pre composed in, over x0 (gate4pre_kernel); b2 = the speaker bias or null
+  void gate_pre(const Rcl& r, View x0, View out, const int* lens, int Lmax, double cols, const float* b2);
   // second: rows >= split of a STACKED pack4 matrix (w4) are another conv over the same LN(y), written to out2 with the
   // per-utterance bias vector bias2 on top (enc_p.proj + dp.pre of a small call in one launch)
   struct LnSecond { const float* w4 = nullptr; int split = 0; View out2{nullptr, 0, 0}; const float* bias2 = nullptr; long bias2_bs = 0; };
@@ -493,6 +497,9 @@ class Engine {
     const float* pre4pad = nullptr;               // the first layer's pre in pack4 order, K padded to 192 (colchain4_kernel mode 3)
     std::vector<PackedConv> in, rs;
     std::vector<const float*> rs4;   // the res/skip 1x1 convs in pack4 order (colchain4_kernel mode 2; null: not packed)
+    // pre composed into the first gate conv (gate4pre_kernel, kernels/gate4.h; null: shapes it is not built for): the
+    // matrix Wg_k . Wp in gate4 order over 96 channels, b_gate + sum_k Wg_k . b_pre, and the per-tap table behind it
+    const float* gpre4 = nullptr; const float* gpre_bias = nullptr; const float* gpre_tapb = nullptr;
     int in_off, out_off;             // channel offsets of x0 / x1 in the physical (unflipped) layout
   };
   std::vector<Rcl> rcls_;            // in execution order

@@ -365,23 +365,40 @@ void Engine::issue_flow() {
   const View fh = VF(fh_, H_), facts = VF(facts_, H_), fskip = VF(fskip_, H_);
   const int half = C_ / 2;
   const bool chain = pol_.chain16(fsum, true, H_, half);
+  // small calls: the LAST WN layer's res/skip conv (skip rows only) rides in front of the post + pre chain launch
+  // (`front` false: the same shapes whatever PIPER_HIP_CHAIN_RS says -- the chain launch takes its 4-column form)
+  auto rs_front_of = [&](size_t ri, bool front = true) {
+    const Rcl& r = rcls_[ri];
+    const int nl = (int)r.in.size();
+    return chain && nl >= 1 && r.rs4[nl - 1] && r.rs[nl - 1].rows == H_ && H_ == 192 && half == 96 &&
+           (front ? pol_.chain_rs_front((long)B * Fmax) : pol_.chain4_frames((long)B * Fmax)) && w4_of(r.post16) &&
+           (ri + 1 >= rcls_.size() || (rcls_[ri + 1].pre.rows <= 192 && w4_of(rcls_[ri + 1].pre16)));
+  };
+  // ... and where the chain is 4 columns wide and the gate conv runs on gate4_kernel: pre composed into the first gate conv
+  // (gate4pre_kernel reads x0; nobody computes h = pre(x0) in front of the WN -- the first res/skip launch writes h + res_0 in
+  // one piece). With PIPER_HIP_CHAIN_RS=0 too: that knob only moves the last res/skip conv, one launch per coupling layer.
+  auto compose_pre_of = [&](size_t ri) {
+    if (ri >= rcls_.size() || !pol_.compose_pre() || !rs_front_of(ri, false)) return false;
+    const Rcl& r = rcls_[ri];
+    return r.in.size() >= 2 && r.gpre4 && r.rs4[0] && r.rs[0].rows == 2 * H_ && w4_of(r.pre16) && r.pre.rows == H_ &&
+           plan_conv(r.in[0], Fmax, EPI_GATE, stage_tiled_).form == CONV_GATE12;
+  };
   for (size_t ri = 0; ri < rcls_.size(); ++ri) {
     Rcl& r = rcls_[ri];
     const View x0{zp_ + (long)r.in_off * Fs, (long)C_ * Fs, Fs};
     const View x1{zp_ + (long)r.out_off * Fs, (long)C_ * Fs, Fs};
-    if (!(chain && ri > 0)) {                                                     // else: written by the previous layer's chain
+    const bool compose_pre = compose_pre_of(ri);
+    if (!(chain && ri > 0) && !compose_pre) {                                     // else: written by the previous layer's chain, or not at all
       if (!(chain && r.pre4pad && conv1x1_col4(nullptr, r.pre.bias, r.pre.rows, x0, fh, lens_b_, B, Fmax, 2.0 * fsum * r.pre.macs_per_col,
                                                nullptr, 0, r.pre4pad, half, LaunchPolicy::col4_max_frames)))
         conv(r.pre, x0, fh, lens_b_, 1, Fmax, EPI_STORE);
     }
     const int nl = (int)r.in.size();
-    // small calls: the LAST layer's res/skip conv (skip rows only) rides in front of the post + pre chain launch
-    const bool rs_front = chain && nl >= 1 && r.rs4[nl - 1] && r.rs[nl - 1].rows == H_ && H_ == 192 && half == 96 &&
-                          pol_.chain_rs_front((long)B * Fmax) && w4_of(r.post16) &&
-                          (ri + 1 >= rcls_.size() || (rcls_[ri + 1].pre.rows <= 192 && w4_of(rcls_[ri + 1].pre16)));
+    const bool rs_front = rs_front_of(ri);
     for (int i = 0; i < nl; ++i) {
       const float* b2 = nspk_ > 1 ? cond_ + cond_off_wn_[ri] + (long)i * 2 * H_ : nullptr;
-      conv(r.in[i], fh, facts, lens_b_, 1, Fmax, EPI_GATE, {.bias2 = b2, .bias2_bs = cond_bs_});
+      if (compose_pre && i == 0) gate_pre(r, x0, facts, lens_b_, Fmax, fsum, b2);
+      else conv(r.in[i], fh, facts, lens_b_, 1, Fmax, EPI_GATE, {.bias2 = b2, .bias2_bs = cond_bs_});
       if (rs_front && i == nl - 1) {
         fl += 2.0 * fsum * (r.in[i].macs_per_col + r.rs[i].macs_per_col);
         continue;
@@ -396,9 +413,15 @@ void Engine::issue_flow() {
         cp.x1 = fh.p; cp.x1_bs = fh.bs; cp.x1_cs = fh.cs;
         cp.out = fskip.p; cp.out_bs = fskip.bs; cp.out_cs = fskip.cs;
         cp.lens = lens_b_;
-        const int kh4 = kbegin(prof_level_ >= 2 ? krow("colchain4_kernel<false>") : 0, 2.0 * fsum * r.rs[i].macs_per_col,
-                               4.0 * (fsum * (H_ + 2.0 * cp.rows1) + (double)cp.rows1 * H_));
-        launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem(), stream_, cp);
+        const bool hpre = compose_pre && i == 0;      // the res part also adds pre(x0): x1 = the whole hidden state, not read
+        if (hpre) {
+          cp.in0 = x0.p; cp.in0_bs = x0.bs; cp.in0_cs = x0.cs;
+          cp.w2 = w4_of(r.pre16); cp.b2 = r.pre.bias; cp.rows2 = H_;
+        }
+        const int kh4 = kbegin(prof_level_ >= 2 ? krow("colchain4_kernel<false>") : 0,
+                               2.0 * fsum * (r.rs[i].macs_per_col + (hpre ? r.pre.macs_per_col : 0)),
+                               4.0 * (fsum * (H_ + 2.0 * cp.rows1) + (double)cp.rows1 * H_ + (hpre ? half * (fsum + H_) : 0)));
+        launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem() + (hpre ? 4 * (96 + 4) * sizeof(float) : 0), stream_, cp);
         kend(kh4);
       } else {
         conv(r.rs[i], facts, fh, lens_b_, 1, Fmax, EPI_WNRS, {.out2 = fskip, .mode = i == 0 ? 1 : 0});
@@ -412,7 +435,7 @@ void Engine::issue_flow() {
       cp.w1 = r.post16; cp.b1 = r.post.bias; cp.rows1 = half;
       cp.mode = 1;
       cp.x1 = x1.p; cp.x1_bs = x1.bs; cp.x1_cs = x1.cs;
-      if (ri + 1 < rcls_.size()) {
+      if (ri + 1 < rcls_.size() && !compose_pre_of(ri + 1)) {      // (composed: the next layer's gate conv reads x0 itself)
         const Rcl& nx = rcls_[ri + 1];
         if (nx.in_off != r.out_off) throw std::runtime_error("coupling layers do not alternate halves");
         cp.w2 = nx.pre16; cp.b2 = nx.pre.bias; cp.rows2 = H_;

@@ -332,6 +332,24 @@ void Engine::conv(const PackedConv& pc, View x, View out, const int* lens, int l
   kend(kh);
 }
 
+// The first WN gate conv of a coupling layer whose pre is composed into it (engine_pack.cpp pack_gate4pre): gate4_kernel's
+// grid over the 96 channels of x0. The caller has asked plan_conv that the plain conv would take gate4_kernel here.
+void Engine::gate_pre(const Rcl& r, View x0, View out, const int* lens, int Lmax, double cols, const float* b2) {
+  const PackedConv& pc = r.in[0];
+  ConvP p{};
+  p.x = x0.p; p.x_bs = x0.bs; p.x_cs = x0.cs;
+  p.wpg4 = r.gpre4; p.bias = r.gpre_bias;
+  p.bias2 = b2; p.bias2_bs = cond_bs_;
+  p.out = out.p; p.o_bs = out.bs; p.o_cs = out.cs;
+  p.lens = lens; p.len_mul = 1;
+  p.Cin = 96; p.rows = pc.rows; p.ntaps = pc.ntaps; p.dil = 1; p.padl = pc.padl; p.xhalo = pc.ntaps - 1;
+  p.in_slope = 1.f; p.epi = EPI_GATE; p.split = pc.split;
+  const double macs = (double)pc.rows * 96 * pc.ntaps;
+  const int kh = kbegin(prof_level_ >= 2 ? krow("gate4pre_kernel") : 0, 2.0 * macs * cols, 4.0 * (cols * (96 + pc.split) + macs));
+  launch::gate4pre(dim3((Lmax + 11) / 12, pc.split / 32, B_), ((size_t)16 * (96 + 4) + (size_t)6 * 64 * 12) * sizeof(float), ls_, p, r.gpre_tapb);
+  kend(kh);
+}
+
 // mrf_kernel launch: the window geometry -- output columns per workgroup N = 16 * NCG * OU -- is chosen here. Few
 // utterances: the launch is one or two rounds of workgroups over the 256 CUs, so the workgroup count should sit just under
 // a multiple of 256 and a workgroup should be short; batches: many rounds, so large N (less halo recompute, fewer

@@ -384,6 +384,53 @@ const float* Engine::pack4_conv_pad192(const WeightSet& ws, const std::string& w
   return pack4(W, Co, 192);
 }
 
+// A coupling layer's pre (1x1, half -> 192, x0's Flip folded in as in pack16_conv(.., odd, 0)) composed into its first gate
+// conv for gate4pre_kernel (kernels/gate4.h): per tap k, Wc_k = Wg_k . Wp (2H x 96) and B_k = Wg_k . b_pre, computed in
+// f64 and rounded once. Wc in pack_matrix's gate4 order with 24 k quads per tap; the biases as [b_gate + sum_k B_k][2H] and
+// the table [row k < 5: B_k (missing taps: zeros) | row 5: b_gate][2H]. Only the shapes gate4_kernel itself is packed for.
+void Engine::pack_gate4pre(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r) {
+  const HostTensor& wg = ws.get(prefix + ".enc.in_layers.0.weight");
+  const HostTensor& wp = ws.get(prefix + ".pre.weight");
+  if (wg.dims.size() != 3 || wp.dims.size() != 3 || wp.dims[2] != 1) return;
+  const int R = (int)wg.dims[0], H = (int)wg.dims[1], nt = (int)wg.dims[2], Ci = (int)wp.dims[1], split = R / 2;
+  if (H != 192 || (int)wp.dims[0] != H || Ci != 96 || nt > 5 || R != 2 * H || !r.in[0].wpg4) return;
+  const std::string bgn = prefix + ".enc.in_layers.0.bias", bpn = prefix + ".pre.bias";
+  const size_t n4 = (size_t)(split / 32) * nt * (Ci / 4) * 256;
+  std::vector<float> G(skeleton_ ? 0 : n4, 0.f), bsum(skeleton_ ? 0 : R, 0.f), tapb(skeleton_ ? 0 : (size_t)6 * R, 0.f);
+  if (!skeleton_) {
+    std::vector<double> P((size_t)H * Ci), bp(H, 0.0), acc(Ci);
+    for (int c = 0; c < H; ++c)
+      for (int i = 0; i < Ci; ++i) P[(size_t)c * Ci + i] = wp.data[(size_t)c * Ci + (odd ? Ci - 1 - i : i)];
+    if (ws.has(bpn))
+      for (int c = 0; c < H; ++c) bp[c] = ws.get(bpn).data[c];
+    const bool has_bg = ws.has(bgn);
+    for (int row = 0; row < R; ++row) {
+      // where gate4_kernel's lanes look for this row: lane l < 32 the tanh row of channel 32 g + l, l >= 32 the sigmoid row
+      const int ch = row < split ? row : row - split, g = ch / 32, lane = (ch & 31) + (row < split ? 0 : 32);
+      double bs = has_bg ? (double)ws.get(bgn).data[row] : 0.0;
+      tapb[(size_t)5 * R + row] = (float)bs;
+      for (int k = 0; k < nt; ++k) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        double bk = 0.0;
+        for (int c = 0; c < H; ++c) {
+          const double a = wg.data[((size_t)row * H + c) * nt + k];
+          const double* pr = &P[(size_t)c * Ci];
+          for (int i = 0; i < Ci; ++i) acc[i] += a * pr[i];
+          bk += a * bp[c];
+        }
+        for (int i = 0; i < Ci; ++i)
+          G[((((size_t)g * nt + k) * (Ci / 4) + i / 4) * 64 + lane) * 4 + (i & 3)] = (float)acc[i];
+        tapb[(size_t)k * R + row] = (float)bk;
+        bs += bk;
+      }
+      bsum[row] = (float)bs;
+    }
+  }
+  r.gpre4 = dev_alloc(n4, skeleton_ ? nullptr : G.data());
+  r.gpre_bias = dev_alloc((size_t)R, skeleton_ ? nullptr : bsum.data());
+  r.gpre_tapb = dev_alloc((size_t)6 * R, skeleton_ ? nullptr : tapb.data());
+}
+
 DdsW Engine::load_dds(const WeightSet& ws, const std::string& p) {
   DdsW d;
   for (int i = 0; i < arch_[A_DDSLAYERS]; ++i) {
@@ -544,6 +591,7 @@ void Engine::init(const WeightSet& ws) {
       r.pre16 = pack16_conv(ws, p + ".pre.weight", odd, 0);
       if (H_ == 192 && rcls_.empty()) r.pre4pad = pack4_conv_pad192(ws, p + ".pre.weight", odd, 0);   // first layer's pre: a launch of its own
       r.post16 = pack16_conv(ws, p + ".post.weight", 0, odd);
+      if (wnl >= 2) pack_gate4pre(ws, p, odd, r);
       rcls_.push_back(r);
       if (gin_) {
         const HostTensor& cw = ws.get(p + ".enc.cond_layer.weight");

@@ -45,13 +45,8 @@ __device__ __forceinline__ void col_gemm4_fetch(Col4W<K>& W, const float* wp4, i
 }
 // partial product of this wave's K range: P[wave][row][4 columns] <- W[:, K range] . Y[K range][4]; YT = [4][K + 4]
 template <int K>
-__device__ __forceinline__ void col_gemm4_run(const Col4W<K>& W, const float* YT, float* P, int wv, int lane) {
+__device__ __forceinline__ void col_gemm4_acc(const Col4W<K>& W, const float* YT, f32x4 (&acc)[C4_NT], int wv, int lane) {
   constexpr int NQ = Col4W<K>::NQ, KS = Col4W<K>::KS;
-  f32x4 acc[C4_NT];
-#pragma unroll
-  for (int m = 0; m < C4_NT; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[m][r] = 0.f;
   const float* yp = YT + (lane & 3) * KS + 4 * NQ * wv;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -63,10 +58,36 @@ __device__ __forceinline__ void col_gemm4_run(const Col4W<K>& W, const float* YT
 #pragma unroll
       for (int m = 0; m < C4_NT; ++m) acc[m] = pe_mfma_4x4x1(W.w[m][q][j], yv[j], acc[m]);
   }
+}
+__device__ __forceinline__ void col_gemm4_zero(f32x4 (&acc)[C4_NT]) {
+#pragma unroll
+  for (int m = 0; m < C4_NT; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[m][r] = 0.f;
+}
+__device__ __forceinline__ void col_gemm4_put(const f32x4 (&acc)[C4_NT], float* P, int wv, int lane) {
 #pragma unroll
   for (int m = 0; m < C4_NT; ++m)
 #pragma unroll
     for (int r = 0; r < 4; ++r) P[((wv * C4_NT + m) * 64 + 4 * (lane >> 2) + r) * 4 + (lane & 3)] = acc[m][r];
+}
+template <int K>
+__device__ __forceinline__ void col_gemm4_run(const Col4W<K>& W, const float* YT, float* P, int wv, int lane) {
+  f32x4 acc[C4_NT];
+  col_gemm4_zero(acc);
+  col_gemm4_acc<K>(W, YT, acc, wv, lane);
+  col_gemm4_put(acc, P, wv, lane);
+}
+// the sum of two products over the same 4 columns, W.Y + W2.Y2, as ONE K range per wave: the wave's accumulators run on
+// from its K slice of the first product into its K2 slice of the second (in that order), then one partial tile as above
+template <int K, int K2>
+__device__ __forceinline__ void col_gemm4_run2(const Col4W<K>& W, const float* YT, const Col4W<K2>& W2, const float* YT2, float* P,
+                                               int wv, int lane) {
+  f32x4 acc[C4_NT];
+  col_gemm4_zero(acc);
+  col_gemm4_acc<K>(W, YT, acc, wv, lane);
+  col_gemm4_acc<K2>(W2, YT2, acc, wv, lane);
+  col_gemm4_put(acc, P, wv, lane);
 }
 // row `c` of the product at column `col`: the four waves' partials in wave order
 __device__ __forceinline__ float col_gemm4_get(const float* P, int c, int col) {
@@ -95,6 +116,10 @@ __device__ __forceinline__ float pe_col_sum4(float v, float* red, int& flip, int
 //   mode 2   (4-column form only) WN res/skip conv (modules.py:200-208), grid.z = 192-row parts of W1:
 //            x1 += W1[res rows].in + b  (the WN hidden state, in place) ; out (+)= W1[skip rows].in + b  (the skip sum;
 //            `first`: not read). rows1 = 384: part 0 = res, part 1 = skip; rows1 = 192 (last WN layer): all skip.
+//            With w2 (the FIRST WN layer of a coupling layer whose pre is composed into its gate conv, gate4.h: nobody
+//            has written the hidden state yet): part 0 writes  x1 = ((W1[res rows].in + W2.in0) + b1) + b2  instead, in0 =
+//            the 96 channels of x0, W2 / b2 = the coupling layer's pre (modules.py:455, 196-208 -- h = pre(x0), then
+//            h + res_0); the two products are one K = 192 + 96 range per wave (col_gemm4_run2), x1 is not read.
 //   mode 3   (4-column form only) a plain 1x1 conv, grid.z = 192-row parts: out = W1.in + b1 (+ res[utterance][row], a
 //            per-utterance bias vector: the speaker conditioning of dp.pre) -- the first encoder layer's q/k/v, dp.pre.
 // 192 input channels, rows1 = 192 (mode 0) / 96 (mode 1), second GEMM 192 rows over the 96 updated channels.
@@ -119,7 +144,8 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   int L = PE_UNIFORM(lens[b]);                              // decides whether the workgroup runs: part of the batch, one wait for both
   if constexpr (FRONT) PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1,
                                       p.in0, p.in0_bs, p.in0_cs, p.w0, p.b0);
-  else PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1);
+  else PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1,
+                      p.in0, p.in0_bs, p.in0_cs, p.w2, p.b2, p.kT, p.kt_bs, p.vQ);
   const int t0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
   if (t0 >= L) return;
   if constexpr (!FRONT) PE_STAMP(3, 1);
@@ -138,6 +164,9 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   Col4W<K1> gw;                                  // first GEMM's fragments
   auto fetch_gw = [&]() { col_gemm4_fetch<K1>(gw, p.w1 + (long)part * C4_NT * (K1 / 4) * 256, (rows_here + 63) / 64, wv, lane); };
   const bool skip_part = p.mode == 2 && (p.rows1 <= C4_H || part == 1);
+  const bool pre_part = !FRONT && p.mode == 2 && p.w2 && !skip_part;      // mode 2 with w2: the res part also adds pre(x0)
+  float* YTP = P + 4 * C4_H * NC + 32 + 64 * 4;   // pre_part: x0 as [4][KS2], behind red and dds4.h's ZL (the launcher adds the room)
+  Col4W<K2> gw2;                                 // second GEMM's fragments: the next layer's pre (mode 1), this layer's (pre_part)
   float sk[NVT];                                 // FRONT: the completed skip sum of this thread's (channel, column) slots
   if constexpr (FRONT) {
     const pe_rowsrc a0 = pe_make_row(p.in0 + (long)b * p.in0_bs, K1 * p.in0_cs);
@@ -170,7 +199,10 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
     const float* obp = p.mode == 0 ? p.res + (long)b * p.res_bs : (skip_part ? p.out + (long)b * p.out_bs : p.x1 + (long)b * p.x1_bs);
     const int ocs = p.mode == 0 ? p.res_cs : (skip_part ? p.out_cs : p.x1_cs);
     const pe_rowsrc od = p.mode == 3 ? pe_make_row(p.res ? p.res + (long)b * p.res_bs + row0 : p.w1, p.res ? rows_here : 0)
+                         : pre_part  ? pe_make_row(p.b2 ? p.b2 : p.w1, p.b2 ? rows_here : 0)      // pre's bias in x1's place
                                      : pe_make_row(obp, (skip_part && p.first) ? 0 : rows_here * ocs);
+    const pe_rowsrc x0d = pe_make_row(p.in0 + (long)b * p.in0_bs, pre_part ? K2 * p.in0_cs : 0);
+    float x0v[2];
     const pe_rowsrc gd = pe_make_row(p.mode == 0 ? p.gamma : p.w1, p.mode == 0 ? p.rows1 : 0);
     const pe_rowsrc bd = pe_make_row(p.mode == 0 ? p.beta : p.w1, p.mode == 0 ? p.rows1 : 0);
     const pe_rowsrc b1d = pe_make_row(p.b1 ? p.b1 + row0 : p.w1, p.b1 ? rows_here : 0);
@@ -179,21 +211,28 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
     for (int k = 0; k < NVT; ++k) {
       const int c = rl + 64 * k;
       xin[k] = FRONT ? sk[k] : pe_row_load(ind, ok ? c * p.in1_cs + t : -1);
-      ov[k] = pe_row_load(od, (ok && c < rows_here) ? (p.mode == 3 ? c : c * ocs + t) : -1);
+      ov[k] = pe_row_load(od, (ok && c < rows_here) ? ((p.mode == 3 || pre_part) ? c : c * ocs + t) : -1);
+      if (!FRONT && k < 2) x0v[k] = pe_row_load(x0d, (ok && c < K2) ? c * p.in0_cs + t : -1);
       gg[k] = pe_row_load(gd, c < rows_here ? c : -1);
       bb[k] = pe_row_load(bd, c < rows_here ? c : -1);
       b1v[k] = pe_row_load(b1d, c < rows_here ? c : -1);
     }
     PE_SCHED_FENCE();
     if constexpr (!FRONT) fetch_gw();
+    if (pre_part) col_gemm4_fetch<K2>(gw2, p.w2, C4_NT, wv, lane);
     if constexpr (!FRONT) PE_STAMP(3, 2);
 #pragma unroll
     for (int k = 0; k < NVT; ++k) YT[col * KS1 + rl + 64 * k] = xin[k];
+    if constexpr (!FRONT)
+      if (pre_part) {
+        YTP[col * KS2 + rl] = x0v[0];
+        if (rl < K2 - 64) YTP[col * KS2 + rl + 64] = x0v[1];
+      }
   }
   __syncthreads();
-  col_gemm4_run<K1>(gw, YT, P, wv, lane);
+  if (pre_part) col_gemm4_run2<K1, K2>(gw, YT, gw2, YTP, P, wv, lane);
+  else col_gemm4_run<K1>(gw, YT, P, wv, lane);
   // second GEMM's fragments (the next layer's pre): in flight under the x1 update
-  Col4W<K2> gw2;
   const bool second = p.mode == 1 && p.w2;
   if (second) col_gemm4_fetch<K2>(gw2, p.w2, (p.rows2 + 63) / 64, wv, lane);
   __syncthreads();

@@ -19,16 +19,22 @@ namespace pe {
 //   * the twelve partial tiles meet in LDS in wave order (deterministic), then bias + speaker bias + tanh * sigmoid.
 // Weights: engine_pack.cpp pack_gate4 -- [group][tap][k quad 48][lane][4].
 constexpr int G4_NC = 12, G4_WC = 16, G4_NW = 12, G4_K = 192, G4_XS = G4_K + 4;
-// Kernel entry (pe_rt.h PE_ENTRY_BATCH): everything in front of the loads arrives in SGPRs (13 dwords); the leading
-// parameters repeat p's fields of the same names.
-__global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int len_mul, const float* x, long x_bs, int x_cs,
-                                                           int Cin, int padl, int ntaps_, const float* wpg4, ConvP p) {
-  PE_KTRACE(4);
-  PE_DYN_SMEM(float, sm);                         // XT[16][196] | P[12 waves][64][12]
-  p.lens = lens; p.len_mul = len_mul; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl; p.ntaps = ntaps_;
-  p.wpg4 = wpg4;
+// The same conv with the coupling layer's `pre` (1x1, 96 -> 192; modules.py:433, 455) composed into it when the weights are
+// packed (engine_pack.cpp pack_gate4pre): Wc_k = Wg_k . Wp over the 96 channels of x0 -- K = 96 x ntaps, 6 waves, half the
+// weight stream and half the MFMAs. gate4pre_kernel below; everything else is gate4_kernel's.
+//   * pre's bias reaches the gate conv only through taps whose input column lies inside [0, L): h = pre(x0) . mask is zero
+//     outside. B_k = Wg_k . b_pre per tap; `tapb` = [ntaps rows B_k | row 5: the gate conv's own bias][2 x split]. A
+//     workgroup none of whose columns has a tap outside [0, L) adds p.bias = b_gate + sum_k B_k (rounded once from f64);
+//     the others (wave-uniform branch) add b_gate + B_k over the inside taps, in tap order. Then the speaker bias, as ever.
+constexpr int G4P_K = 96, G4P_NW = G4P_K / 16;
+// Kernel entry (pe_rt.h PE_ENTRY_BATCH): everything in front of the loads arrives in SGPRs (13 dwords; gate4pre_kernel:
+// 14, Cin is the constant 96 there and tapb rides along); the leading parameters repeat p's fields of the same names.
+template <int K>
+__device__ __forceinline__ void gate4_body(ConvP& p, const float* tapb) {
+  constexpr int NW = K / 16, XS = K + 4;
+  PE_DYN_SMEM(float, sm);                         // XT[16][K + 4] | P[K / 16 waves][64][12]
   float* XT = sm;
-  float* P = XT + G4_WC * G4_XS;
+  float* P = XT + G4_WC * XS;
   const int b = blockIdx.z, grp = blockIdx.y;
   PE_STAMP(5, 0);
   const int L = p.lens[b] * p.len_mul;            // first used after every load below is requested
@@ -36,23 +42,23 @@ __global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int 
   const int tid = threadIdx.x, lane = tid & 63, wv = PE_UNIFORM(tid >> 6);
   const int l3 = lane & 3, lb = lane >> 2;
   const int ntaps = p.ntaps;
-  // ---- the x window (192 channels x 16 columns from n0 - padl), then this wave's fragments
+  // ---- the x window (K channels x 16 columns from n0 - padl), then this wave's fragments
   const pe_rowsrc xd = pe_make_row(p.x + (long)b * p.x_bs, p.Cin * p.x_cs);
   float xv[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    const int idx = tid + 64 * G4_NW * u, ch = idx >> 4, c = idx & 15, t = n0 - p.padl + c;
+    const int idx = tid + 64 * NW * u, ch = idx >> 4, c = idx & 15, t = n0 - p.padl + c;
     xv[u] = pe_row_load(xd, (t >= 0 && t < p.x_cs) ? ch * p.x_cs + t : -1);
   }
   PE_SCHED_FENCE();
   f32x4 wf[5][4];
   {
-    const int tap_floats = (G4_K / 4) * 256;       // one tap of one group: 48 quads x 64 lanes x 4
+    const int tap_floats = (K / 4) * 256;       // one tap of one group: 48 quads x 64 lanes x 4
     const pe_rowsrc wd = pe_make_row_u(p.wpg4 + (long)grp * ntaps * tap_floats, ntaps * tap_floats);
 #pragma unroll
     for (int tp = 0; tp < 5; ++tp)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) wf[tp][q] = pe_row_load4(wd, tp < ntaps ? ((tp * (G4_K / 4) + 4 * wv + q) * 64 + lane) * 4 : -4);
+      for (int q = 0; q < 4; ++q) wf[tp][q] = pe_row_load4(wd, tp < ntaps ? ((tp * (K / 4) + 4 * wv + q) * 64 + lane) * 4 : -4);
   }
   PE_SCHED_FENCE();
   if (n0 >= L) return;
@@ -61,10 +67,10 @@ __global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int 
     const float slope = p.in_slope;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int idx = tid + 64 * G4_NW * u, ch = idx >> 4, c = idx & 15, t = n0 - p.padl + c;
+      const int idx = tid + 64 * NW * u, ch = idx >> 4, c = idx & 15, t = n0 - p.padl + c;
       float v = (t < L) ? xv[u] : 0.f;               // (t < 0: the load was poisoned)
       if (slope != 1.f) v = pe_lrelu(v, slope);
-      XT[c * G4_XS + ch] = v;
+      XT[c * XS + ch] = v;
     }
   }
   __syncthreads();
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int 
     for (int g = 0; g < 3; ++g)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[g][r] = 0.f;
-    const float* xp = XT + l3 * G4_XS + 16 * wv;
+    const float* xp = XT + l3 * XS + 16 * wv;
 #pragma unroll
     for (int tp = 0; tp < 5; ++tp) {
       if (tp < ntaps) {
@@ -84,7 +90,7 @@ __global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int 
         for (int q = 0; q < 4; ++q) {
           f32x4 b4[3];
 #pragma unroll
-          for (int g = 0; g < 3; ++g) b4[g] = *reinterpret_cast<const f32x4*>(xp + (4 * g + tp) * G4_XS + 4 * q);
+          for (int g = 0; g < 3; ++g) b4[g] = *reinterpret_cast<const f32x4*>(xp + (4 * g + tp) * XS + 4 * q);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -107,14 +113,52 @@ __global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int 
     if (ch < p.split && t < L) {
       float ta = 0.f, sa = 0.f;
 #pragma unroll
-      for (int w = 0; w < G4_NW; ++w) {
+      for (int w = 0; w < NW; ++w) {
         ta += P[(w * 64 + c) * G4_NC + col];
         sa += P[(w * 64 + 32 + c) * G4_NC + col];
       }
-      conv_store_gate(p, b, ch, t, ta, sa);
+      if constexpr (K == G4P_K) {
+        // pre's bias through the taps inside [0, L) (see above); conv_store_gate's additions in its order otherwise
+        float bt = p.bias[ch], bs = p.bias[p.split + ch];
+        if (PE_UNIFORM(n0 < p.padl || n0 + G4_NC + ntaps - 1 - p.padl > L)) {
+          const int rs = 2 * p.split;
+          bt = tapb[5 * rs + ch];
+          bs = tapb[5 * rs + p.split + ch];
+          for (int k = 0; k < ntaps; ++k) {
+            const int u = t + k - p.padl;
+            if (u >= 0 && u < L) { bt += tapb[k * rs + ch]; bs += tapb[k * rs + p.split + ch]; }
+          }
+        }
+        ta += bt;
+        sa += bs;
+        if (p.bias2) {
+          const float* b2 = p.bias2 + (long)b * p.bias2_bs;
+          ta += b2[ch];
+          sa += b2[p.split + ch];
+        }
+        p.out[(long)b * p.o_bs + (long)ch * p.o_cs + t] = tanhf(ta) * (1.f / (1.f + expf(-sa)));
+      } else {
+        conv_store_gate(p, b, ch, t, ta, sa);
+      }
     }
   }
   PE_STAMP(5, 5);
+}
+
+__global__ __launch_bounds__(64 * G4_NW) void gate4_kernel(const int* lens, int len_mul, const float* x, long x_bs, int x_cs,
+                                                           int Cin, int padl, int ntaps_, const float* wpg4, ConvP p) {
+  PE_KTRACE(4);
+  p.lens = lens; p.len_mul = len_mul; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = Cin; p.padl = padl; p.ntaps = ntaps_;
+  p.wpg4 = wpg4;
+  gate4_body<G4_K>(p, nullptr);
+}
+// x = the 96 channels of x0 inside the latent (p.Cin == 96), wpg4 = the composed matrix, [group][tap][k quad 24][lane][4]
+__global__ __launch_bounds__(64 * G4P_NW) void gate4pre_kernel(const int* lens, int len_mul, const float* x, long x_bs, int x_cs,
+                                                               int padl, int ntaps_, const float* wpg4, const float* tapb, ConvP p) {
+  PE_KTRACE(4);
+  p.lens = lens; p.len_mul = len_mul; p.x = x; p.x_bs = x_bs; p.x_cs = x_cs; p.Cin = G4P_K; p.padl = padl; p.ntaps = ntaps_;
+  p.wpg4 = wpg4;
+  gate4_body<G4P_K>(p, tapb);
 }
 
 }  // namespace pe

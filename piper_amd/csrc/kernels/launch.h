@@ -23,6 +23,8 @@ void conv_splitk(bool gate, int nw, dim3 grid, size_t smem, hipStream_t stream, 
 void conv_splitk16(bool gate, dim3 grid, size_t smem, hipStream_t stream, const ConvP& p, bool half = false);
 // WN gate conv of short calls on 64-row x 12-column workgroups (gate4.h): grid = (12-column tiles, 32-channel groups, utterances)
 void gate4(dim3 grid, size_t smem, hipStream_t stream, const ConvP& p);
+// ... with the coupling layer's pre composed into it: K = 96 channels of x0, `tapb` = the per-tap bias table (gate4.h)
+void gate4pre(dim3 grid, size_t smem, hipStream_t stream, const ConvP& p, const float* tapb);
 void conv_group(bool wide, dim3 grid, size_t smem, hipStream_t stream, const ConvG& g);
 // the tiled kernel on up to three sibling convs of one tile configuration (conv_mfma.h: conv_mfma_group_kernel)
 void conv_tile_group(int cfg, int halo, dim3 grid, size_t smem, hipStream_t stream, const ConvG& g);

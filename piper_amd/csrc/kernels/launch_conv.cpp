@@ -87,6 +87,10 @@ void gate4(dim3 grid, size_t smem, hipStream_t stream, const ConvP& p) {
   PE_LAUNCH(gate4_kernel, grid, dim3(64 * G4_NW), smem, stream, p.lens, p.len_mul, p.x, p.x_bs, p.x_cs, p.Cin, p.padl, p.ntaps, p.wpg4, p);
 }
 
+void gate4pre(dim3 grid, size_t smem, hipStream_t stream, const ConvP& p, const float* tapb) {
+  PE_LAUNCH(gate4pre_kernel, grid, dim3(64 * G4P_NW), smem, stream, p.lens, p.len_mul, p.x, p.x_bs, p.x_cs, p.padl, p.ntaps, p.wpg4, tapb, p);
+}
+
 void conv_group(bool wide, dim3 grid, size_t smem, hipStream_t stream, const ConvG& g) {
   if (wide) PE_LAUNCH((conv_splitk_group_kernel<4, 2, 128>), grid, dim3(256), smem, stream, g.B, g);
   else PE_LAUNCH((conv_splitk_group_kernel<4, 2, 64>), grid, dim3(256), smem, stream, g.B, g);

@@ -46,7 +46,8 @@ struct LaunchPolicy {
   long stack_pre = 1;         // small calls: enc_p.proj and dp.pre as one lngemm4_kernel launch over the stacked matrix (0: two launches)
   long chain_rs = 1;          // small calls: the last WN layer's res/skip conv in front of the post + pre chain launch (0: a launch of its own)
   long gate4 = 1;             // short calls: the WN gate conv over 192 channels on 64-row x 12-column workgroups with the 4x4x1 MFMA (gate4_kernel) up to 640 workgroups
-  long gate_half = 1;         // short one-utterance calls: the WN gate conv on half a 32-channel group per workgroup (6 waves) while twice the workgroups still fit one per CU
+  long wn_compose = 1;        // one-utterance flow route: 1x1 convs composed into their neighbours at pack time: 0 off, 1 every composition built, 2 only pre -> first gate conv, 3 only post -> skip convs (not built: the route of 0)
+  long gate_half = 1;       // short one-utterance calls: the WN gate conv on half a 32-channel group per workgroup (6 waves) while twice the workgroups still fit one per CU
   long conv1x1 = 1;           // batched one-tap convs through conv1x1_kernel (B operand straight from global memory): 0 = the tiled kernel
   long ws_budget_mb = 0;      // MiB a stage's workspace may take: 0 = a third of the device's memory
   long attn_long = 0;         // attention score slabs in global memory at every length (tests; by default only where they do not fit LDS)
@@ -112,6 +113,8 @@ struct LaunchPolicy {
   bool attn4_ids(long longest_utterance) const { return attn4 == 2 || (attn4 == 1 && longest_utterance <= attn4_maxc); }
   bool chain4_frames(long cols) const { return chain4(cols, col4_max_frames); }
   bool chain_rs_front(long cols) const { return chain_rs && chain4_frames(cols); }
+  // a coupling layer's pre composed into its first gate conv (gate4pre_kernel), where the 4-column chain and gate4_kernel run
+  bool compose_pre() const { return wn_compose == 1 || wn_compose == 2; }
   // fused MRF stage
   bool mrf_build(int channels) const { return mrf != 0 && channels <= 64 && channels % 4 == 0; }
   // `split_fused`: the engine runs a two-term split matrix mode AND holds the stage's split weight stream (mrf_split_kernel):

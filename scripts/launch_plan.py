@@ -1,6 +1,6 @@
 """Launch plan of the engine on the kernel emulator, no GPU needed: what a refactor of the launch code must leave unchanged.
 
-    make emu && python scripts/launch_plan.py OUT [--root CHECKOUT] [--jobs 16]
+    make emu && python scripts/launch_plan.py OUT [--root CHECKOUT] [--jobs 16] [--env KNOB=VALUE]
 
 runs a fixed list of cases, each in a fresh process (policy knobs, the matrix mode and the emulator's plan-only mode are
 read once per process), and writes per case under OUT/<case>/
@@ -133,10 +133,11 @@ def run_case(case, out, root):
         np.concatenate(durs or [np.zeros(0, np.int32)]).tofile(os.path.join(out, "durations.i32"))
 
 
-def spawn(case, out_root, root):
+def spawn(case, out_root, root, base_env):
     out = os.path.join(out_root, case["name"])
     os.makedirs(out)
     env = {k: v for k, v in os.environ.items() if not k.startswith(("PIPER_HIP_", "EMU_"))}
+    env.update(base_env)
     env.update(case["env"], EMU_PLAN_TRACE=os.path.join(out, "trace.txt"), PIPER_HIP_MATRIX=case["matrix"])
     if case["frames"] is not None:
         env.update(EMU_PLAN_ONLY="1", EMU_PLAN_FRAMES=str(case["frames"]))
@@ -163,6 +164,9 @@ def main():
     ap.add_argument("--root", default=HERE, help="checkout whose piper_amd package and emulator library run the cases")
     ap.add_argument("--jobs", type=int, default=16)
     ap.add_argument("--only", default="", help="run only the cases whose name starts with this")
+    ap.add_argument("--env", action="append", default=[], metavar="KNOB=VALUE",
+                    help="a policy knob set for every case, under the case's own settings (e.g. PIPER_HIP_WN_COMPOSE=0: the "
+                         "tree of a parent that has no such knob)")
     ap.add_argument("--case", help=argparse.SUPPRESS)
     a = ap.parse_args()
     root = os.path.abspath(a.root)
@@ -174,7 +178,7 @@ def main():
         ap.error(f"{a.out} is not empty")
     os.makedirs(a.out, exist_ok=True)
     with ThreadPoolExecutor(max(1, min(a.jobs, 16))) as pool:
-        done = list(pool.map(lambda c: spawn(c, a.out, root), todo))
+        done = list(pool.map(lambda c: spawn(c, a.out, root, dict(kv.split("=", 1) for kv in a.env)), todo))
     bad = [(n, rc, err) for n, rc, err in done if rc]
     for n, rc, err in bad:
         print(f"FAILED {n} (exit {rc})\n{err}", file=sys.stderr)
