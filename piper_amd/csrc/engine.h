@@ -407,6 +407,7 @@ class Engine {
   const float* pack4_conv_pad192(const WeightSet& ws, const std::string& wname, int in_rev, int out_rev);
   struct Rcl;
   void pack_gate4pre(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r);
+  void pack_post4(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r);
   // the first gate conv of coupling layer `r` with its pre composed in, over x0 (gate4pre_kernel); b2 = the speaker bias or null
   void gate_pre(const Rcl& r, View x0, View out, const int* lens, int Lmax, double cols, const float* b2);
   // second: rows >= split of a STACKED pack4 matrix (w4) are another conv over the same LN(y), written to out2 with the
@@ -500,6 +501,10 @@ class Engine {
     // pre composed into the first gate conv (gate4pre_kernel, kernels/gate4.h; null: shapes it is not built for): the
     // matrix Wg_k . Wp in gate4 order over 96 channels, b_gate + sum_k Wg_k . b_pre, and the per-tap table behind it
     const float* gpre4 = nullptr; const float* gpre_bias = nullptr; const float* gpre_tapb = nullptr;
+    // post composed into the skip convs (engine_pack.cpp pack_post4; empty: shapes it is not built for). Per WN layer j the
+    // pack4 matrix [Wres_j ; M_j] (288 rows; the last layer: M_j alone, 96 rows) with M_j = Wpost . Wskip_j in post's packed
+    // row order, and its bias [bres_j ; c_j], c_j = Wpost . bskip_j (+ bpost for j = 0)
+    std::vector<const float*> rsp4, rsp_bias;
     int in_off, out_off;             // channel offsets of x0 / x1 in the physical (unflipped) layout
   };
   std::vector<Rcl> rcls_;            // in execution order

@@ -377,11 +377,24 @@ void Engine::issue_flow() {
   // ... and where the chain is 4 columns wide and the gate conv runs on gate4_kernel: pre composed into the first gate conv
   // (gate4pre_kernel reads x0; nobody computes h = pre(x0) in front of the WN -- the first res/skip launch writes h + res_0 in
   // one piece). With PIPER_HIP_CHAIN_RS=0 too: that knob only moves the last res/skip conv, one launch per coupling layer.
-  auto compose_pre_of = [&](size_t ri) {
-    if (ri >= rcls_.size() || !pol_.compose_pre() || !rs_front_of(ri, false)) return false;
+  auto compose_route_of = [&](size_t ri) {      // the route of every composition, whichever of them the knob asks for
+    if (ri >= rcls_.size() || !rs_front_of(ri, false)) return false;
     const Rcl& r = rcls_[ri];
     return r.in.size() >= 2 && r.gpre4 && r.rs4[0] && r.rs[0].rows == 2 * H_ && w4_of(r.pre16) && r.pre.rows == H_ &&
            plan_conv(r.in[0], Fmax, EPI_GATE, stage_tiled_).form == CONV_GATE12;
+  };
+  auto compose_pre_of = [&](size_t ri) { return pol_.compose_pre() && compose_route_of(ri); };
+  // ... and post composed into the skip convs (engine_pack.cpp pack_post4): every WN layer adds post . skip_j, 96 rows, into the
+  // first 96 rows of the skip sum -- s_0 = M_0 a_0 + c_0, s_j = (M_j a_j + c_j) + s_{j-1} -- and the chain launch has no post GEMM:
+  // x1 <- x1 - s_{nl-1}. Launch for launch the route without it, with PIPER_HIP_CHAIN_RS=0 too; on pre's route only (the
+  // knob changes nothing where gate4_kernel does not run).
+  auto compose_post_of = [&](size_t ri) {
+    if (!pol_.compose_post() || !compose_route_of(ri)) return false;
+    const Rcl& r = rcls_[ri];
+    if (r.rsp4.size() != r.in.size()) return false;
+    for (size_t j = 0; j < r.rsp4.size(); ++j)
+      if (!r.rsp4[j] || !r.rsp_bias[j]) return false;
+    return true;
   };
   for (size_t ri = 0; ri < rcls_.size(); ++ri) {
     Rcl& r = rcls_[ri];
@@ -394,7 +407,7 @@ void Engine::issue_flow() {
         conv(r.pre, x0, fh, lens_b_, 1, Fmax, EPI_STORE);
     }
     const int nl = (int)r.in.size();
-    const bool rs_front = rs_front_of(ri);
+    const bool rs_front = rs_front_of(ri), compose_post = compose_post_of(ri);
     for (int i = 0; i < nl; ++i) {
       const float* b2 = nspk_ > 1 ? cond_ + cond_off_wn_[ri] + (long)i * 2 * H_ : nullptr;
       if (compose_pre && i == 0) gate_pre(r, x0, facts, lens_b_, Fmax, fsum, b2);
@@ -408,6 +421,9 @@ void Engine::issue_flow() {
         ColP cp{};
         cp.in1 = facts.p; cp.in1_bs = facts.bs; cp.in1_cs = facts.cs; cp.K1 = H_;
         cp.w1 = r.rs4[i]; cp.b1 = r.rs[i].bias; cp.rows1 = r.rs[i].rows;
+        if (compose_post) {      // the skip rows: post . skip_i, 96 of them
+          cp.w1 = r.rsp4[i]; cp.b1 = r.rsp_bias[i]; cp.rows1 = r.rs[i].rows - H_ + half;
+        }
         cp.mode = 2; cp.first = i == 0 ? 1 : 0;
         cp.xcd = xcd_period_;
         cp.x1 = fh.p; cp.x1_bs = fh.bs; cp.x1_cs = fh.cs;
@@ -419,7 +435,7 @@ void Engine::issue_flow() {
           cp.w2 = w4_of(r.pre16); cp.b2 = r.pre.bias; cp.rows2 = H_;
         }
         const int kh4 = kbegin(prof_level_ >= 2 ? krow("colchain4_kernel<false>") : 0,
-                               2.0 * fsum * (r.rs[i].macs_per_col + (hpre ? r.pre.macs_per_col : 0)),
+                               2.0 * fsum * ((double)cp.rows1 * H_ + (hpre ? r.pre.macs_per_col : 0)),
                                4.0 * (fsum * (H_ + 2.0 * cp.rows1) + (double)cp.rows1 * H_ + (hpre ? half * (fsum + H_) : 0)));
         launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem() + (hpre ? 4 * (96 + 4) * sizeof(float) : 0), stream_, cp);
         kend(kh4);
@@ -446,8 +462,12 @@ void Engine::issue_flow() {
         cp.in0 = facts.p; cp.in0_bs = facts.bs; cp.in0_cs = facts.cs;
         cp.w0 = r.rs4[nl - 1]; cp.b0 = r.rs[nl - 1].bias; cp.first = nl == 1 ? 1 : 0;
       }
-      colchain(cp, B, Fmax, 2.0 * fsum * (r.post.macs_per_col + (cp.w2 ? rcls_[ri + 1].pre.macs_per_col : 0) +
-                                          (rs_front ? r.rs[nl - 1].macs_per_col : 0)));
+      if (compose_post) {        // the skip sum is m: no post GEMM
+        cp.K1 = half; cp.w1 = nullptr; cp.b1 = nullptr;
+        if (rs_front) { cp.w0 = r.rsp4[nl - 1]; cp.b0 = r.rsp_bias[nl - 1]; }
+      }
+      colchain(cp, B, Fmax, 2.0 * fsum * ((compose_post ? 0 : r.post.macs_per_col) + (cp.w2 ? rcls_[ri + 1].pre.macs_per_col : 0) +
+                                          (rs_front ? (compose_post ? (double)half * H_ : r.rs[nl - 1].macs_per_col) : 0)));
     } else {
       conv(r.post, fskip, x1, lens_b_, 1, Fmax, EPI_SUBFROM);
     }

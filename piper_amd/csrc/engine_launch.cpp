@@ -610,24 +610,25 @@ bool Engine::conv1x1_col4(const float* w16, const float* bias, int rows, View in
 void Engine::colchain(const ColP& p, int B, int Lmax, double flops) {
   // algorithmic bytes: GEMM input, the residual / x1 read and written, the second GEMM's output; weights once
   const double cols = p.lens == d_tlens_ ? cols_ids_ : cols_frames_;
-  const double kbytes = 4.0 * (cols * (p.K1 + 2.0 * p.rows1 + (p.w2 ? p.rows2 : 0)) + (double)p.rows1 * p.K1 +
+  // (w1 == null: post composed into the skip convs, kernels/col4.h -- no first GEMM, in1 is subtracted as it is)
+  const double kbytes = 4.0 * (cols * (p.K1 + 2.0 * p.rows1 + (p.w2 ? p.rows2 : 0)) + (p.w1 ? (double)p.rows1 * p.K1 : 0.0) +
                                (p.w2 ? (double)p.rows2 * p.rows1 : 0.0));
   // mode 1 runs on frames (coupling post + pre), mode 0 on ids: separate column limits (profiles/r03_notes.md)
-  if ((p.mode == 1 ? pol_.chain4_frames((long)B * Lmax) : pol_.chain4((long)B * Lmax)) && p.K1 == 192 && (p.mode == 0 ? p.rows1 == 192 : (p.rows1 == 96 && (!p.w2 || p.rows2 <= 192)))) {
-    const float* w1 = w4_of(p.w1);
+  if ((p.mode == 1 ? pol_.chain4_frames((long)B * Lmax) : pol_.chain4((long)B * Lmax)) && p.K1 == (p.w1 ? 192 : 96) && (p.mode == 0 ? p.w1 && p.rows1 == 192 : (p.rows1 == 96 && (!p.w2 || p.rows2 <= 192)))) {
+    const float* w1 = p.w1 ? w4_of(p.w1) : nullptr;
     const float* w2 = p.w2 ? w4_of(p.w2) : nullptr;
-    if (w1 && (!p.w2 || w2)) {
+    if ((w1 || !p.w1) && (!p.w2 || w2)) {
       ColP q = p;
       q.w1 = w1; q.w2 = w2;
       q.xcd = xcd_period_;
-      const double kb0 = q.w0 ? 4.0 * (cols * 192.0 + 192.0 * 192.0) : 0.0;      // the front conv: its input, its weights
+      const double kb0 = q.w0 ? 4.0 * (cols * 192.0 + (q.w1 ? 192.0 : 96.0) * 192.0) : 0.0;      // the front conv: its input, its weights
       const int kh4 = kbegin(prof_level_ >= 2 ? krow(q.w0 ? "colchain4_kernel<true>" : "colchain4_kernel<false>") : 0, flops, kbytes + kb0);
       launch::colchain4(dim3((Lmax + 3) / 4, B), col4_smem(), stream_, q);
       kend(kh4);
       return;
     }
   }
-  if (p.w0) throw std::runtime_error("internal: a res/skip conv in front of a chain that does not take the 4-column form");
+  if (p.w0 || !p.w1) throw std::runtime_error("internal: a res/skip conv in front of a chain that does not take the 4-column form");
   const int kh = kbegin(prof_level_ >= 2 ? krow("colchain_kernel<6>") : 0, flops, kbytes);
   const size_t smem = ((size_t)2 * 6 * 32 * 16 + 16 * 16) * sizeof(float);
   launch::colchain(dim3((Lmax + 15) / 16, B), smem, stream_, p);

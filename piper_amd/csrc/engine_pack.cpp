@@ -431,6 +431,53 @@ void Engine::pack_gate4pre(const WeightSet& ws, const std::string& prefix, bool 
   r.gpre_tapb = dev_alloc((size_t)6 * R, skeleton_ ? nullptr : tapb.data());
 }
 
+// A coupling layer's post (1x1, 192 -> half, the Flip folded into its output rows as in pack16_conv(.., 0, odd)) composed into
+// the skip rows of every WN res/skip conv, for colchain4_kernel modes 2 and 1 (kernels/col4.h): m = post(sum_j skip_j(acts_j))
+// is linear in every acts_j (modules.py:200-208, 455-468), so layer j adds M_j . acts_j + c_j with M_j = Wpost . Wskip_j
+// (half x 192) and c_j = Wpost . bskip_j, bpost riding in c_0 -- computed in f64 and rounded once. Wskip_j = rows [H, 2H) of
+// res_skip_layers.j, every row of the last one. Layers in front of the last: one pack4 matrix [Wres_j ; M_j] of 288 rows
+// (row part 1 of the launch starts at tile 3, as with the plain matrix) and the bias [bres_j ; c_j]; the last: M_j alone.
+// Only the shapes the 4-column chain runs on; anything else leaves the coupling layer on the plain route.
+void Engine::pack_post4(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r) {
+  const HostTensor& wpo = ws.get(prefix + ".post.weight");
+  const int nl = (int)r.in.size(), H = 192, half = 96;
+  if (H_ != H || C_ / 2 != half || nl < 1 || wpo.dims.size() != 3 || wpo.dims[2] != 1 || (int)wpo.dims[0] != half || (int)wpo.dims[1] != H) return;
+  for (int j = 0; j < nl; ++j) {
+    const HostTensor& w = ws.get(prefix + ".enc.res_skip_layers." + std::to_string(j) + ".weight");
+    if (!r.rs4[j] || w.dims.size() != 3 || w.dims[2] != 1 || (int)w.dims[1] != H || (int)w.dims[0] != (j < nl - 1 ? 2 * H : H)) return;
+  }
+  const std::string bpn = prefix + ".post.bias";
+  std::vector<double> acc(H);
+  for (int j = 0; j < nl; ++j) {
+    const bool last = j == nl - 1;
+    const int res = last ? 0 : H, rows = res + half;
+    const std::string rsn = prefix + ".enc.res_skip_layers." + std::to_string(j);
+    std::vector<float> W(skeleton_ ? 0 : (size_t)rows * H), B(skeleton_ ? 0 : rows, 0.f);
+    if (!skeleton_) {
+      const HostTensor& w = ws.get(rsn + ".weight");
+      const float* bs = ws.has(rsn + ".bias") ? ws.get(rsn + ".bias").data.data() : nullptr;
+      const float* bpo = ws.has(bpn) ? ws.get(bpn).data.data() : nullptr;
+      std::copy(w.data.begin(), w.data.begin() + (size_t)res * H, W.begin());
+      if (bs) std::copy(bs, bs + res, B.begin());
+      for (int o = 0; o < half; ++o) {
+        const float* pr = &wpo.data[(size_t)(odd ? half - 1 - o : o) * H];
+        std::fill(acc.begin(), acc.end(), 0.0);
+        double c = (j == 0 && bpo) ? (double)bpo[odd ? half - 1 - o : o] : 0.0;
+        for (int s = 0; s < H; ++s) {
+          const double a = pr[s];
+          const float* sr = &w.data[(size_t)(res + s) * H];
+          for (int i = 0; i < H; ++i) acc[i] += a * sr[i];
+          if (bs) c += a * bs[res + s];
+        }
+        for (int i = 0; i < H; ++i) W[(size_t)(res + o) * H + i] = (float)acc[i];
+        B[res + o] = (float)c;
+      }
+    }
+    r.rsp4.push_back(pack4(W, rows, H));
+    r.rsp_bias.push_back(dev_alloc((size_t)rows, skeleton_ ? nullptr : B.data()));
+  }
+}
+
 DdsW Engine::load_dds(const WeightSet& ws, const std::string& p) {
   DdsW d;
   for (int i = 0; i < arch_[A_DDSLAYERS]; ++i) {
@@ -592,6 +639,7 @@ void Engine::init(const WeightSet& ws) {
       if (H_ == 192 && rcls_.empty()) r.pre4pad = pack4_conv_pad192(ws, p + ".pre.weight", odd, 0);   // first layer's pre: a launch of its own
       r.post16 = pack16_conv(ws, p + ".post.weight", 0, odd);
       if (wnl >= 2) pack_gate4pre(ws, p, odd, r);
+      pack_post4(ws, p, odd, r);
       rcls_.push_back(r);
       if (gin_) {
         const HostTensor& cw = ws.get(p + ".enc.cond_layer.weight");

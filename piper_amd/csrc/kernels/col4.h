@@ -127,6 +127,12 @@ __device__ __forceinline__ float pe_col_sum4(float v, float* red, int& flip, int
 // the post conv's input is (W0.in0 + b0) + in1 instead of in1 (in1 = the skip sum of the layers before; `first`: not
 // read). The same additions in the same order as the mode-2 launch it replaces, whose output is not written at all: the
 // skip sum of a coupling layer has no other reader.
+// POST COMPOSED (w1 == null, mode 1; engine_pack.cpp pack_post4): every WN layer's skip rows are post . skip_j, 96 rows, so
+// the skip sum IS the coupling layer's m and there is no main GEMM: x1 -= in1 (96 rows; FRONT: x1 -= (W0.in0 + b0) + in1, W0
+// = the last layer's 96 composed rows, two tiles), no YT restaging, no fragments of w1, no barrier pair; the old x1 is
+// requested in front of the front GEMM. One branch at the top, ending in the same tail as the plain chain: the code of
+// every other mode is what it was. The mode-2 launches of such a layer run with rows1 = 288 (part 1: 96 rows from tile 3)
+// or 96 (the last layer on its own) and need nothing of their own. w2 / out2 work as before.
 // Kernel entry (pe_rt.h PE_ENTRY_BATCH): the leading parameters repeat p's fields of the same names and arrive in SGPRs
 // (14 dwords); nx = gridDim.x. The length decides whether the workgroup runs at all, so its pointer comes first: lens[b]
 // is requested together with the rest of the struct and both are waited for once.
@@ -143,7 +149,7 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   const int b = blockIdx.y;
   int L = PE_UNIFORM(lens[b]);                              // decides whether the workgroup runs: part of the batch, one wait for both
   if constexpr (FRONT) PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1,
-                                      p.in0, p.in0_bs, p.in0_cs, p.w0, p.b0);
+                                      p.in0, p.in0_bs, p.in0_cs, p.w0, p.b0, p.w2, p.b2, p.rows2, p.out2, p.o2_bs, p.o2_cs);
   else PE_ENTRY_BATCH(L, p.res, p.res_bs, p.res_cs, p.gamma, p.beta, p.out, p.out_bs, p.x1, p.x1_bs, p.x1_cs, p.b1, p.w1,
                       p.in0, p.in0_bs, p.in0_cs, p.w2, p.b2, p.kT, p.kt_bs, p.vQ);
   const int t0 = c4_tile(blockIdx.x, nx, p.xcd) * NC;
@@ -160,6 +166,7 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   // Weight fragments are requested BEHIND the (few) input loads of the phase they belong to: a wave reaches its LDS stores
   // only after the vector-memory pipe has taken every load in front of them, and the memory counter retires in order, so
   // 36 16-byte loads per lane in front of the inputs put their whole fetch on the staging's critical path (profiles/r04_notes.md, calls 60-65)
+  const bool nomain = p.mode == 1 && !p.w1;      // post composed into the skip convs: in1 (FRONT: the front product + in1) is m itself
   Col4W<K1> gw0;                                 // FRONT: the res/skip conv's fragments
   Col4W<K1> gw;                                  // first GEMM's fragments
   auto fetch_gw = [&]() { col_gemm4_fetch<K1>(gw, p.w1 + (long)part * C4_NT * (K1 / 4) * 256, (rows_here + 63) / 64, wv, lane); };
@@ -167,6 +174,78 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   const bool pre_part = !FRONT && p.mode == 2 && p.w2 && !skip_part;      // mode 2 with w2: the res part also adds pre(x0)
   float* YTP = P + 4 * C4_H * NC + 32 + 64 * 4;   // pre_part: x0 as [4][KS2], behind red and dds4.h's ZL (the launcher adds the room)
   Col4W<K2> gw2;                                 // second GEMM's fragments: the next layer's pre (mode 1), this layer's (pre_part)
+  // mode 1 from the x1 update on: x1 <- x1 - m; the updated half is the next layer's x0
+  const bool second = p.mode == 1 && p.w2;
+  auto chain_tail = [&](auto m_of, const float* ovv) {
+    float* xb = p.x1 + (long)b * p.x1_bs;
+    float* YT2 = YT;                             // [4][KS2]: the first GEMM's reads of YT ended before the barrier in front
+    const pe_rowsrc b2d = pe_make_row(second ? p.b2 : p.w1, (second && p.b2) ? p.rows2 : 0);
+    float b2v[NVT];
+#pragma unroll
+    for (int k = 0; k < NVT; ++k) b2v[k] = pe_row_load(b2d, rl + 64 * k);
+#pragma unroll
+    for (int k = 0; k < NVT; ++k) {
+      const int c = rl + 64 * k;
+      if (c < K2) {
+        const float xn = (ok && c < p.rows1) ? ovv[k] - m_of(k, c) : 0.f;
+        if (ok && c < p.rows1) xb[(long)c * p.x1_cs + t] = xn;
+        YT2[col * KS2 + c] = xn;
+      }
+    }
+    if (!second) return;
+    __syncthreads();                             // YT2 complete; every read of the first product done
+    col_gemm4_run<K2>(gw2, YT2, P, wv, lane);
+    __syncthreads();
+    if (!ok) return;
+    float* o2 = p.out2 + (long)b * p.o2_bs;
+#pragma unroll
+    for (int k = 0; k < NVT; ++k) {
+      const int c = rl + 64 * k;
+      if (c < p.rows2) o2[(long)c * p.o2_cs + t] = col_gemm4_get(P, c, col) + b2v[k];
+    }
+  };
+  if (nomain) {
+    // post composed: m = the skip sum over 96 rows (slots k = 0, 1 of a thread), completed by the front conv where there is one
+    const pe_rowsrc s0 = pe_make_row(p.in1 + (long)b * p.in1_bs, (FRONT && p.first) ? 0 : K2 * p.in1_cs);
+    const pe_rowsrc x1d = pe_make_row(p.x1 + (long)b * p.x1_bs, K2 * p.x1_cs);
+    float m[NVT], ovn[NVT];
+    m[2] = ovn[2] = 0.f;
+    if constexpr (FRONT) {
+      const pe_rowsrc a0 = pe_make_row(p.in0 + (long)b * p.in0_bs, K1 * p.in0_cs);
+      const pe_rowsrc b0d = pe_make_row(p.b0 ? p.b0 : p.w0, p.b0 ? K2 : 0);
+      float av[NVT], b0v[2];
+#pragma unroll
+      for (int k = 0; k < NVT; ++k) av[k] = pe_row_load(a0, ok ? (rl + 64 * k) * p.in0_cs + t : -1);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int c = rl + 64 * k;
+        m[k] = pe_row_load(s0, (ok && c < K2) ? c * p.in1_cs + t : -1);
+        b0v[k] = pe_row_load(b0d, c);
+        ovn[k] = pe_row_load(x1d, (ok && c < K2) ? c * p.x1_cs + t : -1);      // flies under the front GEMM
+      }
+      PE_SCHED_FENCE();
+      col_gemm4_fetch<K1>(gw0, p.w0, (K2 + 63) / 64, wv, lane);
+#pragma unroll
+      for (int k = 0; k < NVT; ++k) YT[col * KS1 + rl + 64 * k] = av[k];
+      __syncthreads();
+      if (second) col_gemm4_fetch<K2>(gw2, p.w2, (p.rows2 + 63) / 64, wv, lane);      // in flight under the front GEMM
+      col_gemm4_run<K1>(gw0, YT, P, wv, lane);
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 2; ++k) m[k] = ok ? (col_gemm4_get(P, rl + 64 * k, col) + b0v[k]) + m[k] : 0.f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int c = rl + 64 * k;
+        m[k] = pe_row_load(s0, (ok && c < K2) ? c * p.in1_cs + t : -1);
+        ovn[k] = pe_row_load(x1d, (ok && c < K2) ? c * p.x1_cs + t : -1);
+      }
+      PE_SCHED_FENCE();
+      if (second) col_gemm4_fetch<K2>(gw2, p.w2, (p.rows2 + 63) / 64, wv, lane);
+    }
+    chain_tail([&](int k, int) { return m[k]; }, ovn);
+    return;
+  }
   float sk[NVT];                                 // FRONT: the completed skip sum of this thread's (channel, column) slots
   if constexpr (FRONT) {
     const pe_rowsrc a0 = pe_make_row(p.in0 + (long)b * p.in0_bs, K1 * p.in0_cs);
@@ -233,7 +312,6 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
   if (pre_part) col_gemm4_run2<K1, K2>(gw, YT, gw2, YTP, P, wv, lane);
   else col_gemm4_run<K1>(gw, YT, P, wv, lane);
   // second GEMM's fragments (the next layer's pre): in flight under the x1 update
-  const bool second = p.mode == 1 && p.w2;
   if (second) col_gemm4_fetch<K2>(gw2, p.w2, (p.rows2 + 63) / 64, wv, lane);
   __syncthreads();
 
@@ -281,35 +359,8 @@ __global__ __launch_bounds__(256) void colchain4_kernel(const int* lens, const f
     return;
   }
 
-  // mode 1: x1 <- x1 - (post + bias); the updated half is the next layer's x0
-  {
-    float* xb = p.x1 + (long)b * p.x1_bs;
-    float* YT2 = YT;                             // [4][KS2]: the first GEMM's reads of YT ended before the barrier above
-    const pe_rowsrc b2d = pe_make_row(second ? p.b2 : p.w1, (second && p.b2) ? p.rows2 : 0);
-    float b2v[NVT];
-#pragma unroll
-    for (int k = 0; k < NVT; ++k) b2v[k] = pe_row_load(b2d, rl + 64 * k);
-#pragma unroll
-    for (int k = 0; k < NVT; ++k) {
-      const int c = rl + 64 * k;
-      if (c < K2) {
-        const float xn = (ok && c < p.rows1) ? ov[k] - (col_gemm4_get(P, c, col) + b1v[k]) : 0.f;
-        if (ok && c < p.rows1) xb[(long)c * p.x1_cs + t] = xn;
-        YT2[col * KS2 + c] = xn;
-      }
-    }
-    if (!second) return;
-    __syncthreads();                             // YT2 complete; every read of the first product done
-    col_gemm4_run<K2>(gw2, YT2, P, wv, lane);
-    __syncthreads();
-    if (!ok) return;
-    float* o2 = p.out2 + (long)b * p.o2_bs;
-#pragma unroll
-    for (int k = 0; k < NVT; ++k) {
-      const int c = rl + 64 * k;
-      if (c < p.rows2) o2[(long)c * p.o2_cs + t] = col_gemm4_get(P, c, col) + b2v[k];
-    }
-  }
+  // mode 1: x1 <- x1 - (post + bias)
+  chain_tail([&](int k, int c) { return col_gemm4_get(P, c, col) + b1v[k]; }, ov);
 }
 
 // ------------------------------------------------------------------------------------------------

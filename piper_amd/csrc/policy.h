@@ -46,7 +46,7 @@ struct LaunchPolicy {
   long stack_pre = 1;         // small calls: enc_p.proj and dp.pre as one lngemm4_kernel launch over the stacked matrix (0: two launches)
   long chain_rs = 1;          // small calls: the last WN layer's res/skip conv in front of the post + pre chain launch (0: a launch of its own)
   long gate4 = 1;             // short calls: the WN gate conv over 192 channels on 64-row x 12-column workgroups with the 4x4x1 MFMA (gate4_kernel) up to 640 workgroups
-  long wn_compose = 1;        // one-utterance flow route: 1x1 convs composed into their neighbours at pack time: 0 off, 1 every composition built, 2 only pre -> first gate conv, 3 only post -> skip convs (not built: the route of 0)
+  long wn_compose = 1;        // one-utterance flow route: 1x1 convs composed into their neighbours at pack time: 0 off, 1 every composition built (pre and post), 2 only pre -> first gate conv, 3 the route of 0, 4 only post -> skip convs
   long gate_half = 1;       // short one-utterance calls: the WN gate conv on half a 32-channel group per workgroup (6 waves) while twice the workgroups still fit one per CU
   long conv1x1 = 1;           // batched one-tap convs through conv1x1_kernel (B operand straight from global memory): 0 = the tiled kernel
   long ws_budget_mb = 0;      // MiB a stage's workspace may take: 0 = a third of the device's memory
@@ -115,6 +115,8 @@ struct LaunchPolicy {
   bool chain_rs_front(long cols) const { return chain_rs && chain4_frames(cols); }
   // a coupling layer's pre composed into its first gate conv (gate4pre_kernel), where the 4-column chain and gate4_kernel run
   bool compose_pre() const { return wn_compose == 1 || wn_compose == 2; }
+  // a coupling layer's post composed into its WN skip convs (96 skip rows per WN layer, no post GEMM), where the 4-column chain runs
+  bool compose_post() const { return wn_compose == 1 || wn_compose == 4; }
   // fused MRF stage
   bool mrf_build(int channels) const { return mrf != 0 && channels <= 64 && channels % 4 == 0; }
   // `split_fused`: the engine runs a two-term split matrix mode AND holds the stage's split weight stream (mrf_split_kernel):
