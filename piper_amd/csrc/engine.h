@@ -401,11 +401,18 @@ class Engine {
   // enc_p.proj and dp.pre stacked for lngemm4_kernel (small calls): pack4 matrix, stacked bias, rows of proj
   float* projpre4_ = nullptr; float* projpre_bias_ = nullptr; int projpre_split_ = 0;
   void colchain(const struct ColP& p, int B, int Lmax, double flops);
+  // The route of every coupling layer of a call, decided once per issue_flow (engine_internal.h: FlowLayerPlan): a pure
+  // function of the packed layers (Rcl's *_ok flags), the policy and the call's size.
+  std::vector<struct FlowLayerPlan> plan_flow(int B, int Fmax, double fsum) const;
+  // The three colchain launches that are not plain convs; they alone fill ColP for their mode (engine_launch.cpp).
+  struct EncLayer; struct Rcl;
+  void conv_o_ln(const EncLayer& e, View att, View x, int B, int T, double tsum);
+  void wn_res_skip4(const Rcl& r, int layer, const struct FlowLayerPlan& pl, View x0, View facts, View fh, View fskip, int B, int Fmax, double fsum);
+  void coupling_chain(const Rcl& r, const Rcl* next, const struct FlowLayerPlan& pl, View x1, View facts, View fskip, View fh, int B, int Fmax, double fsum);
   bool conv1x1_col4(const float* w16, const float* bias, int rows, View in, View out, const int* lens, int B, int Lmax,
                     double flops, const float* bias2 = nullptr, long bias2_bs = 0, const float* w4direct = nullptr, int kin = 192,
                     long max_cols = 0);
   const float* pack4_conv_pad192(const WeightSet& ws, const std::string& wname, int in_rev, int out_rev);
-  struct Rcl;
   void pack_gate4pre(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r);
   void pack_post4(const WeightSet& ws, const std::string& prefix, bool odd, Rcl& r);
   // the first gate conv of coupling layer `r` with its pre composed in, over x0 (gate4pre_kernel); b2 = the speaker bias or null
@@ -423,7 +430,8 @@ class Engine {
   int xcc_of_[64] = {0};
   int xcd_period_ = 0;
   void probe_xcds();
-  static size_t col4_smem() { return ((size_t)4 * 196 + 4 * 192 * 4 + 32 + 64 * 4) * sizeof(float); }   // YT | P | red | ZL (kernels/col4.h, dds4.h)
+  // YT | P | red | ZL (kernels/col4.h, dds4.h); with_x0: colchain4_kernel's pre_part keeps x0 as [4][96 + 4] behind them (col4.h: YTP = P + 4 * C4_H * NC + 32 + 64 * 4)
+  static size_t col4_smem(bool with_x0 = false) { return ((size_t)4 * 196 + 4 * 192 * 4 + 32 + 64 * 4 + (with_x0 ? 4 * (96 + 4) : 0)) * sizeof(float); }
   void issue_stage_a();
   void issue_stage_b();
   void issue_flow();
@@ -505,6 +513,9 @@ class Engine {
     // pack4 matrix [Wres_j ; M_j] (288 rows; the last layer: M_j alone, 96 rows) with M_j = Wpost . Wskip_j in post's packed
     // row order, and its bias [bres_j ; c_j], c_j = Wpost . bskip_j (+ bpost for j = 0)
     std::vector<const float*> rsp4, rsp_bias;
+    bool front4_ok = false;          // the last res/skip conv, post and the next layer's pre are packed for the 4-column chain launch
+    bool compose_pre_ok = false;     // pre is packed into the first gate conv, and the first res/skip launch can write the whole hidden state
+    bool compose_post_ok = false;    // post is packed into the skip rows of every res/skip conv
     int in_off, out_off;             // channel offsets of x0 / x1 in the physical (unflipped) layout
   };
   std::vector<Rcl> rcls_;            // in execution order

@@ -105,4 +105,17 @@ struct ConvPlan {
   int group_cfg = CFG_S;                               // ... the latter on this tile configuration (CFG_C or CFG_S)
 };
 
+// One coupling layer of a call, decided once by Engine::plan_flow and carried out by issue_flow's loop and the launch
+// helpers wn_res_skip4 / coupling_chain.
+struct FlowLayerPlan {
+  bool chain = false;               // post + "x1 -= m" (+ the next layer's pre) as a chain launch, not conv(post)
+  bool pre_launch = false;          // this layer's pre is a launch of its own (else: the previous chain wrote it, or it is composed) ...
+  bool pre_col4 = false;            // ... on colchain4_kernel mode 3 through pre4pad, not conv()
+  bool rs_front = false;            // the last res/skip conv rides in front of the chain launch
+  bool compose_pre = false;         // pre composed into the first gate conv (gate4pre_kernel); the first res/skip launch writes h whole
+  bool compose_post = false;        // post composed into the skip rows; the chain launch has no post GEMM
+  bool chain_has_next_pre = false;  // the chain launch writes the next layer's hidden state
+  std::vector<bool> rs_col4;        // per WN layer: its res/skip launch goes to colchain4_kernel mode 2, not conv()
+};
+
 }  // namespace pe

@@ -183,16 +183,7 @@ void Engine::issue_stage_a() {
     kend(kh);
     const bool chain_o = chain_q;
     if (chain_o) {
-      // conv_o + residual + norm_layers_1 in one launch (the 192 x 192 GEMM fits one workgroup per 16 columns)
-      ColP cp{};
-      cp.in1 = att.p; cp.in1_bs = att.bs; cp.in1_cs = att.cs; cp.K1 = H_;
-      cp.w1 = e.o16; cp.b1 = e.o.bias; cp.rows1 = H_;
-      cp.mode = 0;
-      cp.res = x.p; cp.res_bs = x.bs; cp.res_cs = x.cs;
-      cp.gamma = e.g1; cp.beta = e.b1;
-      cp.out = x.p; cp.out_bs = x.bs; cp.out_cs = x.cs;
-      cp.lens = d_tlens_;
-      colchain(cp, B, T, 2.0 * tsum * e.o.macs_per_col);
+      conv_o_ln(e, att, x, B, T, tsum);
     } else {
       conv(e.o, att, y, d_tlens_, 1, T, EPI_RESADD, {.res = x});
     }
@@ -363,114 +354,29 @@ void Engine::issue_flow() {
   }
   auto VF = [&](float* p, int ch) { return View{p, (long)ch * Fs, Fs}; };
   const View fh = VF(fh_, H_), facts = VF(facts_, H_), fskip = VF(fskip_, H_);
-  const int half = C_ / 2;
-  const bool chain = pol_.chain16(fsum, true, H_, half);
-  // small calls: the LAST WN layer's res/skip conv (skip rows only) rides in front of the post + pre chain launch
-  // (`front` false: the same shapes whatever PIPER_HIP_CHAIN_RS says -- the chain launch takes its 4-column form)
-  auto rs_front_of = [&](size_t ri, bool front = true) {
-    const Rcl& r = rcls_[ri];
-    const int nl = (int)r.in.size();
-    return chain && nl >= 1 && r.rs4[nl - 1] && r.rs[nl - 1].rows == H_ && H_ == 192 && half == 96 &&
-           (front ? pol_.chain_rs_front((long)B * Fmax) : pol_.chain4_frames((long)B * Fmax)) && w4_of(r.post16) &&
-           (ri + 1 >= rcls_.size() || (rcls_[ri + 1].pre.rows <= 192 && w4_of(rcls_[ri + 1].pre16)));
-  };
-  // ... and where the chain is 4 columns wide and the gate conv runs on gate4_kernel: pre composed into the first gate conv
-  // (gate4pre_kernel reads x0; nobody computes h = pre(x0) in front of the WN -- the first res/skip launch writes h + res_0 in
-  // one piece). With PIPER_HIP_CHAIN_RS=0 too: that knob only moves the last res/skip conv, one launch per coupling layer.
-  auto compose_route_of = [&](size_t ri) {      // the route of every composition, whichever of them the knob asks for
-    if (ri >= rcls_.size() || !rs_front_of(ri, false)) return false;
-    const Rcl& r = rcls_[ri];
-    return r.in.size() >= 2 && r.gpre4 && r.rs4[0] && r.rs[0].rows == 2 * H_ && w4_of(r.pre16) && r.pre.rows == H_ &&
-           plan_conv(r.in[0], Fmax, EPI_GATE, stage_tiled_).form == CONV_GATE12;
-  };
-  auto compose_pre_of = [&](size_t ri) { return pol_.compose_pre() && compose_route_of(ri); };
-  // ... and post composed into the skip convs (engine_pack.cpp pack_post4): every WN layer adds post . skip_j, 96 rows, into the
-  // first 96 rows of the skip sum -- s_0 = M_0 a_0 + c_0, s_j = (M_j a_j + c_j) + s_{j-1} -- and the chain launch has no post GEMM:
-  // x1 <- x1 - s_{nl-1}. Launch for launch the route without it, with PIPER_HIP_CHAIN_RS=0 too; on pre's route only (the
-  // knob changes nothing where gate4_kernel does not run).
-  auto compose_post_of = [&](size_t ri) {
-    if (!pol_.compose_post() || !compose_route_of(ri)) return false;
-    const Rcl& r = rcls_[ri];
-    if (r.rsp4.size() != r.in.size()) return false;
-    for (size_t j = 0; j < r.rsp4.size(); ++j)
-      if (!r.rsp4[j] || !r.rsp_bias[j]) return false;
-    return true;
-  };
+  // the coupling layers, each on the route plan_flow chose for it (engine_launch.cpp, with what the routes are)
+  const std::vector<FlowLayerPlan> plan = plan_flow(B, Fmax, fsum);
   for (size_t ri = 0; ri < rcls_.size(); ++ri) {
-    Rcl& r = rcls_[ri];
+    const Rcl& r = rcls_[ri];
+    const FlowLayerPlan& pl = plan[ri];
     const View x0{zp_ + (long)r.in_off * Fs, (long)C_ * Fs, Fs};
     const View x1{zp_ + (long)r.out_off * Fs, (long)C_ * Fs, Fs};
-    const bool compose_pre = compose_pre_of(ri);
-    if (!(chain && ri > 0) && !compose_pre) {                                     // else: written by the previous layer's chain, or not at all
-      if (!(chain && r.pre4pad && conv1x1_col4(nullptr, r.pre.bias, r.pre.rows, x0, fh, lens_b_, B, Fmax, 2.0 * fsum * r.pre.macs_per_col,
-                                               nullptr, 0, r.pre4pad, half, LaunchPolicy::col4_max_frames)))
-        conv(r.pre, x0, fh, lens_b_, 1, Fmax, EPI_STORE);
-    }
+    if (pl.pre_launch &&
+        !(pl.pre_col4 && conv1x1_col4(nullptr, r.pre.bias, r.pre.rows, x0, fh, lens_b_, B, Fmax, 2.0 * fsum * r.pre.macs_per_col,
+                                      nullptr, 0, r.pre4pad, C_ / 2, LaunchPolicy::col4_max_frames)))
+      conv(r.pre, x0, fh, lens_b_, 1, Fmax, EPI_STORE);
     const int nl = (int)r.in.size();
-    const bool rs_front = rs_front_of(ri), compose_post = compose_post_of(ri);
     for (int i = 0; i < nl; ++i) {
       const float* b2 = nspk_ > 1 ? cond_ + cond_off_wn_[ri] + (long)i * 2 * H_ : nullptr;
-      if (compose_pre && i == 0) gate_pre(r, x0, facts, lens_b_, Fmax, fsum, b2);
+      if (pl.compose_pre && i == 0) gate_pre(r, x0, facts, lens_b_, Fmax, fsum, b2);
       else conv(r.in[i], fh, facts, lens_b_, 1, Fmax, EPI_GATE, {.bias2 = b2, .bias2_bs = cond_bs_});
-      if (rs_front && i == nl - 1) {
-        fl += 2.0 * fsum * (r.in[i].macs_per_col + r.rs[i].macs_per_col);
-        continue;
-      }
-      if (r.rs4[i] && pol_.chain4_frames((long)B * Fmax) && H_ == 192 && r.rs[i].rows <= 2 * H_) {
-        // small calls: the res/skip 1x1 conv on 4-column workgroups (colchain4_kernel mode 2), one part per 192 rows
-        ColP cp{};
-        cp.in1 = facts.p; cp.in1_bs = facts.bs; cp.in1_cs = facts.cs; cp.K1 = H_;
-        cp.w1 = r.rs4[i]; cp.b1 = r.rs[i].bias; cp.rows1 = r.rs[i].rows;
-        if (compose_post) {      // the skip rows: post . skip_i, 96 of them
-          cp.w1 = r.rsp4[i]; cp.b1 = r.rsp_bias[i]; cp.rows1 = r.rs[i].rows - H_ + half;
-        }
-        cp.mode = 2; cp.first = i == 0 ? 1 : 0;
-        cp.xcd = xcd_period_;
-        cp.x1 = fh.p; cp.x1_bs = fh.bs; cp.x1_cs = fh.cs;
-        cp.out = fskip.p; cp.out_bs = fskip.bs; cp.out_cs = fskip.cs;
-        cp.lens = lens_b_;
-        const bool hpre = compose_pre && i == 0;      // the res part also adds pre(x0): x1 = the whole hidden state, not read
-        if (hpre) {
-          cp.in0 = x0.p; cp.in0_bs = x0.bs; cp.in0_cs = x0.cs;
-          cp.w2 = w4_of(r.pre16); cp.b2 = r.pre.bias; cp.rows2 = H_;
-        }
-        const int kh4 = kbegin(prof_level_ >= 2 ? krow("colchain4_kernel<false>") : 0,
-                               2.0 * fsum * ((double)cp.rows1 * H_ + (hpre ? r.pre.macs_per_col : 0)),
-                               4.0 * (fsum * (H_ + 2.0 * cp.rows1) + (double)cp.rows1 * H_ + (hpre ? half * (fsum + H_) : 0)));
-        launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem() + (hpre ? 4 * (96 + 4) * sizeof(float) : 0), stream_, cp);
-        kend(kh4);
-      } else {
-        conv(r.rs[i], facts, fh, lens_b_, 1, Fmax, EPI_WNRS, {.out2 = fskip, .mode = i == 0 ? 1 : 0});
-      }
       fl += 2.0 * fsum * (r.in[i].macs_per_col + r.rs[i].macs_per_col);
+      if (pl.rs_front && i == nl - 1) continue;      // (its res/skip conv rides in front of the chain launch)
+      if (pl.rs_col4[i]) wn_res_skip4(r, i, pl, x0, facts, fh, fskip, B, Fmax, fsum);
+      else conv(r.rs[i], facts, fh, lens_b_, 1, Fmax, EPI_WNRS, {.out2 = fskip, .mode = i == 0 ? 1 : 0});
     }
-    if (chain) {
-      // post + "x1 -= m" + the next coupling layer's pre over the updated half, one launch
-      ColP cp{};
-      cp.in1 = fskip.p; cp.in1_bs = fskip.bs; cp.in1_cs = fskip.cs; cp.K1 = H_;
-      cp.w1 = r.post16; cp.b1 = r.post.bias; cp.rows1 = half;
-      cp.mode = 1;
-      cp.x1 = x1.p; cp.x1_bs = x1.bs; cp.x1_cs = x1.cs;
-      if (ri + 1 < rcls_.size() && !compose_pre_of(ri + 1)) {      // (composed: the next layer's gate conv reads x0 itself)
-        const Rcl& nx = rcls_[ri + 1];
-        if (nx.in_off != r.out_off) throw std::runtime_error("coupling layers do not alternate halves");
-        cp.w2 = nx.pre16; cp.b2 = nx.pre.bias; cp.rows2 = H_;
-        cp.out2 = fh.p; cp.o2_bs = fh.bs; cp.o2_cs = fh.cs;
-      }
-      cp.lens = lens_b_;
-      if (rs_front) {
-        cp.in0 = facts.p; cp.in0_bs = facts.bs; cp.in0_cs = facts.cs;
-        cp.w0 = r.rs4[nl - 1]; cp.b0 = r.rs[nl - 1].bias; cp.first = nl == 1 ? 1 : 0;
-      }
-      if (compose_post) {        // the skip sum is m: no post GEMM
-        cp.K1 = half; cp.w1 = nullptr; cp.b1 = nullptr;
-        if (rs_front) { cp.w0 = r.rsp4[nl - 1]; cp.b0 = r.rsp_bias[nl - 1]; }
-      }
-      colchain(cp, B, Fmax, 2.0 * fsum * ((compose_post ? 0 : r.post.macs_per_col) + (cp.w2 ? rcls_[ri + 1].pre.macs_per_col : 0) +
-                                          (rs_front ? (compose_post ? (double)half * H_ : r.rs[nl - 1].macs_per_col) : 0)));
-    } else {
-      conv(r.post, fskip, x1, lens_b_, 1, Fmax, EPI_SUBFROM);
-    }
+    if (pl.chain) coupling_chain(r, ri + 1 < rcls_.size() ? &rcls_[ri + 1] : nullptr, pl, x1, facts, fskip, fh, B, Fmax, fsum);
+    else conv(r.post, fskip, x1, lens_b_, 1, Fmax, EPI_SUBFROM);
     fl += 2.0 * fsum * (r.pre.macs_per_col + r.post.macs_per_col);
   }
   prof_end(2, fl);

@@ -175,6 +175,35 @@ Engine::StageSchedule Engine::stage_schedule(const UpStage& st, int Lmax, double
   return {grp ? STAGE_GROUP_SPLITK : (grp_t ? STAGE_GROUP_TILED : STAGE_CHAIN), tiled};
 }
 
+// Where the coupling flow's route is decided: what the weights allow was settled at pack time (Rcl's *_ok flags), the policy
+// answers for the knobs and the call's size, this function asks once per call.
+// Small calls: the LAST WN layer's res/skip conv (skip rows only) rides in front of the post + pre chain launch. Where the
+// chain is 4 columns wide and the gate conv runs on gate4_kernel, pre is composed into the first gate conv (gate4pre_kernel
+// reads x0; nobody computes h = pre(x0) in front of the WN -- the first res/skip launch writes h + res_0 in one piece), and
+// post into the skip convs (engine_pack.cpp pack_post4): every WN layer adds post . skip_j, 96 rows, into the first 96 rows
+// of the skip sum -- s_0 = M_0 a_0 + c_0, s_j = (M_j a_j + c_j) + s_{j-1} -- and the chain launch has no post GEMM:
+// x1 <- x1 - s_{nl-1}. The compositions ask chain4_frames, not chain_rs_front: PIPER_HIP_CHAIN_RS=0 only moves the last
+// res/skip conv, one launch per coupling layer, and leaves pre and post composed. Post is composed on pre's route only (the
+// knob changes nothing where gate4_kernel does not run).
+std::vector<FlowLayerPlan> Engine::plan_flow(int B, int Fmax, double fsum) const {
+  const bool chain = pol_.chain16(fsum, true, H_, C_ / 2), col4 = pol_.chain4_frames((long)B * Fmax);
+  std::vector<FlowLayerPlan> plan(rcls_.size());
+  for (size_t ri = 0; ri < rcls_.size(); ++ri) {
+    const Rcl& r = rcls_[ri];
+    FlowLayerPlan& p = plan[ri];
+    p.chain = chain;
+    p.rs_front = chain && r.front4_ok && pol_.chain_rs_front((long)B * Fmax);
+    const bool compose = chain && r.front4_ok && col4 && r.compose_pre_ok && plan_conv(r.in[0], Fmax, EPI_GATE, stage_tiled_).form == CONV_GATE12;
+    p.compose_pre = pol_.compose_pre() && compose;
+    p.compose_post = pol_.compose_post() && compose && r.compose_post_ok;
+    p.pre_launch = !(chain && ri > 0) && !p.compose_pre;
+    p.pre_col4 = p.pre_launch && chain && r.pre4pad && H_ == 192 && col4;
+    if (ri > 0) plan[ri - 1].chain_has_next_pre = !p.compose_pre;
+    for (size_t i = 0; i < r.rs.size(); ++i) p.rs_col4.push_back(r.rs4[i] && col4 && H_ == 192 && r.rs[i].rows <= 2 * H_);
+  }
+  return plan;
+}
+
 void Engine::group_begin(bool tiled) {
   grouping_ = true;
   group_tiled_ = tiled;
@@ -607,14 +636,79 @@ bool Engine::conv1x1_col4(const float* w16, const float* bias, int rows, View in
   return true;
 }
 
+// conv_o + residual + norm_layers_1 of an encoder layer in one launch (mode 0: the 192 x 192 GEMM fits one workgroup per
+// 16 columns, or per 4 on small calls); x is the residual and the output
+void Engine::conv_o_ln(const EncLayer& e, View att, View x, int B, int T, double tsum) {
+  ColP cp{};
+  cp.in1 = att.p; cp.in1_bs = att.bs; cp.in1_cs = att.cs; cp.K1 = H_;
+  cp.w1 = e.o16; cp.b1 = e.o.bias; cp.rows1 = H_; cp.mode = 0;
+  cp.res = x.p; cp.res_bs = x.bs; cp.res_cs = x.cs;
+  cp.gamma = e.g1; cp.beta = e.b1;
+  cp.out = x.p; cp.out_bs = x.bs; cp.out_cs = x.cs;
+  cp.lens = d_tlens_;
+  colchain(cp, B, T, 2.0 * tsum * e.o.macs_per_col);
+}
+
+// Small calls: the res/skip 1x1 conv of WN layer `layer` on 4-column workgroups (colchain4_kernel mode 2), one part per 192
+// rows: fh += res rows, fskip (+)= skip rows. Post composed: the skip rows are post . skip_i, 96 of them. Pre composed, first
+// layer: the res part also adds pre(x0) -- fh is written as the whole hidden state, not read.
+void Engine::wn_res_skip4(const Rcl& r, int layer, const FlowLayerPlan& pl, View x0, View facts, View fh, View fskip, int B, int Fmax, double fsum) {
+  const int half = C_ / 2;
+  ColP cp{};
+  cp.in1 = facts.p; cp.in1_bs = facts.bs; cp.in1_cs = facts.cs; cp.K1 = H_;
+  cp.w1 = r.rs4[layer]; cp.b1 = r.rs[layer].bias; cp.rows1 = r.rs[layer].rows;
+  if (pl.compose_post) { cp.w1 = r.rsp4[layer]; cp.b1 = r.rsp_bias[layer]; cp.rows1 = r.rs[layer].rows - H_ + half; }
+  cp.mode = 2; cp.first = layer == 0 ? 1 : 0;
+  cp.xcd = xcd_period_;
+  cp.x1 = fh.p; cp.x1_bs = fh.bs; cp.x1_cs = fh.cs;
+  cp.out = fskip.p; cp.out_bs = fskip.bs; cp.out_cs = fskip.cs;
+  cp.lens = lens_b_;
+  const bool hpre = pl.compose_pre && layer == 0;
+  if (hpre) { cp.in0 = x0.p; cp.in0_bs = x0.bs; cp.in0_cs = x0.cs; cp.w2 = w4_of(r.pre16); cp.b2 = r.pre.bias; cp.rows2 = H_; }
+  const int kh4 = kbegin(prof_level_ >= 2 ? krow("colchain4_kernel<false>") : 0,
+                         2.0 * fsum * ((double)cp.rows1 * H_ + (hpre ? r.pre.macs_per_col : 0)),
+                         4.0 * (fsum * (H_ + 2.0 * cp.rows1) + (double)cp.rows1 * H_ + (hpre ? half * (fsum + H_) : 0)));
+  launch::colchain4(dim3((Fmax + 3) / 4, B, (cp.rows1 + 191) / 192), col4_smem(hpre), stream_, cp);
+  kend(kh4);
+}
+
+// post + "x1 -= m" + the next coupling layer's pre over the updated half, one launch (mode 1). rs_front: the last WN layer's
+// res/skip conv (skip rows only) runs in front, from facts. Post composed: the skip sum is m -- no post GEMM, K1 = half and
+// a null w1 tell the kernel so. Pre of the next layer composed: its gate conv reads x0 itself, no second GEMM here.
+void Engine::coupling_chain(const Rcl& r, const Rcl* next, const FlowLayerPlan& pl, View x1, View facts, View fskip, View fh, int B, int Fmax, double fsum) {
+  const int half = C_ / 2, nl = (int)r.in.size();
+  ColP cp{};
+  cp.in1 = fskip.p; cp.in1_bs = fskip.bs; cp.in1_cs = fskip.cs; cp.K1 = H_;
+  cp.w1 = r.post16; cp.b1 = r.post.bias; cp.rows1 = half; cp.mode = 1;
+  cp.x1 = x1.p; cp.x1_bs = x1.bs; cp.x1_cs = x1.cs;
+  if (pl.chain_has_next_pre) {
+    if (next->in_off != r.out_off) throw std::runtime_error("coupling layers do not alternate halves");
+    cp.w2 = next->pre16; cp.b2 = next->pre.bias; cp.rows2 = H_;
+    cp.out2 = fh.p; cp.o2_bs = fh.bs; cp.o2_cs = fh.cs;
+  }
+  cp.lens = lens_b_;
+  if (pl.rs_front) {
+    cp.in0 = facts.p; cp.in0_bs = facts.bs; cp.in0_cs = facts.cs;
+    cp.w0 = r.rs4[nl - 1]; cp.b0 = r.rs[nl - 1].bias; cp.first = nl == 1 ? 1 : 0;
+  }
+  if (pl.compose_post) { cp.K1 = half; cp.w1 = nullptr; cp.b1 = nullptr; }
+  if (pl.compose_post && pl.rs_front) { cp.w0 = r.rsp4[nl - 1]; cp.b0 = r.rsp_bias[nl - 1]; }
+  colchain(cp, B, Fmax, 2.0 * fsum * ((pl.compose_post ? 0 : r.post.macs_per_col) + (cp.w2 ? next->pre.macs_per_col : 0) +
+                                      (pl.rs_front ? (pl.compose_post ? (double)half * H_ : r.rs[nl - 1].macs_per_col) : 0)));
+}
+
+// Whether a chain launch takes its 4-column form (colchain4_kernel), per mode. Mode 0 runs on ids, mode 1 on frames: separate
+// column limits (profiles/r03_notes.md). Mode 1 without w1: post composed into the skip convs, in1 (96 rows) is m as it is.
+static bool conv_o_ln_col4(const LaunchPolicy& pol, const ColP& p, long cols) { return pol.chain4(cols) && p.w1 && p.K1 == 192 && p.rows1 == 192; }
+static bool coupling_chain_col4(const LaunchPolicy& pol, const ColP& p, long cols) { return pol.chain4_frames(cols) && p.K1 == (p.w1 ? 192 : 96) && p.rows1 == 96 && (!p.w2 || p.rows2 <= 192); }
+
+// Modes 0 and 1: 4 columns per workgroup on small calls whose matrices have their pack4 twins, else 16 (colchain_kernel).
 void Engine::colchain(const ColP& p, int B, int Lmax, double flops) {
   // algorithmic bytes: GEMM input, the residual / x1 read and written, the second GEMM's output; weights once
   const double cols = p.lens == d_tlens_ ? cols_ids_ : cols_frames_;
-  // (w1 == null: post composed into the skip convs, kernels/col4.h -- no first GEMM, in1 is subtracted as it is)
   const double kbytes = 4.0 * (cols * (p.K1 + 2.0 * p.rows1 + (p.w2 ? p.rows2 : 0)) + (p.w1 ? (double)p.rows1 * p.K1 : 0.0) +
                                (p.w2 ? (double)p.rows2 * p.rows1 : 0.0));
-  // mode 1 runs on frames (coupling post + pre), mode 0 on ids: separate column limits (profiles/r03_notes.md)
-  if ((p.mode == 1 ? pol_.chain4_frames((long)B * Lmax) : pol_.chain4((long)B * Lmax)) && p.K1 == (p.w1 ? 192 : 96) && (p.mode == 0 ? p.w1 && p.rows1 == 192 : (p.rows1 == 96 && (!p.w2 || p.rows2 <= 192)))) {
+  if (p.mode == 0 ? conv_o_ln_col4(pol_, p, (long)B * Lmax) : coupling_chain_col4(pol_, p, (long)B * Lmax)) {
     const float* w1 = p.w1 ? w4_of(p.w1) : nullptr;
     const float* w2 = p.w2 ? w4_of(p.w2) : nullptr;
     if ((w1 || !p.w1) && (!p.w2 || w2)) {

@@ -648,6 +648,16 @@ void Engine::init(const WeightSet& ws) {
       }
     }
     if (flips & 1) throw std::runtime_error("odd number of flow layers is not supported");
+    // what the packed weights allow of the one-utterance routes (Engine::plan_flow adds the policy and the call's size)
+    for (size_t ri = 0; ri < rcls_.size(); ++ri) {
+      Rcl& r = rcls_[ri];
+      const Rcl* nx = ri + 1 < rcls_.size() ? &rcls_[ri + 1] : nullptr;
+      r.front4_ok = wnl >= 1 && r.rs4[wnl - 1] && r.rs[wnl - 1].rows == H_ && H_ == 192 && half == 96 && w4_of(r.post16) &&
+                    (!nx || (nx->pre.rows <= 192 && w4_of(nx->pre16)));
+      r.compose_pre_ok = wnl >= 2 && r.gpre4 && r.rs4[0] && r.rs[0].rows == 2 * H_ && w4_of(r.pre16) && r.pre.rows == H_;
+      r.compose_post_ok = r.rsp4.size() == r.in.size();
+      for (size_t j = 0; j < r.rsp4.size(); ++j) r.compose_post_ok = r.compose_post_ok && r.rsp4[j] && r.rsp_bias[j];
+    }
   }
 
   // ---- HiFiGAN

@@ -12,8 +12,9 @@ read once per process), and writes per case under OUT/<case>/
 
 Plan-only cases (EMU_PLAN_ONLY=1, EMU_PLAN_FRAMES set) take the full-size voices: presets medium and high, batch 1..64,
 16..500 ids, 60..1200 frames per utterance, the four matrix modes, every routing knob changed one at a time, and one
-chunk of each stream kind. Executing cases run the tiny voices through the same knobs and stream kinds. Every case makes
-two consecutive calls. Run it on two checkouts (--root: the tree whose package and emulator library are used) and
+chunk of each stream kind. Executing cases run the tiny voices through the same knobs and stream kinds; two of them have
+the 192 channels of the full-size voices (the coupling flow's 4-column route: Engine::plan_flow) and also run at forced
+frame counts that are no multiples of 4, under every setting of the flow's own knobs. Every case makes two consecutive calls. Run it on two checkouts (--root: the tree whose package and emulator library are used) and
 `diff -r` the two output trees; the last line printed is a JSON summary with a sha256 over the tree
 (profiles/launch_plan.md)."""
 import argparse
@@ -27,7 +28,17 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOBS = (("SPLITK_MAX", 0), ("SPLITK16", 0), ("SPLITK16", 3), ("WIDE_SPLITK", 0), ("WIDE_SPLITK", 2), ("GATE4", 0),
          ("GATE4", 2), ("GATE_HALF", 0), ("CONV1X1", 0), ("GROUP_MRF", 0), ("GROUP_MRF", 2), ("GROUP_TILED", 0),
-         ("GROUP_MAXB", 0), ("MRF", 0), ("MRF", 2), ("MRF_TAIL", 0), ("TPB", 3), ("PROF_SITES", 1))
+         ("GROUP_MAXB", 0), ("MRF", 0), ("MRF", 2), ("MRF_TAIL", 0), ("TPB", 3), ("PROF_SITES", 1),
+         # the coupling flow's route (Engine::plan_flow)
+         ("COLCHAIN", 0), ("COLCHAIN", 2), ("COL4", 0), ("COL4", 2), ("CHAIN_RS", 0), ("STACK_PRE", 0),
+         ("WN_COMPOSE", 0), ("WN_COMPOSE", 2), ("WN_COMPOSE", 3), ("WN_COMPOSE", 4))
+KNOB_PAIRS = ((("WN_COMPOSE", 1), ("CHAIN_RS", 0)), (("WN_COMPOSE", 4), ("GATE4", 0)))
+# tiny with the 192 channels of medium / high (tests/one_utterance_truth_case.py: tiny192; tests/test_wn_compose_emu.py: its
+# multi-speaker variant): the executing voices on which the 4-column flow route runs
+WIDE = {"tiny192": dict(hidden=192, inter=192, filter=96, n_layers=2)}
+WIDE["tiny192-ms"] = dict(WIDE["tiny192"], n_speakers=4, gin=16)
+# forced frame counts that are no multiples of 4 (ragged 4-column tiles): one utterance, and two
+FORCED = ((13,), (3, 13))
 MATRIX = ("f32", "bf16x3", "f16x3", "bf16x6")
 STREAMS = ("stream", "stream_batch", "pool")
 SCALES = (0.667, 1.0, 0.8)
@@ -37,9 +48,13 @@ def cases():
     out = []
 
     def add(name, preset, **kw):
-        c = dict(name=name, preset=preset, B=1, ids=128, frames=None, matrix="f32", env={}, kind="call")
+        c = dict(name=name, preset=preset, B=1, ids=128, frames=None, matrix="f32", env={}, kind="call", forced=None)
         c.update(kw)
         out.append(c)
+
+    knobs = [(kv,) for kv in KNOBS] + list(KNOB_PAIRS)
+    tag = lambda kvs: "_".join(f"{k}{v}" for k, v in kvs)
+    env = lambda kvs: {"PIPER_HIP_" + k: str(v) for k, v in kvs}
 
     for preset in ("medium", "high"):
         for B in (1, 2, 4, 16, 64):
@@ -51,20 +66,25 @@ def cases():
         for m in MATRIX[1:]:
             for B, frames in ((1, 417), (2, 417), (16, 417), (1, 1200), (64, 60)):
                 add(f"plan/{preset}/{m}_b{B}_f{frames}", preset, B=B, frames=frames, matrix=m)
-        for k, v in KNOBS:
+        for kvs in knobs:
             for B, ids in ((1, 128), (1, 16), (2, 64), (16, 128)):
-                add(f"plan/{preset}/{k}{v}_b{B}_i{ids}", preset, B=B, ids=ids, frames=417, env={"PIPER_HIP_" + k: str(v)})
+                add(f"plan/{preset}/{tag(kvs)}_b{B}_i{ids}", preset, B=B, ids=ids, frames=417, env=env(kvs))
     for kind in STREAMS:
         add(f"plan/medium/{kind}", "medium", B=1 if kind == "stream" else 4, frames=417, kind=kind)
-    for preset in ("tiny", "tiny-high", "tiny-ms"):
+    for preset in ("tiny", "tiny-high", "tiny-ms", "tiny192", "tiny192-ms"):
         add(f"exec/{preset}/b1", preset, ids=21)
         add(f"exec/{preset}/b3", preset, B=3, ids=21)
         for m in MATRIX[1:]:
             add(f"exec/{preset}/{m}", preset, ids=21, matrix=m)
-        for k, v in KNOBS:
-            add(f"exec/{preset}/{k}{v}", preset, ids=21, env={"PIPER_HIP_" + k: str(v)})
+        for kvs in knobs:
+            add(f"exec/{preset}/{tag(kvs)}", preset, ids=21, env=env(kvs))
         for kind in STREAMS:
             add(f"exec/{preset}/{kind}", preset, B=1 if kind == "stream" else 3, ids=21, kind=kind)
+    for preset in ("tiny192", "tiny192-ms"):
+        for forced in FORCED:
+            for kvs in [()] + [kvs for kvs in knobs if kvs[0][0] in ("CHAIN_RS", "WN_COMPOSE")]:
+                add(f"exec/{preset}/frames{'_'.join(map(str, forced))}{'_' if kvs else ''}{tag(kvs)}", preset, B=len(forced),
+                    forced=forced, env=env(kvs))
     return out
 
 
@@ -73,8 +93,8 @@ def run_case(case, out, root):
     sys.path.insert(0, root)
     import numpy as np
     from piper_amd import _lib as L, weights as W
-    from piper_amd.engine import Engine
-    cfg = W.preset(case["preset"])
+    from piper_amd.engine import Engine, Timing
+    cfg = W.preset("tiny", **WIDE[case["preset"]]) if case["preset"] in WIDE else W.preset(case["preset"])
     eng = Engine(blob=W.pack_blob(cfg, W.synthetic_weights(cfg, 1234)), lib=L.bind(os.path.join(root, "tests", "emu", "libpiper_hip_emu.so")))
     eng.set_seed(77)
     eng.profile_enable(2)
@@ -82,6 +102,10 @@ def run_case(case, out, root):
     # ragged batches: utterance i has ids - 3 * (i % 4) ids
     ids = [W.synthetic_phoneme_ids(max(4, case["ids"] - 3 * (i % 4)), i, id_max=cfg.n_vocab - 1) for i in range(B)]
     sids = [i % cfg.n_speakers for i in range(B)] if cfg.n_speakers > 1 else None
+    timing = None
+    if case["forced"]:      # exactly F frames per utterance, through the timing plan: two ids (one frame, the rest)
+        timing = Timing(durations=[[1, F - 1] for F in case["forced"]])
+        ids = [s[:2] for s in ids]
     launches, audio, pcm, durs = [], [], [], []
 
     def keep(a, p):
@@ -90,7 +114,7 @@ def run_case(case, out, root):
             pcm.append(np.asarray(p, np.int16).ravel())
 
     if case["kind"] == "call":
-        eng.upload(ids, SCALES, sids=sids)
+        eng.upload(ids, SCALES, sids=sids, timing=timing)
         for _ in range(2):
             eng.run()
             launches.append(eng.run_launches)
