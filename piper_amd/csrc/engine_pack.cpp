@@ -262,8 +262,9 @@ PackedConv Engine::pack_qkv(const WeightSet& ws, const std::string& prefix, floa
 PackedConv Engine::pack_convT(const WeightSet& ws, const std::string& prefix, int stride) {
   const HostTensor& w = ws.get(prefix + ".weight");
   const int Ci = (int)w.dims[0], Co = (int)w.dims[1], K = (int)w.dims[2];
-  if (K != 2 * stride || ((K - stride) & 1))
-    throw std::runtime_error(prefix + ": ConvTranspose1d with kernel != 2*stride is not supported");
+  if (K != 2 * stride) throw std::runtime_error(prefix + ": ConvTranspose1d with kernel != 2*stride is not supported");
+  // padding (K - stride) / 2 = stride / 2 is exact only for an even stride: an odd one makes stride * L + 1 samples
+  if (stride & 1) throw std::runtime_error(prefix + ": ConvTranspose1d with an odd stride is not supported (kernel - stride must be even)");
   const int rows = Co * stride;
   std::vector<float> W(skeleton_ ? 0 : (size_t)rows * Ci * 2);
   for (int co = 0; co < (skeleton_ ? 0 : Co); ++co)

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void dds_layer4_kernel(const int* lens, const 
 #pragma unroll
       for (int kk = 0; kk < MAXK; ++kk) a = fmaf(ww[k][kk], xv[k][kk], a);
       v[k] = a;
-      xc[k] = xv[k][(MAXK - 1) / 2];     // centre tap = x[c][t] (odd kernel, "same" padding)
+      xc[k] = p.dw_k > 1 ? xv[k][1] : xv[k][0];     // centre tap (dw_k - 1) / 2 = x[c][t] (dw_k 1 or 3, "same" padding)
     }
   }
   float s = 0.f;
