@@ -383,6 +383,53 @@ int pe_get_stream_gain(pe_engine* e, int32_t* mode, float* peak, int32_t* ramp_s
  * afterwards. */
 int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacity, int32_t* n);
 
+/* Streams at a target loudness: a fourth stream level, PE_GAIN_LOUDNESS. A stream cannot know its final integrated loudness
+ * before it ends, but the gated loudness of what it has delivered SO FAR is known after every chunk -- the figure a live
+ * loudness meter shows -- and equals the final value once the last chunk has passed. Each stream carries that running
+ * measure on the device and every chunk's gain follows it toward target_lufs under a peak ceiling, with no host round trip
+ * (DESIGN.md section 4.9). One stream as above; x_k[0 .. n_k) the floats chunk k delivers, N_k = n_0 + .. + n_k, fs the
+ * delivered rate.
+ *   L_k        the integrated loudness pe_set_loudness defines (below), of the prefix X[0 .. N_k): the K-weighting runs from
+ *              zero state at stream sample 0 THROUGH the chunk boundaries, segments and blocks lie on stream sample indices,
+ *              both gates are re-evaluated over all blocks complete so far; PE_LOUD_SHORT while N_k < 4 h,
+ *              PE_LOUD_UNMEASURABLE where nothing passes the absolute gate. L of the last chunk is that of the whole of X.
+ *   state      running sample peak r (0 at begin / join), previous end-of-chunk gain G, the last loudness used.
+ *   a chunk with n_k > 0:
+ *              r' = max(r, max |x_k|). Lu = L_k if measurable and not (SHORT with a prior set), else prior_lufs if set
+ *              (PE_LOUD_PRIOR), else the stream's last Lu, else none. a = 10^((target_lufs - Lu) / 20) in f64, 1 when there
+ *              is none: a stream that is still silent is delivered as generated. cap = (float)(32767 C / r'),
+ *              C = 10^(ceiling_db / 20), one ulp less where the rounding would lift r' over the ceiling; +inf when r' = 0.
+ *              g1 = min((float)(32767 a), cap), PE_LOUD_LIMITED when the cap is the smaller. g0 = g1 on the stream's first
+ *              delivered chunk, else min(G, cap). With R = min(ramp_samples, n_k), sample i < R is scaled by
+ *              fma(g0 - g1, (R - 1 - i) / R, g1), every later one by g1; clamp and truncation as before. Then r = r', G = g1.
+ *   n_k == 0   moves nothing.
+ * Unlike PE_GAIN_RUNNING the gain may rise as well as fall, and g0 is cut to the cap: |pcm| <= floor(32767 C) outside ramps
+ * and <= floor(32767 C) + 1 inside them. Not covered on streams: the true-peak ceiling, the look-ahead limiter, a slew limit
+ * beyond the ramp, stereo. target_lufs in [-40, -5], ceiling_db in [-20, 0], prior_lufs finite in [-70, 0] or NaN for none,
+ * ramp_samples 0 .. 65536. Errors that change nothing, each naming the value: a value out of range or not finite, an unknown
+ * delivered rate (a voice without a header rate: pe_set_output_rate(native, ...) first), and any call while a stream, a batch
+ * stream or a pool slot is live / occupied. All four numbers are data the kernels read in place: new values replay the
+ * captured graphs; the mode is part of the graph keys, and all four modes' graphs stay cached side by side.
+ * pe_set_stream_gain with one of the other modes leaves this one; pe_get_stream_gain reports mode 3 while it is set.
+ * pe_get_stream_loudness reads the setting back (*on: the mode is set; any pointer may be NULL). */
+enum { PE_GAIN_LOUDNESS = 3 };
+enum { PE_LOUD_PRIOR = 16 };
+int pe_set_stream_loudness(pe_engine* e, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples);
+int pe_get_stream_loudness(pe_engine* e, int32_t* on, float* target_lufs, float* ceiling_db, float* prior_lufs, int32_t* ramp_samples);
+/* The last chunk call on the handle in that mode: *n rows; lufs[r] = the running loudness L_k of row r (-inf: not measurable),
+ * gain[r] = g1, peak[r] = r', flags[r] = PE_LOUD_* bits. A row that delivered nothing in the call reports the state its
+ * stream's last chunk left -- a finished row keeps its end state -- and {-inf, 0, 0, SHORT | UNMEASURABLE} while its stream
+ * has delivered nothing yet. pe_stream_last_gains reports the same g1 and r'. Any array may be NULL; capacity < *n is an error. */
+int pe_stream_last_loudness(pe_engine* e, float* lufs, float* gain, float* peak, int32_t* flags, int64_t capacity, int32_t* n);
+/* Test hook, the counterpart of pe_debug_loudness: the production kernels of the mode chunk after chunk on caller-supplied
+ * rows x[batch][stride] (host) at rate fs (8000 .. 48000). chunks[n_chunks][batch]: chunk k of row b holds the row's next
+ * chunks[k][b] samples (0 allowed; a row's sum <= stride). Out, [n_chunks][batch] each: lufs, g0, g1, flags as reported after
+ * that chunk; pcm[batch][stride]: the int16 of every chunk at its place in the row (what no chunk covers is left alone).
+ * Independent of the handle's setting and rate. */
+int pe_debug_stream_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
+                             int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
+                             float* lufs, float* g0, float* g1, int32_t* flags, int16_t* pcm);
+
 /* Target loudness of whole utterances. By default every utterance of pe_synthesize*, pe_fetch, the groups and the coalescer
  * is scaled by 32767 / max(0.01, its peak) (the reference's rule, piper.cpp:410-431): the PEAK is fixed, the level is not, and a
  * nearly empty phrase is amplified by up to 100. With on != 0 every whole-utterance call delivers its int16 PCM at a target
@@ -401,8 +448,8 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
  *              utterance; products are clamped to [-32768, 32767] and truncated.
  * The ceiling holds the sample peak by default and the true peak after the call below. The measurement is mono and covers whole
  * utterances only: pe_stream_next, pe_stream_next_batch and pe_stream_pool_next keep their chunk rule and the
- * pe_set_stream_gain modes -- an integrated loudness is not known before an utterance ends -- and the setting may change
- * while a stream is live. target_lufs in [-40, -5], ceiling_db in [-20, 0], both finite (on == 0: ignored); a voice without
+ * pe_set_stream_gain modes -- a stream follows a RUNNING loudness instead, pe_set_stream_loudness above -- and the setting may
+ * change while a stream is live. target_lufs in [-40, -5], ceiling_db in [-20, 0], both finite (on == 0: ignored); a voice without
  * a header rate needs pe_set_output_rate(native, ...) first. A refused call names the value and changes nothing. target and
  * ceiling are data the kernels read in place: new values replay the captured graphs; on / off is part of the graph keys.
  * With on == 0 -- the default -- every launch, graph and bit of output is what it is without this call. One setting per

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <deque>
+#include <limits>
 #include <list>
 #include <map>
 #include <string>
@@ -239,6 +240,22 @@ class Engine {
   int stream_gain_mode() const { return gain_mode_; }
   float stream_gain_peak() const { return gain_peak_; }
   int stream_gain_ramp() const { return gain_ramp_; }
+  // Streams at a target loudness (mode GAIN_LOUDNESS): a running BS.1770-4 loudness per stream sets every
+  // chunk's gain toward target_lufs under the peak ceiling; prior_lufs NaN: none. Refused, with nothing changed, for values
+  // out of range, an unknown delivered rate, or while a stream is live / a pool slot occupied.
+  void set_stream_loudness(float target_lufs, float ceiling_db, float prior_lufs, int ramp_samples);
+  float stream_loudness_target() const { return sl_T_; }
+  float stream_loudness_ceiling() const { return sl_cdb_; }
+  float stream_loudness_prior() const { return sl_prior_; }
+  // the report of the last chunk call in that mode: per row the running loudness (-inf: not measurable), the gain at the
+  // chunk's end, the running peak and the flags; rows that delivered nothing report their stream's last state
+  int stream_last_loudness(float* lufs, float* gain, float* peak, int32_t* flags, int64_t capacity);
+  // test hook: the two stream loudness kernels and chunk_pcm_gain_kernel chunk after chunk on caller-given rows
+  // x[batch][stride] at rate fs; chunks[n_chunks][batch] = the chunk lengths (zeros allowed, a row's sum <= stride). Out per
+  // chunk and row lufs / g0 / g1 / flags [n_chunks][batch], and the int16 pcm[batch][stride].
+  void debug_stream_loudness(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                             float ceiling_db, float prior_lufs, int ramp_samples, float* lufs, float* g0, float* g1, int32_t* flags,
+                             int16_t* pcm);
   // end-of-chunk gain and the level it came from, per row of the last chunk call of any kind; returns the rows
   int stream_last_gains(float* gain, float* peak, int64_t capacity);
 
@@ -690,6 +707,10 @@ class Engine {
     int cap = 0;                                   // rows the blocks are sized for (even)
     PinBuf<int> host; DevBuf<int> dev;             // state blocks
     PinBuf<int> gctl; DevBuf<int> gdev;            // gain control (pinned) and gain state (device) blocks
+    // target loudness of streams (params.h: slc_*, sld_*): control (pinned), state, segment sums [cap][lnseg], tails
+    // [cap][2][lW]; allocated with the first chunk in that mode, they live and die with the blocks above
+    PinBuf<int> lctl; DevBuf<int> ldev; DevBuf<double> lseg; DevBuf<float> ltail;
+    int lnseg = 0, lW = 0;
     std::vector<char> gfirst;                      // per row: nothing delivered yet (its level starts afresh)
     std::vector<int32_t> pos;                      // frames delivered per row; its size is the number of rows
     std::vector<int64_t> off;                      // sample offsets of the current chunk
@@ -723,6 +744,25 @@ class Engine {
   // Default mode: the peaks stay on the device (`peaks`, one word per row) and are fetched when the report is asked for.
   void gain_collect(const int* ctl, int cap, int n, std::vector<char>& first, const int64_t* off, const unsigned* peaks);
   void gain_report_idle(const int* ctl, int cap, int n);   // a chunk call that ran nothing: stored state / zeros
+  // target loudness of streams: the setting, the filter block of the delivered rate sl_fs_ (h / W / R follow it), the
+  // one-utterance stream's state (its filter and conversion run on the host, f64 serial) and the last chunk call's report
+  float sl_T_ = -23.f, sl_cdb_ = -1.f, sl_prior_ = std::numeric_limits<float>::quiet_NaN();
+  int sl_fs_ = 0, sl_h_ = 0, sl_W_ = 0, sl_R_ = 0;
+  DevBuf<double> sl_coef_;
+  void sl_upload_filter(int fs);
+  // r's blocks for cap rows of streams of up to max_samples delivered samples, at the delivered rate (grown: graphs dropped)
+  void sl_ensure(ChunkRows& r, int cap, int64_t max_samples);
+  void sl_prepare(ChunkRows& r, int n);
+  SlP sl_params(const ChunkRows& r) const;
+  void issue_stream_loudness(const ChunkRows& r, int B, long max_n, bool rs);
+  void sl_collect(ChunkRows& r, int n, bool ran);
+  struct HostLoud {
+    double coef[10]; double z[4]; std::vector<double> seg; int64_t N = 0; int h = 1;
+    float r = 0.f, G = 0.f, lu = 0.f, L = 0.f; int flags = 0; bool first = true;
+  } s_sl_;
+  std::vector<float> lsl_lufs_;
+  std::vector<int32_t> lsl_flags_;
+  int lsl_n_ = -1;
   std::vector<float> lg_gain_, lg_peak_;
   std::vector<char> lg_got_;
   int lg_n_ = -1;                                          // rows of the last chunk call (-1: none yet)

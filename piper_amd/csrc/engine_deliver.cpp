@@ -116,6 +116,7 @@ void Engine::set_output_rate(int native, int output) {
   if (ld_on_) loud_check_rate(on ? output : native);    // (the target loudness is measured at the delivered rate)
   if (ld_on_ && ld_kind_ == PEAK_TRUE) tp_check_rate(on ? output : native);
   if (ld_on_ && lim_on_) check_limiter_window_at(lim_ms_, on ? output : native);
+  if (gain_mode_ == GAIN_LOUDNESS) loud_check_rate(on ? output : native);      // (so is a stream's running loudness)
   const std::string pair = std::to_string(native) + " -> " + std::to_string(output) + " Hz";
   int L = 1, M = 1, K = 0, Tp = 0, tile = RS_TILE;
   std::vector<float> table;
@@ -359,6 +360,15 @@ void Engine::loud_upload_filter(int fs) {
   ld_coef_.grow(LOUD_COEF_DOUBLES);
   PE_HIP(hipMemcpy(ld_coef_.get(), blk, sizeof(blk), hipMemcpyHostToDevice));
   ld_fs_ = fs; ld_h_ = h; ld_W_ = W; ld_R_ = R;
+}
+
+void Engine::sl_upload_filter(int fs) {
+  double blk[LOUD_COEF_DOUBLES];
+  int h, W, R;
+  loud_plan(fs, h, W, R, blk);
+  sl_coef_.grow(LOUD_COEF_DOUBLES);
+  PE_HIP(hipMemcpy(sl_coef_.get(), blk, sizeof(blk), hipMemcpyHostToDevice));
+  sl_fs_ = fs; sl_h_ = h; sl_W_ = W; sl_R_ = R;
 }
 
 void Engine::loud_write_ctl() {
@@ -904,6 +914,119 @@ void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int
       scale[b] = rf[ld_o_scale(cap) + b];
       flags[b] = ctl.get()[ldc_o_report(cap) + ld_o_flags(cap) + b];
     }
+  } catch (...) {
+    hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)
+    throw;
+  }
+}
+
+// The production kernels of a stream at a target loudness, chunk after chunk: the rows are windows of hop 1 that hold the
+// whole row, the chunk of row b its next chunks[k][b] samples; the peak word is the host's max |x| over the chunk.
+void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                                   float ceiling_db, float prior_lufs, int ramp_samples, float* lufs, float* g0, float* g1,
+                                   int32_t* flags, int16_t* pcm) {
+  EntryLock entry_lock;
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (!x || !chunks || !lufs || !g0 || !g1 || !flags || !pcm) throw std::runtime_error("null argument");
+  if (stride < 1 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [1, 2^28]");
+  if (n_chunks < 1 || n_chunks > 65536) throw std::runtime_error("n_chunks outside [1, 65536]");
+  if (fs < 8000 || fs > 48000) throw std::runtime_error("stream loudness hook: rate " + std::to_string(fs) + " Hz outside [8000, 48000]");
+  check_target(target);
+  check_ceiling(ceiling_db);
+  if (std::isinf(prior_lufs) || (prior_lufs == prior_lufs && (prior_lufs < -70.f || prior_lufs > 0.f)))
+    throw std::runtime_error("prior loudness " + std::to_string(prior_lufs) + " LUFS outside [-70, 0] (NaN: none)");
+  if (ramp_samples < 0 || ramp_samples > GAIN_MAX_RAMP) throw std::runtime_error("ramp_samples outside [0, " + std::to_string(GAIN_MAX_RAMP) + "]");
+  int maxc = 1;
+  for (int b = 0; b < batch; ++b) {
+    int64_t sum = 0;
+    for (int k = 0; k < n_chunks; ++k) {
+      const int c = chunks[(size_t)k * batch + b];
+      if (c < 0) throw std::runtime_error("row " + std::to_string(b) + ": negative chunk length");
+      sum += c;
+      maxc = std::max(maxc, c);
+    }
+    if (sum > stride) throw std::runtime_error("row " + std::to_string(b) + ": the chunks hold more than stride samples");
+  }
+  double blk[LOUD_COEF_DOUBLES];
+  int h, W, R;
+  loud_plan(fs, h, W, R, blk);
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const int cap = (batch + 1) & ~1, nseg_cap = (int)((stride + h - 1) / h) + 2;
+  const long xs = (long)((stride + 3) & ~(int64_t)3);
+  DevBuf<float> dx, dtail;
+  DevBuf<double> dcoef, dseg;
+  DevBuf<int> ddev, dgq;
+  PinBuf<int> ctl, st;
+  PinBuf<int16_t> hp;
+  try {
+    dx.grow((size_t)batch * xs);
+    dcoef.grow(LOUD_COEF_DOUBLES);
+    dseg.grow((size_t)cap * nseg_cap);
+    dtail.grow((size_t)cap * 2 * W);
+    ddev.grow((size_t)sld_words(cap));
+    dgq.grow((size_t)sgd_words(cap));
+    ctl.grow((size_t)slc_words(cap));
+    st.grow((size_t)sb_words(cap));
+    hp.grow((size_t)batch * stride);
+    ctl.zero();
+    st.zero();
+    memcpy(hp.get(), pcm, (size_t)batch * stride * sizeof(int16_t));      // (what no chunk covers comes back as the caller left it)
+    const float C = ceiling_ratio(ceiling_db);
+    memcpy(ctl.get(), &target, sizeof(float));
+    memcpy(ctl.get() + 1, &C, sizeof(float));
+    memcpy(ctl.get() + 2, &prior_lufs, sizeof(float));
+    ctl.get()[3] = ramp_samples;
+    rows_to_device(dx.get(), xs, x, batch, stride);
+    PE_HIP(hipMemcpyAsync(dcoef.get(), blk, sizeof(blk), hipMemcpyHostToDevice, stream_));
+    // (every word of the state a stream carries is poisoned: a row's first chunk must not read any of it)
+    PE_HIP(hipMemsetAsync(dseg.get(), 0xFF, dseg.bytes(), stream_));
+    PE_HIP(hipMemsetAsync(dtail.get(), 0xFF, dtail.bytes(), stream_));
+    PE_HIP(hipMemsetAsync(ddev.get(), 0xFF, ddev.bytes(), stream_));
+    PE_HIP(hipMemsetAsync(dgq.get(), 0, dgq.bytes(), stream_));
+    PE_HIP(hipStreamSynchronize(stream_));
+    SlP p{};
+    p.ctl = ctl.get(); p.dev = ddev.get(); p.cap = cap; p.coef = dcoef.get(); p.h = h; p.W = W; p.R = R;
+    p.seg = dseg.get(); p.nseg_cap = nseg_cap; p.tail = dtail.get();
+    SlChunkP q{};
+    q.x = dx.get(); q.x_bs = xs; q.st = st.get(); q.cap = cap; q.hop = 1;
+    int* s = st.get();
+    void* ptrs[2] = {hp.get(), nullptr};
+    memcpy(s + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
+    std::vector<int64_t> done((size_t)batch, 0);
+    std::vector<char> first((size_t)batch, 1);
+    const int nseg = (maxc + h - 1) / h + 1, steps = std::max(1, (maxc + CHUNK_SPB - 1) / CHUNK_SPB);
+    for (int k = 0; k < n_chunks; ++k) {
+      for (int b = 0; b < batch; ++b) {
+        const int c = chunks[(size_t)k * batch + b];
+        float m = 0.f;
+        for (int i = 0; i < c; ++i) m = std::max(m, std::fabs(x[(size_t)b * stride + done[b] + i]));
+        s[b] = 0;
+        s[sb_o_len(cap) + b] = (int)stride;
+        s[sb_o_first(cap) + b] = (int)done[b];
+        s[sb_o_count(cap) + b] = c;
+        reinterpret_cast<long long*>(s + sb_o_off(cap))[b] = (long long)b * stride + done[b];
+        memcpy(s + sb_o_peak(cap) + b, &m, sizeof(float));
+        ctl.get()[slc_o_first(cap) + b] = first[b];
+      }
+      launch::stream_loudness_seg(stream_, nseg, batch, p, q);
+      launch::stream_loudness_gain(stream_, batch, p, q, dgq.get());
+      launch::chunk_pcm_gain(dim3(steps, batch), stream_, dx.get(), xs, s, cap, 1, dgq.get());
+      PE_HIP(hipStreamSynchronize(stream_));
+      const float* cf = reinterpret_cast<const float*>(ctl.get());
+      for (int b = 0; b < batch; ++b) {
+        const size_t o = (size_t)k * batch + b;
+        const int c = chunks[o];
+        const bool none = first[b] && c == 0;            // (nothing delivered yet: the kernel wrote the empty report)
+        lufs[o] = cf[slc_o_lufs(cap) + b];
+        g0[o] = none ? 0.f : cf[slc_o_g0(cap) + b];
+        g1[o] = cf[slc_o_gain(cap) + b];
+        flags[o] = ctl.get()[slc_o_flags(cap) + b];
+        done[b] += c;
+        if (c > 0) first[b] = 0;
+      }
+    }
+    memcpy(pcm, hp.get(), (size_t)batch * stride * sizeof(int16_t));
   } catch (...) {
     hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)
     throw;

@@ -433,6 +433,8 @@ void Engine::issue_window_rows(const ChunkRows& r) {
     issue_resample(B, audio_, Ss_, rs_host_.get(), nullptr, max_out, (double)B * wg * hop_);
     const int rsteps = std::max(1, (int)((max_out + CHUNK_SPB - 1) / CHUNK_SPB));
     if (gm != GAIN_CHUNK) {
+      if (gm == GAIN_LOUDNESS) issue_stream_loudness(r, B, max_out, true);
+      else
       PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, rs_dev_.get(), rs_cap_, So_));
       PE_LAUNCH_KB("chunk_pcm_rs_gain_kernel", 10.0 * B * (double)max_out,
                    launch::chunk_pcm_rs_gain(dim3(rsteps, B), stream_, raudio_.get(), So_, rs_dev_.get(), rs_cap_, dst, cap, gdev));
@@ -447,12 +449,29 @@ void Engine::issue_window_rows(const ChunkRows& r) {
   if (gm != GAIN_FIXED)
     PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
   if (gm != GAIN_CHUNK) {
+    if (gm == GAIN_LOUDNESS) issue_stream_loudness(r, B, (long)wg * hop_, false);
+    else
     PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, nullptr, 0, 0));
     PE_LAUNCH_KB("chunk_pcm_gain_kernel", 10.0 * B * wg * hop_,
                  launch::chunk_pcm_gain(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_, gdev));
     return;
   }
   PE_LAUNCH_KB("chunk_pcm_kernel", 10.0 * B * wg * hop_, launch::chunk_pcm(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
+}
+
+// Target loudness of streams, in stream_gain_kernel's place between the chunk's peak and its conversion: the segment sums of
+// the rows' chunks (at most max_n samples each) added to the streams' own, then the running loudness and the gain per row
+// (kernels/stream_loudness.h). rs: the chunks are the resampled rows.
+void Engine::issue_stream_loudness(const ChunkRows& r, int B, long max_n, bool rs) {
+  if (!r.lctl || !r.ldev || !r.lseg || !r.ltail || !sl_coef_ || r.lW != sl_W_ || sl_h_ < 1 || B > r.cap)
+    throw std::runtime_error("stream loudness blocks are not sized for this call");
+  const SlP p = sl_params(r);
+  SlChunkP q{};
+  if (rs) { q.x = raudio_.get(); q.x_bs = So_; q.rows = rs_dev_.get(); q.rcap = rs_cap_; q.y_cap = So_; }
+  else { q.x = audio_; q.x_bs = Ss_; q.st = r.dev.get(); q.cap = r.cap; q.hop = hop_; }
+  const int nseg = (int)((std::max<long>(max_n, 1) + sl_h_ - 1) / sl_h_) + 1;
+  PE_LAUNCH_KB("stream_loudness_seg_kernel", 4.0 * B * (double)max_n, launch::stream_loudness_seg(stream_, nseg, B, p, q));
+  PE_LAUNCH_K("stream_loudness_gain_kernel", launch::stream_loudness_gain(stream_, B, p, q, r.gdev.get()));
 }
 
 // HiFiGAN generator + conv_post + int16 on z (already masked by its length semantics). `zsrc` is

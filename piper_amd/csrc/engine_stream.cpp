@@ -1,8 +1,51 @@
 // Host engine, streaming: the one-utterance stream, the batch stream in lock step, the stream pool and the stream-wide
 // gain. The window stages' kernel sequences: engine_issue.cpp; life cycle, workspaces and whole-utterance calls: engine.cpp.
 #include "engine_internal.h"
+#include "kernels/stream_loudness_rule.h"
 
 namespace pe {
+
+// One sample through the K-weighting cascade in f64, as loud_step (kernels/loudness.h): the one-utterance stream's filter.
+static inline double host_loud_step(const double (&c)[10], double x, double (&z)[4]) {
+  const double ya = std::fma(c[0], x, z[0]);
+  z[0] = std::fma(-c[3], ya, std::fma(c[1], x, z[1]));
+  z[1] = std::fma(-c[4], ya, c[2] * x);
+  const double yb = std::fma(c[5], ya, z[2]);
+  z[2] = std::fma(-c[8], yb, std::fma(c[6], ya, z[3]));
+  z[3] = std::fma(-c[9], yb, c[7] * ya);
+  return yb;
+}
+
+// The gated loudness of a prefix of N samples from its segment sums, serial in f64.
+static bool host_gated_loudness(const std::vector<double>& s, int64_t N, int h, bool& is_short, double& L) {
+  is_short = N < 4 * (int64_t)h;
+  L = 0.0;
+  if (N <= 0) return false;
+  if (is_short) {
+    double sum = 0.0;
+    for (double v : s) sum += v;
+    L = -0.691 + 10.0 * std::log10(sum / (double)N);
+    return L > -70.0;
+  }
+  const int nb = (int)(N / h) - 3;
+  const double inv = 1.0 / (4.0 * (double)h);
+  double gate = -70.0;
+  bool ok = false;
+  for (int pass = 0; pass < 2; ++pass) {
+    double tot = 0.0;
+    int ct = 0;
+    for (int j = 0; j < nb; ++j) {
+      const double zj = (((s[j] + s[j + 1]) + s[j + 2]) + s[j + 3]) * inv;
+      const double lj = -0.691 + 10.0 * std::log10(zj);
+      if (lj > -70.0 && lj > gate) { tot += zj; ++ct; }
+    }
+    ok = ct > 0;
+    if (!ok) return false;
+    L = -0.691 + 10.0 * std::log10(tot / (double)ct);
+    gate = L - 10.0;
+  }
+  return ok;
+}
 
 int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], int64_t sid, const NoiseIn* noise,
                          const TimingIn* timing, const SeedsIn* seeds, const BlendIn* blend) {
@@ -18,6 +61,16 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
   s_active_ = true;
   s_gain_r_ = std::max(0.01f, gain_peak_);
   s_gain_first_ = true;
+  if (gain_mode_ == GAIN_LOUDNESS) {                   // the stream's loudness state starts from nothing
+    HostLoud fresh;
+    loudness_filter(output_rate(), fresh.coef);
+    fresh.h = (output_rate() + 5) / 10;
+    fresh.z[0] = fresh.z[1] = fresh.z[2] = fresh.z[3] = 0.0;
+    fresh.lu = std::numeric_limits<float>::quiet_NaN();
+    fresh.L = -std::numeric_limits<float>::infinity();
+    fresh.flags = LOUD_SHORT | LOUD_UNMEASURABLE;
+    s_sl_ = std::move(fresh);
+  }
   sample_off_.assign(2, 0);
   return s_frames_;
 }
@@ -30,6 +83,10 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
       lg_n_ = 1; lg_dev_peaks_ = nullptr; lg_lazy_ = false;
       lg_gain_.assign(1, run ? 32767.0f / s_gain_r_ : 0.f);
       lg_peak_.assign(1, run ? s_gain_r_ : 0.f);
+      if (gain_mode_ == GAIN_LOUDNESS) {                 // the stream's end state
+        lg_gain_[0] = s_sl_.first ? 0.f : s_sl_.G; lg_peak_[0] = s_sl_.r;
+        lsl_n_ = 1; lsl_lufs_.assign(1, s_sl_.L); lsl_flags_.assign(1, s_sl_.flags);
+      }
     }
     s_active_ = false;
     if (nsamples) *nsamples = 0;
@@ -73,6 +130,29 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
     R = std::min<size_t>((size_t)gain_ramp_, n);
     s_gain_r_ = level;
     s_gain_first_ = false;
+  } else if (gain_mode_ == GAIN_LOUDNESS && n > 0) {
+    // the rule of stream_loudness_gain_kernel on an f64 serial filter that runs through the chunks
+    HostLoud& q = s_sl_;
+    float c = 0.f;
+    for (size_t i = 0; i < n; ++i) {
+      c = std::max(c, std::fabs(ha[i]));
+      const double y = host_loud_step(q.coef, (double)ha[i], q.z);
+      const size_t j = (size_t)((q.N + (int64_t)i) / q.h);
+      if (j >= q.seg.size()) q.seg.resize(j + 1, 0.0);
+      q.seg[j] = std::fma(y, y, q.seg[j]);
+    }
+    q.N += (int64_t)n;
+    bool is_short;
+    double L;
+    const bool ok = host_gated_loudness(q.seg, q.N, q.h, is_short, L);
+    const float rp = std::max(q.r, c);
+    const SlRule o = sl_rule(ok, is_short, L, sl_T_, (float)std::pow(10.0, (double)sl_cdb_ / 20.0), sl_prior_, rp, q.G, q.first, q.lu);
+    g0 = o.g0; sc = o.g1; level = rp;
+    R = std::min<size_t>((size_t)gain_ramp_, n);
+    q.r = rp; q.G = o.g1; q.first = false;
+    q.L = ok ? (float)L : -std::numeric_limits<float>::infinity();
+    q.flags = o.flags;
+    lsl_n_ = 1; lsl_lufs_.assign(1, q.L); lsl_flags_.assign(1, q.flags);
   }
   const float dg = g0 - sc, Rf = (float)std::max<size_t>(R, 1);
   s_pcm_.resize(n);
@@ -98,6 +178,8 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
 
 void Engine::rows_free(ChunkRows& r) {
   r.host.reset(); r.dev.reset(); r.pcm.reset(); r.audio.reset(); r.gctl.reset(); r.gdev.reset();
+  r.lctl.reset(); r.ldev.reset(); r.lseg.reset(); r.ltail.reset();
+  r.lnseg = r.lW = 0;
   lg_dev_peaks_ = nullptr;                               // (a default-mode report not yet fetched pointed into r.dev)
   r.cap = 0;
 }
@@ -214,6 +296,7 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   out.audio = nullptr;
   if (total == 0) {                                    // no row has frames left
     gain_report_idle(r.gctl.get(), cap, n);
+    if (gain_mode_ == GAIN_LOUDNESS) sl_collect(r, n, false);
     return false;
   }
   grow_pinned(r.pcm, (size_t)total);
@@ -229,13 +312,19 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   } else {
     if (!r.gctl) gain_blocks_alloc(r, cap);            // (the batch stream's: the pool's exist since open)
     if ((int)r.gfirst.size() < n) r.gfirst.assign(n, 1);
-    gain_prepare(r.gctl.get(), cap, r.gfirst, n);
+    if (gain_mode_ == GAIN_LOUDNESS) {
+      sl_ensure(r, cap, out_samples((int64_t)clamp * hop_));
+      sl_prepare(r, n);
+    } else {
+      gain_prepare(r.gctl.get(), cap, r.gfirst, n);
+    }
     snprintf(key, sizeof(key), "%c|%d|%d|%d|g%d", r.stage, n, r.wg, Fs_, gain_mode_);
   }
   run_stage(r.stage, key);
   PE_HIP(hipStreamSynchronize(stream_));
   gain_collect(r.gctl.get(), cap, n, r.gfirst, r.off.data(),
                rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(r.dev.get()) + sb_o_peak(cap));
+  if (gain_mode_ == GAIN_LOUDNESS) sl_collect(r, n, true);
   for (int b = 0; b < n; ++b) r.pos[b] += st[sb_o_count(cap) + b] / hop_;
   out.pcm = r.pcm.get();
   out.audio = want_audio ? r.audio.get() : nullptr;
@@ -485,6 +574,7 @@ void Engine::gain_collect(const int* ctl, int cap, int n, std::vector<char>& fir
   }
   lg_dev_peaks_ = nullptr;
   lg_lazy_ = false;
+  if (gain_mode_ == GAIN_LOUDNESS) return;             // (sl_collect: the report lies in the rows' own control block)
   const float* cf = reinterpret_cast<const float*>(ctl);
   lg_gain_.assign(cf + sg_o_rgain(cap), cf + sg_o_rgain(cap) + n);
   lg_peak_.assign(cf + sg_o_rpeak(cap), cf + sg_o_rpeak(cap) + n);
@@ -504,6 +594,113 @@ void Engine::gain_report_idle(const int* ctl, int cap, int n) {
   // its final level; a row that delivered nothing since wrote its stored one)
   const float* cf = reinterpret_cast<const float*>(ctl);
   for (int b = 0; b < n && b < cap; ++b) { lg_gain_[b] = cf[sg_o_rgain(cap) + b]; lg_peak_[b] = cf[sg_o_rpeak(cap) + b]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// streams at a target loudness (kernels/stream_loudness.h)
+// ------------------------------------------------------------------------------------------------
+
+void Engine::set_stream_loudness(float target_lufs, float ceiling_db, float prior_lufs, int ramp_samples) {
+  EntryLock entry_lock;
+  check_target(target_lufs);
+  check_ceiling(ceiling_db);
+  if (std::isinf(prior_lufs) || (prior_lufs == prior_lufs && (prior_lufs < -70.f || prior_lufs > 0.f)))
+    throw std::runtime_error("prior loudness " + std::to_string(prior_lufs) + " LUFS outside [-70, 0] (NaN: none)");
+  if (ramp_samples < 0 || ramp_samples > GAIN_MAX_RAMP)
+    throw std::runtime_error("stream loudness ramp_samples " + std::to_string(ramp_samples) + " outside [0, " +
+                             std::to_string(GAIN_MAX_RAMP) + "]");
+  loud_check_rate(output_rate());
+  bool live = s_active_ && s_pos_ < s_frames_;
+  if (sb_active_)
+    for (int b = 0; b < B_ && b < (int)batch_rows_.pos.size(); ++b) live = live || batch_rows_.pos[b] < frames_h_[b];
+  bool pool = false;
+  for (int s = 0; s < sp_slots_; ++s) pool = pool || sp_live_[s] != 0;
+  if (live || pool)
+    throw std::runtime_error(std::string("the stream loudness cannot change while a ") +
+                             (pool ? "stream pool slot is occupied" : "stream is live") + " on this handle");
+  // all four numbers are data the gain kernel reads from the control block; the mode is part of the window stages' graph
+  // keys, so nothing is dropped here
+  sl_T_ = target_lufs; sl_cdb_ = ceiling_db; sl_prior_ = prior_lufs;
+  gain_mode_ = GAIN_LOUDNESS; gain_ramp_ = ramp_samples;
+}
+
+int Engine::stream_last_loudness(float* lufs, float* gain, float* peak, int32_t* flags, int64_t capacity) {
+  EntryLock entry_lock;
+  if (lsl_n_ < 0 || lg_n_ < 0) throw std::runtime_error("no stream chunk delivered at a target loudness on this handle yet");
+  if (gain_mode_ != GAIN_LOUDNESS) throw std::runtime_error("the stream loudness is not set (pe_set_stream_loudness)");
+  if ((lufs || gain || peak || flags) && capacity < lsl_n_) throw std::runtime_error("stream loudness report buffer too small");
+  for (int b = 0; b < lsl_n_; ++b) {
+    if (lufs) lufs[b] = lsl_lufs_[b];
+    if (gain) gain[b] = lg_gain_[b];
+    if (peak) peak[b] = lg_peak_[b];
+    if (flags) flags[b] = lsl_flags_[b];
+  }
+  return lsl_n_;
+}
+
+void Engine::sl_ensure(ChunkRows& r, int cap, int64_t max_samples) {
+  const int fs = output_rate();
+  loud_check_rate(fs);
+  if (!sl_coef_ || sl_fs_ != fs) {
+    PE_HIP(hipStreamSynchronize(stream_));
+    if (sl_coef_) drop_graphs();                       // (h / W / R are kernel arguments inside the graphs)
+    sl_upload_filter(fs);
+  }
+  const int nseg = (int)((max_samples + sl_h_ - 1) / sl_h_) + 2;
+  if (r.lctl && r.ldev && r.lseg && r.ltail && r.lnseg >= nseg && r.lW == sl_W_) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  if (r.lctl) drop_graphs();                           // the blocks' addresses are kernel arguments inside the stage's graphs
+  r.lnseg = r.lW = 0;
+  side_alloc(r.lctl, (size_t)slc_words(cap), false, FILL_ZERO);
+  side_alloc(r.ldev, (size_t)sld_words(cap), false, FILL_POISON_OR_ZERO);
+  side_alloc(r.lseg, (size_t)cap * nseg, false, FILL_POISON, "stream loudness segment sums");
+  side_alloc(r.ltail, (size_t)cap * 2 * sl_W_, false, FILL_POISON);
+  PE_HIP(hipDeviceSynchronize());
+  r.lnseg = nseg; r.lW = sl_W_;
+  // (nothing of a stream survives this: every row starts afresh, as after a begin or a join)
+  r.gfirst.assign(r.gfirst.size(), 1);
+}
+
+// The previous chunk ended with a synchronisation: nothing on the device reads or writes the control block any more.
+void Engine::sl_prepare(ChunkRows& r, int n) {
+  int* ctl = r.lctl.get();
+  const float C = (float)std::pow(10.0, (double)sl_cdb_ / 20.0);
+  memcpy(ctl, &sl_T_, sizeof(float));
+  memcpy(ctl + 1, &C, sizeof(float));
+  memcpy(ctl + 2, &sl_prior_, sizeof(float));
+  ctl[3] = gain_ramp_;
+  for (int b = 0; b < n && b < r.cap; ++b) ctl[slc_o_first(r.cap) + b] = r.gfirst[b] ? 1 : 0;
+}
+
+SlP Engine::sl_params(const ChunkRows& r) const {
+  SlP p{};
+  p.ctl = r.lctl.get(); p.dev = r.ldev.get(); p.cap = r.cap;
+  p.coef = sl_coef_.get(); p.h = sl_h_; p.W = sl_W_; p.R = sl_R_;
+  p.seg = r.lseg.get(); p.nseg_cap = r.lnseg; p.tail = r.ltail.get();
+  return p;
+}
+
+// The report of a chunk call over n rows (ran: its kernels ran; else nothing was delivered): a row whose stream has
+// delivered nothing yet reports {-inf, 0, 0, SHORT | UNMEASURABLE}, every other row what its last chunk wrote.
+void Engine::sl_collect(ChunkRows& r, int n, bool ran) {
+  lsl_n_ = n;
+  lsl_lufs_.assign(n, -std::numeric_limits<float>::infinity());
+  lsl_flags_.assign(n, LOUD_SHORT | LOUD_UNMEASURABLE);
+  lg_gain_.assign(n, 0.f);
+  lg_peak_.assign(n, 0.f);
+  const int cap = r.cap;
+  const int* ctl = r.lctl.get();
+  if (!ctl) return;
+  const float* cf = reinterpret_cast<const float*>(ctl);
+  for (int b = 0; b < n && b < cap; ++b) {
+    const bool got = ran && lg_got_[b];
+    if (b < (int)r.gfirst.size() && r.gfirst[b] && !got) continue;
+    lsl_lufs_[b] = cf[slc_o_lufs(cap) + b];
+    lsl_flags_[b] = ctl[slc_o_flags(cap) + b];
+    lg_gain_[b] = cf[slc_o_gain(cap) + b];
+    lg_peak_[b] = cf[slc_o_peak(cap) + b];
+    if (got) r.gfirst[b] = 0;
+  }
 }
 
 }  // namespace pe

@@ -7,6 +7,7 @@
 #include "loudness.h"
 #include "true_peak.h"
 #include "limiter.h"
+#include "stream_loudness.h"
 
 namespace pe {
 namespace launch {
@@ -74,6 +75,14 @@ void chunk_pcm_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs
 void stream_gain(hipStream_t stream, int* ctl, int* gb, int cap, int B, int mode, const int* st, int hop, const int* rows,
                  int rcap, long y_cap) {
   PE_LAUNCH(stream_gain_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, ctl, gb, cap, B, mode, st, hop, rows, rcap, y_cap);
+}
+
+void stream_loudness_seg(hipStream_t stream, int nseg, int B, const SlP& p, const SlChunkP& q) {
+  PE_LAUNCH(stream_loudness_seg_kernel, dim3(nseg, B), dim3(LOUD_TPB), 0, stream, p, q);
+}
+
+void stream_loudness_gain(hipStream_t stream, int B, const SlP& p, const SlChunkP& q, int* gq) {
+  PE_LAUNCH(stream_loudness_gain_kernel, dim3(B), dim3(64), 0, stream, p, q, gq);
 }
 
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,

@@ -291,6 +291,48 @@ static constexpr int sgd_o_g1(int cap) { return 2 * cap; }
 static constexpr int sgd_o_ramp(int cap) { return 3 * cap; }
 static constexpr int sgd_words(int cap) { return 4 * cap; }
 
+// ---- target loudness of streams (stream_loudness.h: stream_loudness_seg_kernel, stream_loudness_gain_kernel; mode
+// GAIN_LOUDNESS of the stream-wide gain). The setting's numbers are DATA like the other modes': a pinned host
+// control block of its own for `cap` rows, which the gain kernel reads in place and writes its report into; what a stream
+// carries from chunk to chunk lives on the device: a state block, the segment sums seg[cap][nseg_cap] (f64) and two tail
+// buffers of W floats per row, tail[cap][2][W] (the kernels alternate between them: the seg kernel reads one and writes the
+// other). The conversion's operands go to the sgd_* words of the rows' gain block.
+//   control (pinned host)  T (LUFS), C (ceiling as a peak ratio), prior (LUFS; NaN: none) as f32, R0, first[cap], then the
+//                          report: L[cap] (f32 LUFS, -inf: not measurable), g1[cap], r'[cap] (f32), flags[cap], g0[cap], R[cap]
+//   state (device)         r[cap] running peak, G[cap] last end-of-chunk gain, lu[cap] last loudness used (NaN: none) as
+//                          f32, N[cap] samples delivered, par[cap] which tail buffer holds the stream's last W samples
+static constexpr int GAIN_LOUDNESS = 3;
+static constexpr int LOUD_PRIOR = 16;          // (beside LOUD_SHAPED = 8 of the whole-utterance flags, below)
+static constexpr int slc_o_first(int cap) { (void)cap; return 4; }
+static constexpr int slc_o_lufs(int cap) { return 4 + cap; }
+static constexpr int slc_o_gain(int cap) { return 4 + 2 * cap; }
+static constexpr int slc_o_peak(int cap) { return 4 + 3 * cap; }
+static constexpr int slc_o_flags(int cap) { return 4 + 4 * cap; }
+static constexpr int slc_o_g0(int cap) { return 4 + 5 * cap; }
+static constexpr int slc_o_ramp(int cap) { return 4 + 6 * cap; }
+static constexpr int slc_words(int cap) { return 4 + 7 * cap; }
+static constexpr int sld_o_r(int cap) { (void)cap; return 0; }
+static constexpr int sld_o_g(int cap) { return cap; }
+static constexpr int sld_o_lu(int cap) { return 2 * cap; }
+static constexpr int sld_o_n(int cap) { return 3 * cap; }
+static constexpr int sld_o_par(int cap) { return 4 * cap; }
+static constexpr int sld_words(int cap) { return 5 * cap; }
+struct SlP {
+  int* ctl; int* dev; int cap;                 // control and state blocks for cap rows
+  const double* coef;                          // filter block (LOUD_COEF_DOUBLES, as LoudP's)
+  int h, W, R;                                 // samples of a 100 ms segment, of the tail (50 ms), of one thread's run
+  double* seg; int nseg_cap;                   // segment sums seg[cap][nseg_cap], indexed by STREAM segment
+  float* tail;                                 // tail[cap][2][W]
+};
+// Row b's chunk: n samples at x. Native rate (rows null): [first, first + count) of the row's window waveform, by the
+// window state block; converted rate: the first count outputs of the row's resampled waveform, by the resampling row block,
+// cut to y_cap as the conversion cuts it. c = the chunk's peak word.
+struct SlChunkP {
+  const float* x; long x_bs;                   // audio_ [rows][x_bs], or raudio_ [rows][y_cap ..]
+  const int* st; int cap; int hop;             // window state block (device)
+  const int* rows; int rcap; long y_cap;       // resampling row block (device), or null
+};
+
 // ---- stream pool (post.h: stream_adopt_kernel). The join block, pinned host memory for `cap` newcomers that the kernel
 // reads in place: which slot every newcomer of a join takes and how many frames it has -- data, not kernel arguments.
 //   n, (pad)               newcomers of this join

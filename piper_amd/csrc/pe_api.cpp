@@ -683,6 +683,41 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
   });
 }
 
+int pe_set_stream_loudness(pe_engine* e, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_stream_loudness(target_lufs, ceiling_db, prior_lufs, ramp_samples);
+  });
+}
+
+int pe_get_stream_loudness(pe_engine* e, int32_t* on, float* target_lufs, float* ceiling_db, float* prior_lufs, int32_t* ramp_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (on) *on = e->eng->stream_gain_mode() == PE_GAIN_LOUDNESS ? 1 : 0;
+    if (target_lufs) *target_lufs = e->eng->stream_loudness_target();
+    if (ceiling_db) *ceiling_db = e->eng->stream_loudness_ceiling();
+    if (prior_lufs) *prior_lufs = e->eng->stream_loudness_prior();
+    if (ramp_samples) *ramp_samples = e->eng->stream_gain_ramp();
+  });
+}
+
+int pe_stream_last_loudness(pe_engine* e, float* lufs, float* gain, float* peak, int32_t* flags, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->stream_last_loudness(lufs, gain, peak, flags, capacity);
+  });
+}
+
+int pe_debug_stream_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
+                             int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
+                             float* lufs, float* g0, float* g1, int32_t* flags, int16_t* pcm) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_stream_loudness(x, batch, stride, fs, chunks, n_chunks, target_lufs, ceiling_db, prior_lufs, ramp_samples, lufs,
+                                  g0, g1, flags, pcm);
+  });
+}
+
 int pe_set_loudness(pe_engine* e, int32_t on, float target_lufs, float ceiling_db) {
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");

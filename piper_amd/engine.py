@@ -543,7 +543,7 @@ class Engine:
         """(mode, peak, ramp in samples) as set by ``set_stream_gain``."""
         m, p, r = C.c_int32(), C.c_float(), C.c_int32()
         self._check(self._lib.pe_get_stream_gain(self._h, C.byref(m), C.byref(p), C.byref(r)))
-        return self.GAIN_MODES[m.value], float(p.value), int(r.value)
+        return (self.GAIN_MODES + ("loudness",))[m.value], float(p.value), int(r.value)
 
     def stream_last_gains(self):
         """(gain, peak) float32 arrays of the last chunk call of any kind, one entry per utterance / slot: the gain at the
@@ -556,6 +556,40 @@ class Engine:
         return g[:n.value], p[:n.value]
 
     LOUD_SHORT, LOUD_UNMEASURABLE, LOUD_LIMITED = 1, 2, 4
+    LOUD_PRIOR = 16
+
+    def set_stream_loudness(self, target_lufs: float, ceiling_db: float = -1.0, prior_lufs=None, ramp_ms: float = 5.0):
+        """Deliver the chunks of ``stream``, ``stream_batch`` and ``StreamPool`` at a target loudness (include/piper_hip.h:
+        pe_set_stream_loudness, stream gain mode ``"loudness"``): every stream carries the running BS.1770-4 gated
+        loudness of what it has delivered so far, and each chunk's gain follows it toward ``target_lufs`` under the peak
+        ceiling ``ceiling_db``, spread over the chunk's first ``ramp_ms`` milliseconds. ``prior_lufs``: the loudness
+        assumed while the stream is too short or too quiet to measure (None: none -- such chunks are delivered as
+        generated). The float chunks are the same in every mode. Not while a stream is live; ``set_stream_gain`` leaves
+        the mode."""
+        ramp = int(round(float(ramp_ms) * self.output_rate / 1000.0))
+        prior = float("nan") if prior_lufs is None else float(prior_lufs)
+        self._check(self._lib.pe_set_stream_loudness(self._h, float(target_lufs), float(ceiling_db), prior, ramp))
+
+    @property
+    def stream_loudness(self):
+        """(on, target_lufs, ceiling_db, prior_lufs or None, ramp in samples) as set by ``set_stream_loudness``."""
+        on, t, c, p, r = C.c_int32(), C.c_float(), C.c_float(), C.c_float(), C.c_int32()
+        self._check(self._lib.pe_get_stream_loudness(self._h, C.byref(on), C.byref(t), C.byref(c), C.byref(p), C.byref(r)))
+        prior = None if p.value != p.value else float(p.value)
+        return bool(on.value), float(t.value), float(c.value), prior, int(r.value)
+
+    def stream_last_loudness(self):
+        """(lufs, gain, peak, flags) of the last chunk call in the loudness mode, one entry per utterance / slot: the
+        running loudness (-inf: not measurable), the gain at the chunk's end, the running peak, LOUD_* bits
+        (pe_stream_last_loudness)."""
+        n = C.c_int32()
+        self._check(self._lib.pe_stream_last_loudness(self._h, None, None, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        L, g, p, f = np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.int32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.pe_stream_last_loudness(self._h, L.ctypes.data_as(fp), g.ctypes.data_as(fp), p.ctypes.data_as(fp),
+                                                      f.ctypes.data_as(C.POINTER(C.c_int32)), m, C.byref(n)))
+        return L[:n.value], g[:n.value], p[:n.value], f[:n.value]
 
     PEAK_SAMPLE, PEAK_TRUE = 0, 1
 
@@ -708,6 +742,30 @@ class Engine:
             float(target_lufs), float(ceiling_db), L.ctypes.data_as(fp), s.ctypes.data_as(fp),
             f.ctypes.data_as(C.POINTER(C.c_int32))))
         return L, s, f
+
+    def debug_stream_loudness(self, rows, fs: int, chunks, target_lufs: float = -23.0, ceiling_db: float = -1.0,
+                              prior_lufs=None, ramp_samples: int = 0):
+        """Test hook (pe_debug_stream_loudness): the stream loudness kernels and the chunk conversion, chunk after chunk,
+        on ``rows``, a list of 1-D float arrays at rate ``fs``. ``chunks``: an int array [n_chunks][len(rows)] of chunk
+        lengths (zeros allowed; a column's sum at most the row's length). Returns (lufs, g0, g1, flags), each
+        [n_chunks][rows], and the int16 rows (a list; what no chunk covers is zero)."""
+        B = len(rows)
+        ch = np.ascontiguousarray(np.asarray(chunks, np.int32).reshape(-1, B))
+        stride = max(1, max(len(r) for r in rows))
+        x = np.zeros((B, stride), np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        K = ch.shape[0]
+        L, g0, g1 = (np.zeros((K, B), np.float32) for _ in range(3))
+        f = np.zeros((K, B), np.int32)
+        pcm = np.zeros((B, stride), np.int16)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        prior = float("nan") if prior_lufs is None else float(prior_lufs)
+        self._check(self._lib.pe_debug_stream_loudness(
+            self._h, x.ctypes.data_as(fp), B, stride, int(fs), ch.ctypes.data_as(ip), K, float(target_lufs),
+            float(ceiling_db), prior, int(ramp_samples), L.ctypes.data_as(fp), g0.ctypes.data_as(fp), g1.ctypes.data_as(fp),
+            f.ctypes.data_as(ip), pcm.ctypes.data_as(C.POINTER(C.c_int16))))
+        return L, g0, g1, f, [pcm[b, :len(r)].copy() for b, r in enumerate(rows)]
 
     def _rates(self):
         nat, out, k = C.c_int32(), C.c_int32(), C.c_int32()
