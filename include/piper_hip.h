@@ -404,7 +404,7 @@ int pe_stream_last_gains(pe_engine* e, float* gain, float* peak, int64_t capacit
  *              fma(g0 - g1, (R - 1 - i) / R, g1), every later one by g1; clamp and truncation as before. Then r = r', G = g1.
  *   n_k == 0   moves nothing.
  * Unlike PE_GAIN_RUNNING the gain may rise as well as fall, and g0 is cut to the cap: |pcm| <= floor(32767 C) outside ramps
- * and <= floor(32767 C) + 1 inside them. Not covered on streams: the true-peak ceiling, the look-ahead limiter, a slew limit
+ * and <= floor(32767 C) + 1 inside them. Not covered on streams: the true-peak ceiling, a slew limit
  * beyond the ramp, stereo. target_lufs in [-40, -5], ceiling_db in [-20, 0], prior_lufs finite in [-70, 0] or NaN for none,
  * ramp_samples 0 .. 65536. Errors that change nothing, each naming the value: a value out of range or not finite, an unknown
  * delivered rate (a voice without a header rate: pe_set_output_rate(native, ...) first), and any call while a stream, a batch
@@ -429,6 +429,43 @@ int pe_stream_last_loudness(pe_engine* e, float* lufs, float* gain, float* peak,
 int pe_debug_stream_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
                              int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
                              float* lufs, float* g0, float* g1, int32_t* flags, int16_t* pcm);
+
+/* Look-ahead limiter on streams at a target loudness. Step 5 above caps the gain at 32767 C / r', and r'
+ * only grows: the first plosive lowers the rest of the stream. With the limiter on the stream keeps the gain of its target and
+ * only the neighbourhood of its peaks is turned down, by the zero-phase envelope of pe_set_loudness_limiter formed over the WHOLE
+ * stream. window_ms in [1, 10]; W = max(1, floor(window_ms fs / 1000 + 0.5)) at the delivered rate fs, D = 2 W. It acts in
+ * PE_GAIN_LOUDNESS only; in the other modes it is remembered and nothing changes.
+ *   gain       steps 1 to 4 and 7 to 8 above are unchanged. g1 = (float)(32767 a) always; PE_LOUD_LIMITED | PE_LOUD_SHAPED where
+ *              cap < g1 (cap from r' as before). g0 = g1 on the stream's first delivered chunk, else G, not cut to the cap.
+ *   envelope   with X the stream's floats, s_i the per-sample scale of step 7 and N_end the stream's total:
+ *              g_i = (float)((double)s_i / 32767), r[i] = min(1, C / (g_i |X_i|)), 1 where X_i = 0 and outside [0, N_end);
+ *              m, d, h and e exactly as pe_set_loudness_limiter defines them; z_i = X_i e_i in f32;
+ *              pcm_i = trunc(clamp(z_i s_i, +-floor(32767 C))). e is exactly 1 wherever no sample within 2 W passes the ceiling:
+ *              a stream that is never LIMITED delivers the int16 of the mode without the limiter bit for bit, and
+ *              |pcm| <= floor(32767 C) on every sample, ramps included.
+ *   delivery   e[i] depends on r[i - 2 W .. i + 2 W] only, so the stream holds back D samples: with N_k the stream's floats after
+ *              call k and b_-1 = 0, call k hands out the stream samples [b_k-1, b_k), b_k = N_k if the call consumed the row's
+ *              last frame, else max(0, N_k - D). The int16 and, on request, the floats (X unchanged) cover that range, and
+ *              sample_offsets / n_samples count it. A call may deliver 0 samples for a row that still has frames: the end of a
+ *              stream is decided by its frames (frames_done against total_frames; pe_stream_next: by the frames asked for so
+ *              far), not by an empty chunk. The loudness and its report stay on the undelayed prefix N_k.
+ *              pe_stream_pool_leave drops what a slot holds back.
+ * Refused, with the value named and nothing changed: window_ms out of range or not finite (on != 0), an unknown delivered rate,
+ * and any call while a stream, a batch stream or a pool slot is live / occupied. On / off and W are part of the graph keys:
+ * both sets of graphs stay cached. pe_get_stream_limiter reads on, window_ms, W and D back (any pointer may be NULL). */
+int pe_set_stream_limiter(pe_engine* e, int32_t on, float window_ms);
+int pe_get_stream_limiter(pe_engine* e, int32_t* on, float* window_ms, int32_t* window_samples, int32_t* delay_samples);
+/* The last chunk call on the handle with the limiter: *n rows (0: it ran without); max_reduction[r] = 1 - min e and
+ * shaped_samples[r] = the count of e < 1 over the samples that call delivered for row r. Any array may be NULL; capacity < *n is
+ * an error. */
+int pe_stream_last_limiter(pe_engine* e, float* max_reduction, int32_t* shaped_samples, int64_t capacity, int32_t* n);
+/* Test hook: pe_debug_stream_loudness with the limiter of window_ms on, the production kernels chunk after chunk. A row ends
+ * with its last chunk of length > 0. Also out: delivered[n_chunks][batch] = samples handed out per call and row;
+ * env[batch][stride] = e per stream sample; pcm[batch][stride] holds the int16 in delivery order, which is stream order. */
+int pe_debug_stream_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
+                            int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
+                            float window_ms, float* lufs, float* g0, float* g1, int32_t* flags, int32_t* delivered, float* env,
+                            int16_t* pcm);
 
 /* Target loudness of whole utterances. By default every utterance of pe_synthesize*, pe_fetch, the groups and the coalescer
  * is scaled by 32767 / max(0.01, its peak) (the reference's rule, piper.cpp:410-431): the PEAK is fixed, the level is not, and a

@@ -27,6 +27,7 @@ SYMBOLS = [
     "pe_get_durations", "pe_get_info", "pe_set_output_rate", "pe_get_output_rate", "pe_debug_resample",
     "pe_set_stream_gain", "pe_get_stream_gain", "pe_stream_last_gains",
     "pe_set_stream_loudness", "pe_get_stream_loudness", "pe_stream_last_loudness", "pe_debug_stream_loudness",
+    "pe_set_stream_limiter", "pe_get_stream_limiter", "pe_stream_last_limiter", "pe_debug_stream_limiter",
     "pe_set_loudness", "pe_get_loudness", "pe_last_loudness", "pe_loudness_filter", "pe_debug_loudness",
     "pe_set_loudness_ceiling", "pe_get_loudness_ceiling", "pe_last_true_peak", "pe_true_peak_filter", "pe_debug_true_peak",
     "pe_set_loudness_limiter", "pe_get_loudness_limiter", "pe_last_limiter", "pe_limiter_window", "pe_debug_limiter",
@@ -139,6 +140,12 @@ def bind(path: str) -> C.CDLL:
     lib.pe_stream_last_loudness.argtypes = [vp, f32p, f32p, f32p, i32p, C.c_int64, i32p]
     lib.pe_debug_stream_loudness.argtypes = [vp, f32p, C.c_int32, C.c_int64, C.c_int32, i32p, C.c_int32, C.c_float, C.c_float,
                                              C.c_float, C.c_int32, f32p, f32p, f32p, i32p, C.POINTER(C.c_int16)]
+    lib.pe_set_stream_limiter.argtypes = [vp, C.c_int32, C.c_float]
+    lib.pe_get_stream_limiter.argtypes = [vp, i32p, f32p, i32p, i32p]
+    lib.pe_stream_last_limiter.argtypes = [vp, f32p, i32p, C.c_int64, i32p]
+    lib.pe_debug_stream_limiter.argtypes = [vp, f32p, C.c_int32, C.c_int64, C.c_int32, i32p, C.c_int32, C.c_float, C.c_float,
+                                            C.c_float, C.c_int32, C.c_float, f32p, f32p, f32p, i32p, i32p, f32p,
+                                            C.POINTER(C.c_int16)]
     lib.pe_set_loudness.argtypes = [vp, C.c_int32, C.c_float, C.c_float]
     lib.pe_get_loudness.argtypes = [vp, i32p, f32p, f32p]
     lib.pe_last_loudness.argtypes = [vp, f32p, f32p, f32p, i32p, C.c_int64, i32p]

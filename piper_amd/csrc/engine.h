@@ -258,6 +258,25 @@ class Engine {
                              int16_t* pcm);
   // end-of-chunk gain and the level it came from, per row of the last chunk call of any kind; returns the rows
   int stream_last_gains(float* gain, float* peak, int64_t capacity);
+  // Look-ahead limiter on streams at a target loudness (kernels/stream_limiter.h). Acts in GAIN_LOUDNESS
+  // only (remembered otherwise): a chunk whose cap is under its target gain keeps that gain (LIMITED | SHAPED) and the
+  // envelope of 4.6.1, formed over the WHOLE stream, turns down the neighbourhood of the peaks; every stream holds back
+  // D = 2 W samples for it, W = round(window_ms fs / 1000) at the delivered rate, and hands them out with the chunk that
+  // consumes its last frame. Refused, with nothing changed, for a window outside [1, 10] ms or not finite, an unknown
+  // delivered rate, or while a stream is live / a pool slot occupied. On / off and W are part of the window stages' graph keys.
+  void set_stream_limiter(bool on, float window_ms);
+  bool stream_limiter_on() const { return slim_on_; }
+  float stream_limiter_ms() const { return slim_ms_; }
+  int stream_limiter_window() const { return output_rate() > 0 ? limiter_window_samples(output_rate(), slim_ms_) : 0; }
+  // per row of the last chunk call with the limiter: 1 - min e and the count of e < 1 over the samples that call delivered;
+  // returns the rows (0: that call did not run with the limiter)
+  int stream_last_limiter(float* max_reduction, int32_t* shaped_samples, int64_t capacity);
+  // test hook: debug_stream_loudness with the limiter of window_ms on -- the production kernels chunk after chunk; a row ends
+  // with its last chunk of length > 0. Also out: delivered[n_chunks][batch] samples handed out per call and row,
+  // env[batch][stride] = e per stream sample; pcm[batch][stride] holds the int16 in delivery order.
+  void debug_stream_limiter(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                            float ceiling_db, float prior_lufs, int ramp_samples, float window_ms, float* lufs, float* g0, float* g1,
+                            int32_t* flags, int32_t* delivered, float* env, int16_t* pcm);
 
   // Streaming decode of a whole BATCH in lock step: stream_begin_batch is upload (one scales triple per utterance) + text
   // encoder + durations + flow for B utterances, once; the latent stays resident. Every stream_next_batch decodes the
@@ -711,6 +730,11 @@ class Engine {
     // [cap][2][lW]; allocated with the first chunk in that mode, they live and die with the blocks above
     PinBuf<int> lctl; DevBuf<int> ldev; DevBuf<double> lseg; DevBuf<float> ltail;
     int lnseg = 0, lW = 0;
+    // look-ahead limiter on streams (params.h: slm_*): control (pinned), report words (device) and their pinned copy, scale
+    // tails [cap][2][SLM_TAIL]; allocated with the first chunk that runs with it, beside the blocks above. Host view per
+    // row: stream samples so far and handed out so far (reset with the row's gfirst flag)
+    PinBuf<int> mctl, mreph; DevBuf<int> mrep; DevBuf<float> mstail;
+    std::vector<int64_t> mN, mB;
     std::vector<char> gfirst;                      // per row: nothing delivered yet (its level starts afresh)
     std::vector<int32_t> pos;                      // frames delivered per row; its size is the number of rows
     std::vector<int64_t> off;                      // sample offsets of the current chunk
@@ -754,12 +778,26 @@ class Engine {
   void sl_ensure(ChunkRows& r, int cap, int64_t max_samples);
   void sl_prepare(ChunkRows& r, int n);
   SlP sl_params(const ChunkRows& r) const;
-  void issue_stream_loudness(const ChunkRows& r, int B, long max_n, bool rs);
+  void issue_stream_loudness(const ChunkRows& r, int B, long max_n, bool rs);      // (with the limiter on: its launch too)
   void sl_collect(ChunkRows& r, int n, bool ran);
   struct HostLoud {
     double coef[10]; double z[4]; std::vector<double> seg; int64_t N = 0; int h = 1;
     float r = 0.f, G = 0.f, lu = 0.f, L = 0.f; int flags = 0; bool first = true;
+    // look-ahead limiter: floats and scales of the stream samples [N - hx.size(), N), what has been handed out, the weights
+    std::vector<float> hx, hs, hw; int64_t B = 0; int W = 0;
   } s_sl_;
+  // look-ahead limiter on streams: the setting, the weights for the window at the delivered rate (a table of fixed size:
+  // its address stays, W is part of the graph keys), the report of the last chunk call
+  bool slim_on_ = false;
+  float slim_ms_ = 5.f;
+  DevBuf<float> slim_h_; int slim_fs_ = 0, slim_W_ = 0; float slim_hms_ = 0.f;
+  std::vector<float> lsm_maxred_;
+  std::vector<int32_t> lsm_shaped_;
+  int lsm_n_ = 0;
+  std::vector<float> s_pcm_f_;                             // one-utterance stream: the floats a delayed delivery hands out
+  bool slim_active() const { return gain_mode_ == GAIN_LOUDNESS && slim_on_; }
+  void slim_ensure(ChunkRows& r, int cap);                 // the table for the rate and the rows' limiter blocks
+  SlmP slim_params(const ChunkRows& r) const;
   std::vector<float> lsl_lufs_;
   std::vector<int32_t> lsl_flags_;
   int lsl_n_ = -1;
@@ -844,6 +882,9 @@ class Engine {
     return ld_kind_ == PEAK_TRUE ? "|l2" : "|l1";
   }
   static void lim_check(bool on, float window_ms);                // throws the refusal
+  void debug_stream_rows(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                         float ceiling_db, float prior_lufs, int ramp_samples, float window_ms, float* lufs, float* g0, float* g1,
+                         int32_t* flags, int32_t* delivered, float* env, int16_t* pcm);      // both stream test hooks
   // the delivery chain's other refusals and small formulas, each written once (engine_deliver.cpp)
   static void check_target(float target_lufs);
   static void check_ceiling(float ceiling_db);

@@ -3,6 +3,7 @@
 // kernel sequences (issue_resample, issue_loudness), the reports and the four debug hooks. Life cycle, workspaces and the
 // synthesis call: engine.cpp; streams: engine_stream.cpp.
 #include "engine_internal.h"
+#include "kernels/stream_limiter_rule.h"
 
 #include <numeric>
 
@@ -925,7 +926,26 @@ void Engine::debug_loudness(const float* x, int batch, int64_t stride, const int
 void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
                                    float ceiling_db, float prior_lufs, int ramp_samples, float* lufs, float* g0, float* g1,
                                    int32_t* flags, int16_t* pcm) {
+  debug_stream_rows(x, batch, stride, fs, chunks, n_chunks, target, ceiling_db, prior_lufs, ramp_samples, 0.f, lufs, g0, g1, flags,
+                    nullptr, nullptr, pcm);
+}
+
+void Engine::debug_stream_limiter(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                                  float ceiling_db, float prior_lufs, int ramp_samples, float window_ms, float* lufs, float* g0,
+                                  float* g1, int32_t* flags, int32_t* delivered, float* env, int16_t* pcm) {
+  if (!delivered || !env) throw std::runtime_error("null argument");
+  lim_check(true, window_ms);
+  debug_stream_rows(x, batch, stride, fs, chunks, n_chunks, target, ceiling_db, prior_lufs, ramp_samples, window_ms, lufs, g0, g1,
+                    flags, delivered, env, pcm);
+}
+
+// window_ms > 0: with the look-ahead limiter (stream_limiter_kernel in the conversion's place; a row ends with its last chunk
+// of length > 0; pcm in delivery order, delivered[n_chunks][batch], env[batch][stride]).
+void Engine::debug_stream_rows(const float* x, int batch, int64_t stride, int fs, const int32_t* chunks, int n_chunks, float target,
+                               float ceiling_db, float prior_lufs, int ramp_samples, float window_ms, float* lufs, float* g0, float* g1,
+                               int32_t* flags, int32_t* delivered, float* env, int16_t* pcm) {
   EntryLock entry_lock;
+  const bool lim = window_ms > 0.f;
   if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
   if (!x || !chunks || !lufs || !g0 || !g1 || !flags || !pcm) throw std::runtime_error("null argument");
   if (stride < 1 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [1, 2^28]");
@@ -937,6 +957,7 @@ void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, in
     throw std::runtime_error("prior loudness " + std::to_string(prior_lufs) + " LUFS outside [-70, 0] (NaN: none)");
   if (ramp_samples < 0 || ramp_samples > GAIN_MAX_RAMP) throw std::runtime_error("ramp_samples outside [0, " + std::to_string(GAIN_MAX_RAMP) + "]");
   int maxc = 1;
+  std::vector<int> lastk((size_t)batch, -1);             // the call that consumes the row's last samples
   for (int b = 0; b < batch; ++b) {
     int64_t sum = 0;
     for (int k = 0; k < n_chunks; ++k) {
@@ -944,22 +965,42 @@ void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, in
       if (c < 0) throw std::runtime_error("row " + std::to_string(b) + ": negative chunk length");
       sum += c;
       maxc = std::max(maxc, c);
+      if (c > 0) lastk[b] = k;
     }
     if (sum > stride) throw std::runtime_error("row " + std::to_string(b) + ": the chunks hold more than stride samples");
   }
   double blk[LOUD_COEF_DOUBLES];
   int h, W, R;
   loud_plan(fs, h, W, R, blk);
+  int LW = 0;
+  float table[2 * LIM_MAXW + 1] = {};
+  if (lim) {
+    std::vector<double> exact;
+    limiter_window(fs, window_ms, LW, exact);
+    to_f32(exact, table);
+  }
   PE_HIP(hipSetDevice(device_));
   finish_run();
   const int cap = (batch + 1) & ~1, nseg_cap = (int)((stride + h - 1) / h) + 2;
   const long xs = (long)((stride + 3) & ~(int64_t)3);
-  DevBuf<float> dx, dtail;
+  DevBuf<float> dx, dtail, dstail, dh, denv;
   DevBuf<double> dcoef, dseg;
-  DevBuf<int> ddev, dgq;
-  PinBuf<int> ctl, st;
+  DevBuf<int> ddev, dgq, drep;
+  PinBuf<int> ctl, st, mctl;
   PinBuf<int16_t> hp;
   try {
+    if (lim) {
+      dstail.grow((size_t)cap * 2 * SLM_TAIL);
+      dh.grow(2 * LIM_MAXW + 1);
+      denv.grow((size_t)batch * xs);
+      drep.grow((size_t)slm_rep_words(cap));
+      mctl.grow((size_t)slm_words(cap));
+      mctl.zero();
+      PE_HIP(hipMemcpyAsync(dh.get(), table, sizeof(table), hipMemcpyHostToDevice, stream_));
+      PE_HIP(hipMemsetAsync(dstail.get(), 0xFF, dstail.bytes(), stream_));
+      PE_HIP(hipMemsetAsync(drep.get(), 0xFF, drep.bytes(), stream_));
+      rows_to_device(denv.get(), xs, env, batch, stride);    // (what no call delivers comes back as the caller left it)
+    }
     dx.grow((size_t)batch * xs);
     dcoef.grow(LOUD_COEF_DOUBLES);
     dseg.grow((size_t)cap * nseg_cap);
@@ -993,25 +1034,38 @@ void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, in
     int* s = st.get();
     void* ptrs[2] = {hp.get(), nullptr};
     memcpy(s + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
-    std::vector<int64_t> done((size_t)batch, 0);
+    std::vector<int64_t> done((size_t)batch, 0), given((size_t)batch, 0);
     std::vector<char> first((size_t)batch, 1);
     const int nseg = (maxc + h - 1) / h + 1, steps = std::max(1, (maxc + CHUNK_SPB - 1) / CHUNK_SPB);
+    SlmP m{};
+    m.mctl = mctl.get(); m.lctl = ctl.get(); m.ldev = ddev.get(); m.gq = dgq.get(); m.cap = cap;
+    m.tail = dtail.get(); m.TW = W; m.stail = dstail.get(); m.h = dh.get(); m.W = LW;
+    m.st = s; m.rep = drep.get(); m.env = denv.get(); m.e_bs = xs;
     for (int k = 0; k < n_chunks; ++k) {
       for (int b = 0; b < batch; ++b) {
         const int c = chunks[(size_t)k * batch + b];
-        float m = 0.f;
-        for (int i = 0; i < c; ++i) m = std::max(m, std::fabs(x[(size_t)b * stride + done[b] + i]));
+        float pk = 0.f;
+        for (int i = 0; i < c; ++i) pk = std::max(pk, std::fabs(x[(size_t)b * stride + done[b] + i]));
         s[b] = 0;
         s[sb_o_len(cap) + b] = (int)stride;
         s[sb_o_first(cap) + b] = (int)done[b];
         s[sb_o_count(cap) + b] = c;
-        reinterpret_cast<long long*>(s + sb_o_off(cap))[b] = (long long)b * stride + done[b];
-        memcpy(s + sb_o_peak(cap) + b, &m, sizeof(float));
+        reinterpret_cast<long long*>(s + sb_o_off(cap))[b] = (long long)b * stride + (lim ? given[b] : done[b]);
+        memcpy(s + sb_o_peak(cap) + b, &pk, sizeof(float));
         ctl.get()[slc_o_first(cap) + b] = first[b];
+        if (lim) {
+          const int64_t to = c > 0 ? slm_delivered(done[b] + c, 2 * LW, k == lastk[b]) : given[b];
+          mctl.get()[b] = (int)done[b];
+          mctl.get()[slm_o_b0(cap) + b] = (int)given[b];
+          mctl.get()[slm_o_cnt(cap) + b] = (int)(to - given[b]);
+          delivered[(size_t)k * batch + b] = (int32_t)(to - given[b]);
+          given[b] = to;
+        }
       }
       launch::stream_loudness_seg(stream_, nseg, batch, p, q);
-      launch::stream_loudness_gain(stream_, batch, p, q, dgq.get());
-      launch::chunk_pcm_gain(dim3(steps, batch), stream_, dx.get(), xs, s, cap, 1, dgq.get());
+      launch::stream_loudness_gain(stream_, batch, p, q, dgq.get(), lim ? drep.get() : nullptr);
+      if (lim) launch::stream_limiter(stream_, (maxc + 2 * LW + LIM_TILE - 1) / LIM_TILE, batch, m, q);
+      else launch::chunk_pcm_gain(dim3(steps, batch), stream_, dx.get(), xs, s, cap, 1, dgq.get());
       PE_HIP(hipStreamSynchronize(stream_));
       const float* cf = reinterpret_cast<const float*>(ctl.get());
       for (int b = 0; b < batch; ++b) {
@@ -1027,6 +1081,10 @@ void Engine::debug_stream_loudness(const float* x, int batch, int64_t stride, in
       }
     }
     memcpy(pcm, hp.get(), (size_t)batch * stride * sizeof(int16_t));
+    if (lim) {
+      rows_to_host(env, stride, denv.get(), xs, batch);
+      PE_HIP(hipStreamSynchronize(stream_));
+    }
   } catch (...) {
     hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)
     throw;

@@ -433,8 +433,10 @@ void Engine::issue_window_rows(const ChunkRows& r) {
     issue_resample(B, audio_, Ss_, rs_host_.get(), nullptr, max_out, (double)B * wg * hop_);
     const int rsteps = std::max(1, (int)((max_out + CHUNK_SPB - 1) / CHUNK_SPB));
     if (gm != GAIN_CHUNK) {
-      if (gm == GAIN_LOUDNESS) issue_stream_loudness(r, B, max_out, true);
-      else
+      if (gm == GAIN_LOUDNESS) {
+        issue_stream_loudness(r, B, max_out, true);
+        if (slim_on_) return;                            // (stream_limiter_kernel has converted)
+      } else
       PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, rs_dev_.get(), rs_cap_, So_));
       PE_LAUNCH_KB("chunk_pcm_rs_gain_kernel", 10.0 * B * (double)max_out,
                    launch::chunk_pcm_rs_gain(dim3(rsteps, B), stream_, raudio_.get(), So_, rs_dev_.get(), rs_cap_, dst, cap, gdev));
@@ -449,8 +451,10 @@ void Engine::issue_window_rows(const ChunkRows& r) {
   if (gm != GAIN_FIXED)
     PE_LAUNCH_KB("chunk_peak_kernel", 4.0 * B * wg * hop_, launch::chunk_peak(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_));
   if (gm != GAIN_CHUNK) {
-    if (gm == GAIN_LOUDNESS) issue_stream_loudness(r, B, (long)wg * hop_, false);
-    else
+    if (gm == GAIN_LOUDNESS) {
+      issue_stream_loudness(r, B, (long)wg * hop_, false);
+      if (slim_on_) return;
+    } else
     PE_LAUNCH_K("stream_gain_kernel", launch::stream_gain(stream_, gctl, gdev, cap, B, gm, dst, hop_, nullptr, 0, 0));
     PE_LAUNCH_KB("chunk_pcm_gain_kernel", 10.0 * B * wg * hop_,
                  launch::chunk_pcm_gain(dim3(steps, B), stream_, audio_, Ss_, dst, cap, hop_, gdev));
@@ -471,7 +475,17 @@ void Engine::issue_stream_loudness(const ChunkRows& r, int B, long max_n, bool r
   else { q.x = audio_; q.x_bs = Ss_; q.st = r.dev.get(); q.cap = r.cap; q.hop = hop_; }
   const int nseg = (int)((std::max<long>(max_n, 1) + sl_h_ - 1) / sl_h_) + 1;
   PE_LAUNCH_KB("stream_loudness_seg_kernel", 4.0 * B * (double)max_n, launch::stream_loudness_seg(stream_, nseg, B, p, q));
-  PE_LAUNCH_K("stream_loudness_gain_kernel", launch::stream_loudness_gain(stream_, B, p, q, r.gdev.get()));
+  if (!slim_on_) {
+    PE_LAUNCH_K("stream_loudness_gain_kernel", launch::stream_loudness_gain(stream_, B, p, q, r.gdev.get()));
+    return;
+  }
+  // the look-ahead limiter (kernels/stream_limiter.h): the rule with its flag, then the conversion of what
+  // this call delivers -- up to D = 2 W samples of the chunk before and all but D of this one
+  if (!r.mctl || !r.mrep || !r.mstail || !slim_h_ || slim_W_ < 1 || 4 * slim_W_ > sl_W_)
+    throw std::runtime_error("stream limiter blocks are not sized for this call");
+  PE_LAUNCH_K("stream_loudness_gain_kernel", launch::stream_loudness_gain(stream_, B, p, q, r.gdev.get(), r.mrep.get()));
+  const int tiles = (int)((std::max<long>(max_n, 1) + 2 * slim_W_ + LIM_TILE - 1) / LIM_TILE);
+  PE_LAUNCH_KB("stream_limiter_kernel", 10.0 * B * (double)max_n, launch::stream_limiter(stream_, tiles, B, slim_params(r), q));
 }
 
 // HiFiGAN generator + conv_post + int16 on z (already masked by its length semantics). `zsrc` is

@@ -2,6 +2,7 @@
 // gain. The window stages' kernel sequences: engine_issue.cpp; life cycle, workspaces and whole-utterance calls: engine.cpp.
 #include "engine_internal.h"
 #include "kernels/stream_loudness_rule.h"
+#include "kernels/stream_limiter_rule.h"
 
 namespace pe {
 
@@ -69,6 +70,12 @@ int Engine::stream_begin(const int64_t* ids, int64_t n, const float scales[3], i
     fresh.lu = std::numeric_limits<float>::quiet_NaN();
     fresh.L = -std::numeric_limits<float>::infinity();
     fresh.flags = LOUD_SHORT | LOUD_UNMEASURABLE;
+    if (slim_on_) {                                      // the limiter's window at the delivered rate, rounded as the device table
+      std::vector<double> exact;
+      limiter_window(output_rate(), slim_ms_, fresh.W, exact);
+      fresh.hw.assign(exact.size(), 0.f);
+      to_f32(exact, fresh.hw.data());
+    }
     s_sl_ = std::move(fresh);
   }
   sample_off_.assign(2, 0);
@@ -119,6 +126,8 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
   for (size_t i = 0; i < n; ++i) peak = std::max(peak, std::fabs(ha[i]));
   float g0 = 32767.0f / peak, sc = g0, level = peak;
   size_t R = 0;
+  const bool lim = slim_active() && s_sl_.W > 0;
+  lsm_n_ = 0;
   if (gain_mode_ == GAIN_FIXED) {
     level = std::max(0.01f, gain_peak_);
     g0 = sc = 32767.0f / level;
@@ -146,7 +155,7 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
     double L;
     const bool ok = host_gated_loudness(q.seg, q.N, q.h, is_short, L);
     const float rp = std::max(q.r, c);
-    const SlRule o = sl_rule(ok, is_short, L, sl_T_, (float)std::pow(10.0, (double)sl_cdb_ / 20.0), sl_prior_, rp, q.G, q.first, q.lu);
+    const SlRule o = sl_rule(ok, is_short, L, sl_T_, (float)std::pow(10.0, (double)sl_cdb_ / 20.0), sl_prior_, rp, q.G, q.first, q.lu, lim);
     g0 = o.g0; sc = o.g1; level = rp;
     R = std::min<size_t>((size_t)gain_ramp_, n);
     q.r = rp; q.G = o.g1; q.first = false;
@@ -155,20 +164,59 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
     lsl_n_ = 1; lsl_lufs_.assign(1, q.L); lsl_flags_.assign(1, q.flags);
   }
   const float dg = g0 - sc, Rf = (float)std::max<size_t>(R, 1);
-  s_pcm_.resize(n);
-  for (size_t i = 0; i < n; ++i) {
-    const float g = i < R ? std::fmaf(dg, (float)(int)(R - 1 - i) / Rf, sc) : sc;
-    float v = ha[i] * g;
-    v = std::min(std::max(v, -32768.0f), 32767.0f);
-    s_pcm_[i] = (int16_t)v;
+  const float* fout = ha;
+  size_t nout = n;
+  if (lim) {
+    // the look-ahead limiter (the arithmetic of kernels/stream_limiter_rule.h): the chunk joins the held-back
+    // samples, and the stream is handed out up to D = 2 W short of its end -- to its end with the last frame
+    HostLoud& q = s_sl_;
+    const int W = q.W, D = 2 * W;
+    const float C = (float)std::pow(10.0, (double)sl_cdb_ / 20.0), cq = (float)std::floor(32767.0 * (double)C);
+    for (size_t i = 0; i < n; ++i) {
+      q.hx.push_back(ha[i]);
+      q.hs.push_back(slm_scale_at(sc, dg, (int)R, Rf, (int)i));
+    }
+    const int64_t base = q.N - (int64_t)q.hx.size(), b0 = q.B, b1 = slm_delivered(q.N, D, f1 >= s_frames_);
+    nout = (size_t)(b1 - b0);
+    std::vector<float> rr(nout + 4 * (size_t)W, 1.0f), d(nout + 2 * (size_t)W), e(nout);
+    for (size_t k = 0; k < rr.size(); ++k) {
+      const int64_t i = b0 - 2 * W + (int64_t)k;
+      if (i >= 0 && i >= base && i < q.N) rr[k] = slm_r(q.hx[(size_t)(i - base)], q.hs[(size_t)(i - base)], C);
+    }
+    slm_host_env(rr.data(), (int)nout, W, q.hw.data(), d.data(), e.data());
+    s_pcm_.resize(nout);
+    s_pcm_f_.resize(nout);
+    float red = 0.f;
+    int shaped = 0;
+    for (size_t k = 0; k < nout; ++k) {
+      const size_t j = (size_t)(b0 + (int64_t)k - base);
+      s_pcm_f_[k] = q.hx[j];
+      s_pcm_[k] = slm_pcm(q.hx[j], e[k], q.hs[j], cq);
+      red = std::max(red, 1.0f - e[k]);
+      shaped += e[k] < 1.0f ? 1 : 0;
+    }
+    q.B = b1;
+    const size_t keep = std::min(q.hx.size(), (size_t)4 * W);
+    q.hx.erase(q.hx.begin(), q.hx.end() - (long)keep);
+    q.hs.erase(q.hs.begin(), q.hs.end() - (long)keep);
+    fout = s_pcm_f_.data();
+    lsm_n_ = 1; lsm_maxred_.assign(1, red); lsm_shaped_.assign(1, shaped);
+  } else {
+    s_pcm_.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      const float g = i < R ? std::fmaf(dg, (float)(int)(R - 1 - i) / Rf, sc) : sc;
+      float v = ha[i] * g;
+      v = std::min(std::max(v, -32768.0f), 32767.0f);
+      s_pcm_[i] = (int16_t)v;
+    }
   }
   lg_n_ = 1; lg_dev_peaks_ = nullptr; lg_lazy_ = false;
   lg_gain_.assign(1, sc);
   lg_peak_.assign(1, level);
   s_pos_ = f1;
-  if (audio) *audio = ha;
+  if (audio) *audio = fout;
   if (pcm) *pcm = s_pcm_.data();
-  if (nsamples) *nsamples = (int64_t)n;
+  if (nsamples) *nsamples = (int64_t)nout;
   return true;
 }
 
@@ -180,6 +228,7 @@ void Engine::rows_free(ChunkRows& r) {
   r.host.reset(); r.dev.reset(); r.pcm.reset(); r.audio.reset(); r.gctl.reset(); r.gdev.reset();
   r.lctl.reset(); r.ldev.reset(); r.lseg.reset(); r.ltail.reset();
   r.lnseg = r.lW = 0;
+  r.mctl.reset(); r.mreph.reset(); r.mrep.reset(); r.mstail.reset();
   lg_dev_peaks_ = nullptr;                               // (a default-mode report not yet fetched pointed into r.dev)
   r.cap = 0;
 }
@@ -262,6 +311,21 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   long long* off = reinterpret_cast<long long*>(st + sb_o_off(cap));
   int wmax = 1, cmax = 1;
   int64_t total = 0;
+  // the look-ahead limiter: a row hands out its stream up to D = 2 W short of what exists, everything with
+  // the chunk that consumes its last frame; the chunk counts go to `coff`, the delivered ones to the offsets
+  const bool lim = slim_active();
+  const int D = lim ? 2 * limiter_window_samples(output_rate(), slim_ms_) : 0;
+  bool any = false;
+  std::vector<int64_t> coff((size_t)n + 1, 0), Nk, Bk;
+  if (lim) {
+    if (!r.gctl) gain_blocks_alloc(r, cap);
+    if ((int)r.gfirst.size() < n) r.gfirst.assign(n, 1);
+    sl_ensure(r, cap, out_samples((int64_t)clamp * hop_));
+    slim_ensure(r, cap);
+    if ((int)r.mN.size() < n) { r.mN.assign(n, 0); r.mB.assign(n, 0); }
+    Nk.assign(r.mN.begin(), r.mN.begin() + n);
+    Bk.assign(r.mB.begin(), r.mB.begin() + n);
+  }
   for (int b = 0; b < n; ++b) {
     const int F = frames[b], f0 = r.pos[b];
     const int c = std::min(per_row && per_row[b] > 0 ? per_row[b] : chunk, clamp);
@@ -275,6 +339,22 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
       count = (f1 - f0) * hop_;
       ocount = out_samples((int64_t)f1 * hop_) - out_samples((int64_t)f0 * hop_);
       cmax = std::max(cmax, c);
+      any = true;
+    }
+    coff[b + 1] = coff[b] + ocount;
+    int64_t dcount = ocount;
+    if (lim) {
+      int* m = r.mctl.get();
+      const int64_t N0 = r.gfirst[b] ? 0 : r.mN[b], B0 = r.gfirst[b] ? 0 : r.mB[b];
+      dcount = 0;
+      if (ocount > 0) {
+        Nk[b] = N0 + ocount;
+        Bk[b] = slm_delivered(Nk[b], D, f0 + c >= F);
+        dcount = Bk[b] - B0;
+      }
+      m[b] = (int)std::min<int64_t>(N0, 0x7fffffff);
+      m[slm_o_b0(cap) + b] = (int)std::min<int64_t>(B0, 0x7fffffff);
+      m[slm_o_cnt(cap) + b] = (int)dcount;
     }
     st[b] = a;
     st[sb_o_len(cap) + b] = e - a;
@@ -285,7 +365,7 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
     if (rs_on_) rs_host_row(b, out_samples((int64_t)f0 * hop_), (int64_t)a * hop_, (int)ocount, (e - a) * hop_);
     off[b] = (long long)total;
     r.off[b] = total;
-    total += ocount;
+    total += dcount;
     wmax = std::max(wmax, e - a);
   }
   r.off[n] = total;
@@ -294,13 +374,15 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   out.frames_done = r.pos.data();
   out.pcm = r.pcm.get();
   out.audio = nullptr;
-  if (total == 0) {                                    // no row has frames left
+  lsm_n_ = 0;
+  if (!any) {                                          // no row has frames left (a call may deliver nothing while rows go on)
     gain_report_idle(r.gctl.get(), cap, n);
     if (gain_mode_ == GAIN_LOUDNESS) sl_collect(r, n, false);
+    if (lim) { lsm_n_ = n; lsm_maxred_.assign(n, 0.f); lsm_shaped_.assign(n, 0); }
     return false;
   }
-  grow_pinned(r.pcm, (size_t)total);
-  if (want_audio) grow_pinned(r.audio, (size_t)total);
+  grow_pinned(r.pcm, (size_t)std::max<int64_t>(total, 1));
+  if (want_audio) grow_pinned(r.audio, (size_t)std::max<int64_t>(total, 1));
   void* ptrs[2] = {r.pcm.get(), want_audio ? r.audio.get() : nullptr};
   memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
   // the window bucket: by the largest step among the rows that deliver
@@ -318,13 +400,30 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
     } else {
       gain_prepare(r.gctl.get(), cap, r.gfirst, n);
     }
-    snprintf(key, sizeof(key), "%c|%d|%d|%d|g%d", r.stage, n, r.wg, Fs_, gain_mode_);
+    if (lim) snprintf(key, sizeof(key), "%c|%d|%d|%d|g3l%d", r.stage, n, r.wg, Fs_, slim_W_);
+    else snprintf(key, sizeof(key), "%c|%d|%d|%d|g%d", r.stage, n, r.wg, Fs_, gain_mode_);
   }
   run_stage(r.stage, key);
+  if (lim) PE_HIP(hipMemcpyAsync(r.mreph.get(), r.mrep.get(), (size_t)slm_rep_words(cap) * sizeof(int), hipMemcpyDeviceToHost, stream_));
   PE_HIP(hipStreamSynchronize(stream_));
-  gain_collect(r.gctl.get(), cap, n, r.gfirst, r.off.data(),
+  // (which rows moved their state is decided by the chunks, not by what was handed out)
+  gain_collect(r.gctl.get(), cap, n, r.gfirst, coff.data(),
                rs_on_ ? rs_peaks() : reinterpret_cast<const unsigned*>(r.dev.get()) + sb_o_peak(cap));
   if (gain_mode_ == GAIN_LOUDNESS) sl_collect(r, n, true);
+  if (lim) {
+    lsm_n_ = n;
+    lsm_maxred_.assign(n, 0.f);
+    lsm_shaped_.assign(n, 0);
+    const int* w = r.mreph.get();
+    for (int b = 0; b < n; ++b) {
+      if (r.off[b + 1] > r.off[b]) {
+        memcpy(&lsm_maxred_[b], w + lim_o_maxred(cap) + b, sizeof(float));
+        lsm_shaped_[b] = w[lim_o_count(cap) + b];
+      }
+      r.mN[b] = Nk[b];
+      r.mB[b] = Bk[b];
+    }
+  }
   for (int b = 0; b < n; ++b) r.pos[b] += st[sb_o_count(cap) + b] / hop_;
   out.pcm = r.pcm.get();
   out.audio = want_audio ? r.audio.get() : nullptr;
@@ -636,6 +735,73 @@ int Engine::stream_last_loudness(float* lufs, float* gain, float* peak, int32_t*
     if (flags) flags[b] = lsl_flags_[b];
   }
   return lsl_n_;
+}
+
+// ------------------------------------------------------------------------------------------------
+// look-ahead limiter on streams (kernels/stream_limiter.h)
+// ------------------------------------------------------------------------------------------------
+
+void Engine::set_stream_limiter(bool on, float window_ms) {
+  EntryLock entry_lock;
+  lim_check(on, window_ms);
+  loud_check_rate(output_rate());
+  if (on) check_limiter_window_at(window_ms, output_rate());
+  bool live = s_active_ && s_pos_ < s_frames_;
+  if (sb_active_)
+    for (int b = 0; b < B_ && b < (int)batch_rows_.pos.size(); ++b) live = live || batch_rows_.pos[b] < frames_h_[b];
+  bool pool = false;
+  for (int s = 0; s < sp_slots_; ++s) pool = pool || sp_live_[s] != 0;
+  if (live || pool)
+    throw std::runtime_error(std::string("the stream limiter cannot change while a ") +
+                             (pool ? "stream pool slot is occupied" : "stream is live") + " on this handle");
+  // on / off and W are part of the window stages' graph keys, the weights a table behind a fixed address: nothing is dropped
+  slim_on_ = on;
+  if (on) slim_ms_ = window_ms;
+}
+
+int Engine::stream_last_limiter(float* max_reduction, int32_t* shaped_samples, int64_t capacity) {
+  EntryLock entry_lock;
+  if ((max_reduction || shaped_samples) && capacity < lsm_n_) throw std::runtime_error("stream limiter report buffer too small");
+  for (int b = 0; b < lsm_n_; ++b) {
+    if (max_reduction) max_reduction[b] = lsm_maxred_[b];
+    if (shaped_samples) shaped_samples[b] = lsm_shaped_[b];
+  }
+  return lsm_n_;
+}
+
+// The weights of the window at the delivered rate (they depend on W alone, and W is in the graph keys: a graph captured for
+// one W is replayed only after the table holds that W's weights again) and the rows' limiter blocks.
+void Engine::slim_ensure(ChunkRows& r, int cap) {
+  const int fs = output_rate();
+  if (!slim_h_ || slim_fs_ != fs || slim_hms_ != slim_ms_) {
+    int W;
+    std::vector<double> exact;
+    limiter_window(fs, slim_ms_, W, exact);
+    float table[2 * LIM_MAXW + 1] = {};
+    to_f32(exact, table);
+    PE_HIP(hipStreamSynchronize(stream_));
+    if (!slim_h_) slim_h_.grow(2 * LIM_MAXW + 1);
+    PE_HIP(hipMemcpy(slim_h_.get(), table, sizeof(table), hipMemcpyHostToDevice));
+    slim_fs_ = fs; slim_W_ = W; slim_hms_ = slim_ms_;
+  }
+  if (r.mctl && r.mreph && r.mrep && r.mstail) return;
+  PE_HIP(hipStreamSynchronize(stream_));
+  side_alloc(r.mctl, (size_t)slm_words(cap), false, FILL_ZERO);
+  side_alloc(r.mreph, (size_t)slm_rep_words(cap), false, FILL_ZERO);
+  side_alloc(r.mrep, (size_t)slm_rep_words(cap), false, FILL_POISON_OR_ZERO);
+  side_alloc(r.mstail, (size_t)cap * 2 * SLM_TAIL, false, FILL_POISON, "stream limiter scale tails");
+  PE_HIP(hipDeviceSynchronize());
+  r.mN.assign(r.mN.size(), 0);
+  r.mB.assign(r.mB.size(), 0);
+}
+
+SlmP Engine::slim_params(const ChunkRows& r) const {
+  SlmP p{};
+  p.mctl = r.mctl.get(); p.lctl = r.lctl.get(); p.ldev = r.ldev.get(); p.gq = r.gdev.get(); p.cap = r.cap;
+  p.tail = r.ltail.get(); p.TW = sl_W_; p.stail = r.mstail.get();
+  p.h = slim_h_.get(); p.W = slim_W_;
+  p.st = r.dev.get(); p.rep = r.mrep.get();
+  return p;
 }
 
 void Engine::sl_ensure(ChunkRows& r, int cap, int64_t max_samples) {

@@ -94,7 +94,9 @@ void chunk_pcm_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs
 // target loudness of streams (params.h: sl*, SlP, SlChunkP), in stream_gain's place: grid = (nseg segments a chunk can touch,
 // B rows), then one wave per row; `gq` = the rows' gain block, whose sgd_* words the conversions read
 void stream_loudness_seg(hipStream_t stream, int nseg, int B, const SlP& p, const SlChunkP& q);
-void stream_loudness_gain(hipStream_t stream, int B, const SlP& p, const SlChunkP& q, int* gq);
+void stream_loudness_gain(hipStream_t stream, int B, const SlP& p, const SlChunkP& q, int* gq, int* limrep = nullptr);
+// the look-ahead limiter on streams in the gain conversion's place: grid = (tiles of LIM_TILE delivered samples, rows)
+void stream_limiter(hipStream_t stream, int tiles, int B, const SlmP& p, const SlChunkP& q);
 // stream pool (params.h: sj_*): grid = (64-frame tiles of the newcomers' frame bucket, channels, newcomers)
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,
                   int cond_rows, const int* join, int cap, float* pool, long p_bs, int ps, float* pcond, int slots);

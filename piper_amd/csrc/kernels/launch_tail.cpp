@@ -8,6 +8,7 @@
 #include "true_peak.h"
 #include "limiter.h"
 #include "stream_loudness.h"
+#include "stream_limiter.h"
 
 namespace pe {
 namespace launch {
@@ -81,8 +82,12 @@ void stream_loudness_seg(hipStream_t stream, int nseg, int B, const SlP& p, cons
   PE_LAUNCH(stream_loudness_seg_kernel, dim3(nseg, B), dim3(LOUD_TPB), 0, stream, p, q);
 }
 
-void stream_loudness_gain(hipStream_t stream, int B, const SlP& p, const SlChunkP& q, int* gq) {
-  PE_LAUNCH(stream_loudness_gain_kernel, dim3(B), dim3(64), 0, stream, p, q, gq);
+void stream_loudness_gain(hipStream_t stream, int B, const SlP& p, const SlChunkP& q, int* gq, int* limrep) {
+  PE_LAUNCH(stream_loudness_gain_kernel, dim3(B), dim3(64), 0, stream, p, q, gq, limrep);
+}
+
+void stream_limiter(hipStream_t stream, int tiles, int B, const SlmP& p, const SlChunkP& q) {
+  PE_LAUNCH(stream_limiter_kernel, dim3(tiles, B), dim3(256), 0, stream, p, q);
 }
 
 void stream_adopt(dim3 grid, hipStream_t stream, const float* z, long z_bs, int zs, const float* cond, int cond_bs,

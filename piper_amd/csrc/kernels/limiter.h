@@ -14,6 +14,52 @@ __device__ __forceinline__ void lim_store(const LimP& p, int b, int t, float v, 
   if (p.host) p.host[host_off + t] = (short)v;
 }
 
+// The tile body shared with stream_limiter_kernel (stream_limiter.h). ms[0 .. span) holds r on entry (and a barrier has
+// passed); on return ms[q] = d[q] = 1 - min r[q - W .. q + W] for the q whose window lies in the span, 0 for the others.
+__device__ __forceinline__ void lim_window_d(float* ms, int span, int W, int tid) {
+  float v[LIM_PER];
+  int run = 1;
+  for (; 2 * run <= 2 * W + 1; run *= 2) {
+#pragma unroll
+    for (int j = 0; j < LIM_PER; ++j) {
+      const int q = tid + 256 * j;
+      v[j] = q < span ? fminf(ms[q], q + run < span ? ms[q + run] : 1.0f) : 1.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < LIM_PER; ++j) {
+      const int q = tid + 256 * j;
+      if (q < span) ms[q] = v[j];
+    }
+    __syncthreads();
+  }
+  // ms[q] = min r[q .. q + run - 1]; d[q] = 1 - min(ms[q - W], ms[q + W - run + 1]) for the q whose window lies in the span
+#pragma unroll
+  for (int j = 0; j < LIM_PER; ++j) {
+    const int q = tid + 256 * j;
+    v[j] = (q >= W && q + W < span) ? 1.0f - fminf(ms[q - W], ms[q + W - run + 1]) : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < LIM_PER; ++j) {
+    const int q = tid + 256 * j;
+    if (q < span) ms[q] = v[j];
+  }
+  __syncthreads();
+}
+// e of the span element q from d (ms), r (rs) and the weights: the taps first to last, one fma each; skipped where every d
+// of the sum is 0 (the minimum over +-2 W is 1).
+__device__ __forceinline__ float lim_env_at(const float* ms, const float* rs, const float* hs, int q, int W) {
+  float e = 1.0f;
+  if (ms[q - W] != 0.f || ms[q + W] != 0.f) {
+    const float* d = ms + q - W;
+    float acc = 0.f;
+    for (int k = 0; k <= 2 * W; ++k) acc = fmaf(hs[k], d[k], acc);
+    e = fminf(rs[q], 1.0f - acc);
+  }
+  return e;
+}
+
 // With x[0 .. n) a row, g = scale / 32767 its loudness gain, C the ceiling and W the window (all f32 unless said):
 //   r[i] = min(1, C / (g |x[i]|)), 1 where x[i] = 0 and outside [0, n): the gain that alone would hold sample i
 //   m[j] = min r[j - W .. j + W],  d = 1 - m
@@ -132,46 +178,12 @@ __device__ __forceinline__ void limiter_body(const LimP& p) {
     ms[q] = r;
   }
   __syncthreads();
-  float v[LIM_PER];
-  int run = 1;
-  for (; 2 * run <= 2 * W + 1; run *= 2) {
-#pragma unroll
-    for (int j = 0; j < LIM_PER; ++j) {
-      const int q = tid + 256 * j;
-      v[j] = q < span ? fminf(ms[q], q + run < span ? ms[q + run] : 1.0f) : 1.0f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < LIM_PER; ++j) {
-      const int q = tid + 256 * j;
-      if (q < span) ms[q] = v[j];
-    }
-    __syncthreads();
-  }
-  // ms[q] = min r[q .. q + run - 1]; d[q] = 1 - min(ms[q - W], ms[q + W - run + 1]) for the q whose window lies in the span
-#pragma unroll
-  for (int j = 0; j < LIM_PER; ++j) {
-    const int q = tid + 256 * j;
-    v[j] = (q >= W && q + W < span) ? 1.0f - fminf(ms[q - W], ms[q + W - run + 1]) : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < LIM_PER; ++j) {
-    const int q = tid + 256 * j;
-    if (q < span) ms[q] = v[j];
-  }
-  __syncthreads();
+  lim_window_d(ms, span, W, tid);
   float red = 0.f, zm = 0.f;
   int cnt = 0;
   for (int i = tid; i < nt; i += 256) {
     const int q = lead + 2 * W + i;
-    float e = 1.0f;
-    if (ms[q - W] != 0.f || ms[q + W] != 0.f) {
-      const float* d = ms + q - W;
-      float acc = 0.f;
-      for (int k = 0; k <= 2 * W; ++k) acc = fmaf(hs[k], d[k], acc);
-      e = fminf(rs[q], 1.0f - acc);
-    }
+    const float e = lim_env_at(ms, rs, hs, q, W);
     const float z = xs[q] * e;
     if constexpr (TRUE_PEAK) {
       p.z[(long)b * p.x_bs + t0 + i] = z;

@@ -461,6 +461,33 @@ struct TrimP {
   short* pcm; long p_bs; short* host;
 };
 
+// ---- look-ahead limiter on streams (stream_limiter.h: stream_limiter_kernel; mode GAIN_LOUDNESS with pe_set_stream_limiter,
+// DESIGN.md 4.9.1). A stream holds back D = 2 W samples so that what it hands out carries the envelope a whole-stream
+// computation would give. What a call delivers is DATA like the window state: a pinned host block for `cap` rows that the
+// kernel reads in place; the per-sample scales of the last SLM_TAIL samples of every stream live next to the float tails,
+// stail[cap][2][SLM_TAIL], in the same two parities (stream_loudness_gain_kernel flips the word, one workgroup per row
+// writes the other buffer). The report words (device; lim_o_maxred, lim_o_count) are cleared by the gain kernel.
+//   control (pinned host)  nprev[cap] stream samples in front of this chunk (N of the call before), b0[cap] first stream
+//                          sample this call delivers, cnt[cap] how many
+static constexpr int SLM_TAIL = 4 * LIM_MAXW;  // scales kept per stream: the 4 W samples of past a delivery looks at
+static constexpr int slm_o_b0(int cap) { return cap; }
+static constexpr int slm_o_cnt(int cap) { return 2 * cap; }
+static constexpr int slm_words(int cap) { return 3 * cap; }
+static constexpr int slm_rep_words(int cap) { return 2 * cap; }
+struct SlmP {
+  const int* mctl;                             // limiter control block (pinned host)
+  const int* lctl;                             // loudness control block: C at word 1
+  const int* ldev;                             // loudness state block: the tail parity, flipped by the gain kernel
+  const int* gq;                               // sgd_* words: g0, g1, R of this chunk
+  int cap;
+  const float* tail; int TW;                   // float tails tail[cap][2][TW] (SlP's)
+  float* stail;                                // scale tails stail[cap][2][SLM_TAIL]
+  const float* h; int W;                       // [2 W + 1] weights, W <= LIM_MAXW
+  const int* st;                               // window state block (device): packed offsets and the host output pointers
+  int* rep;                                    // report words [slm_rep_words(cap)]
+  float* env; long e_bs;                       // test hook: e[b][stream sample], or null
+};
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

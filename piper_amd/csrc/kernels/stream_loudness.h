@@ -133,7 +133,9 @@ __global__ __launch_bounds__(LOUD_TPB) void stream_loudness_seg_kernel(SlP p, Sl
 // block; {g0, g1, R} go to the sgd_* words the conversions read; {L, g1, r', flags, g0, R} into the control block's report.
 // A row with n == 0 moves nothing: its report words keep what its last chunk wrote (a `first` row: -inf, 0, 0, UNMEASURABLE),
 // and its sgd_* words are left as they are (the conversion returns at once on an empty chunk).
-__global__ __launch_bounds__(64) void stream_loudness_gain_kernel(SlP p, SlChunkP cq, int* gq) {
+// limrep (the look-ahead limiter on streams, stream_limiter.h; null: off): the rule runs with its `lim` flag, and the row's two
+// report words are cleared for stream_limiter_kernel, whatever n is.
+__global__ __launch_bounds__(64) void stream_loudness_gain_kernel(SlP p, SlChunkP cq, int* gq, int* limrep) {
   PE_KTRACE(41);
   __shared__ double ps[64];
   __shared__ int pc[64];
@@ -145,6 +147,10 @@ __global__ __launch_bounds__(64) void stream_loudness_gain_kernel(SlP p, SlChunk
   (void)sl_chunk(cq, b, n, cpk);
   const bool first = p.ctl[slc_o_first(p.cap) + b] != 0;
   float* rf = reinterpret_cast<float*>(p.ctl);
+  if (limrep && t == 0) {
+    limrep[lim_o_maxred(p.cap) + b] = 0;
+    limrep[lim_o_count(p.cap) + b] = 0;
+  }
   if (n <= 0) {
     if (first && t == 0) {
       rf[slc_o_lufs(p.cap) + b] = -__builtin_inff();
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(64) void stream_loudness_gain_kernel(SlP p, SlChunk
   const float rp = fmaxf(r >= 0.f ? r : 0.f, cpk);
   float lu = first ? __builtin_nanf("") : df[sld_o_lu(p.cap) + b];
   const float G = first ? 0.f : df[sld_o_g(p.cap) + b];
-  const SlRule o = sl_rule(ok, is_short, L, T, C, prior, rp, G, first, lu);
+  const SlRule o = sl_rule(ok, is_short, L, T, C, prior, rp, G, first, lu, limrep != nullptr);
   const int R = R0 < n ? R0 : n;
   df[sld_o_r(p.cap) + b] = rp;
   df[sld_o_g(p.cap) + b] = o.g1;

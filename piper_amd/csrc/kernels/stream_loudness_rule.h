@@ -11,8 +11,11 @@ namespace pe {
 // one-utterance stream's host conversion. In: the running loudness L of the prefix (`ok`: measurable, `is_short`), the
 // setting {T, C, prior (NaN: none)}, the running peak r' with this chunk in it, the previous end-of-chunk gain G, the
 // stream's last used loudness `lu` (NaN: none yet) and `first`. Out: g0, g1, the flags, and `lu` moved on.
+// lim (the look-ahead limiter on streams): the cap only marks -- g1 stays the target's gain, LIMITED | SHAPED
+// where the cap is the smaller, and g0 is the previous gain uncut; stream_limiter_kernel holds the ceiling sample by sample.
 struct SlRule { float g0, g1; int flags; };
-__host__ __device__ __forceinline__ SlRule sl_rule(bool ok, bool is_short, double L, float T, float C, float prior, float rp, float G, bool first, float& lu) {
+__host__ __device__ __forceinline__ SlRule sl_rule(bool ok, bool is_short, double L, float T, float C, float prior, float rp, float G, bool first, float& lu,
+                                                   bool lim = false) {
   SlRule o;
   o.flags = (is_short ? LOUD_SHORT : 0) | (ok ? 0 : LOUD_UNMEASURABLE);
   const bool has_prior = prior == prior;
@@ -37,8 +40,12 @@ __host__ __device__ __forceinline__ SlRule sl_rule(bool ok, bool is_short, doubl
   }
   const float want = (float)(32767.0 * a);
   o.g1 = want;
-  if (cap < want) { o.g1 = cap; o.flags |= LOUD_LIMITED; }
-  o.g0 = first ? o.g1 : (G < cap ? G : cap);
+  if (cap < want) {
+    o.flags |= LOUD_LIMITED;
+    if (lim) o.flags |= LOUD_SHAPED;
+    else o.g1 = cap;
+  }
+  o.g0 = first ? o.g1 : (lim || G < cap ? G : cap);
   return o;
 }
 

@@ -708,6 +708,41 @@ int pe_stream_last_loudness(pe_engine* e, float* lufs, float* gain, float* peak,
   });
 }
 
+int pe_set_stream_limiter(pe_engine* e, int32_t on, float window_ms) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_stream_limiter(on != 0, window_ms);
+  });
+}
+
+int pe_get_stream_limiter(pe_engine* e, int32_t* on, float* window_ms, int32_t* window_samples, int32_t* delay_samples) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (on) *on = e->eng->stream_limiter_on() ? 1 : 0;
+    if (window_ms) *window_ms = e->eng->stream_limiter_ms();
+    if (window_samples) *window_samples = e->eng->stream_limiter_window();
+    if (delay_samples) *delay_samples = 2 * e->eng->stream_limiter_window();
+  });
+}
+
+int pe_stream_last_limiter(pe_engine* e, float* max_reduction, int32_t* shaped_samples, int64_t capacity, int32_t* n) {
+  return guard([&] {
+    if (!e || !n) throw std::runtime_error("null argument");
+    *n = e->eng->stream_last_limiter(max_reduction, shaped_samples, capacity);
+  });
+}
+
+int pe_debug_stream_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
+                            int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
+                            float window_ms, float* lufs, float* g0, float* g1, int32_t* flags, int32_t* delivered, float* env,
+                            int16_t* pcm) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_stream_limiter(x, batch, stride, fs, chunks, n_chunks, target_lufs, ceiling_db, prior_lufs, ramp_samples, window_ms,
+                                 lufs, g0, g1, flags, delivered, env, pcm);
+  });
+}
+
 int pe_debug_stream_loudness(pe_engine* e, const float* x, int32_t batch, int64_t stride, int32_t fs, const int32_t* chunks,
                              int32_t n_chunks, float target_lufs, float ceiling_db, float prior_lufs, int32_t ramp_samples,
                              float* lufs, float* g0, float* g1, int32_t* flags, int16_t* pcm) {

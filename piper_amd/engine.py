@@ -446,11 +446,18 @@ class Engine:
         self._check(entry(self._h, ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, sc,
                           -1 if sid is None else int(sid), nref, C.byref(frames), C.byref(halo), *extra))
         self.stream_frames, self.stream_halo = frames.value, halo.value
+        done = 0
         while True:
             a, p, n = C.POINTER(C.c_float)(), C.POINTER(C.c_int16)(), C.c_int64()
             self._check(self._lib.pe_stream_next(self._h, int(chunk_frames), C.byref(a), C.byref(p), C.byref(n)))
             if n.value == 0:
-                return
+                # (the end is decided by the frames: with the stream limiter a call may hand out nothing and go on)
+                if done >= frames.value:
+                    return
+                done = min(frames.value, done + int(chunk_frames))
+                yield np.zeros(0, np.float32), np.zeros(0, np.int16)
+                continue
+            done = min(frames.value, done + int(chunk_frames))
             yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
 
     def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
@@ -493,12 +500,19 @@ class Engine:
         while True:
             cf = int(chunk_frames(k)) if callable(chunk_frames) else int(chunk_frames)
             ch = L.PeStreamChunk()
+            before = self.stream_frames_done
             self._check(self._lib.pe_stream_next_batch(self._h, cf, int(bool(want_audio)), C.byref(ch)))
             offs_k = np.frombuffer(C.string_at(ch.sample_offsets, 8 * (B + 1)), np.int64)
             self.stream_frames_done = np.frombuffer(C.string_at(ch.frames_done, 4 * B), np.int32).copy()
             total = int(offs_k[-1])
             if total == 0:
-                return
+                # (the end is decided by the frames: with the stream limiter a call may hand out nothing and go on)
+                if not np.any(before < self.stream_frames):
+                    return
+                empty = np.zeros(0, np.float32) if want_audio else None
+                yield [(empty, np.zeros(0, np.int16)) for _ in range(B)]
+                k += 1
+                continue
             p = np.frombuffer(bytearray(C.string_at(ch.pcm, 2 * total)), np.int16)
             a = np.frombuffer(bytearray(C.string_at(ch.audio, 4 * total)), np.float32) if ch.audio else None
             yield [(None if a is None else a[offs_k[b]:offs_k[b + 1]], p[offs_k[b]:offs_k[b + 1]]) for b in range(B)]
@@ -558,17 +572,45 @@ class Engine:
     LOUD_SHORT, LOUD_UNMEASURABLE, LOUD_LIMITED = 1, 2, 4
     LOUD_PRIOR = 16
 
-    def set_stream_loudness(self, target_lufs: float, ceiling_db: float = -1.0, prior_lufs=None, ramp_ms: float = 5.0):
+    def set_stream_loudness(self, target_lufs: float, ceiling_db: float = -1.0, prior_lufs=None, ramp_ms: float = 5.0,
+                            limiter: bool = False, limiter_ms: float = 5.0):
         """Deliver the chunks of ``stream``, ``stream_batch`` and ``StreamPool`` at a target loudness (include/piper_hip.h:
         pe_set_stream_loudness, stream gain mode ``"loudness"``): every stream carries the running BS.1770-4 gated
         loudness of what it has delivered so far, and each chunk's gain follows it toward ``target_lufs`` under the peak
         ceiling ``ceiling_db``, spread over the chunk's first ``ramp_ms`` milliseconds. ``prior_lufs``: the loudness
         assumed while the stream is too short or too quiet to measure (None: none -- such chunks are delivered as
         generated). The float chunks are the same in every mode. Not while a stream is live; ``set_stream_gain`` leaves
-        the mode."""
+        the mode. ``limiter``: the look-ahead limiter on streams (pe_set_stream_limiter) with a window of ``limiter_ms`` in
+        [1, 10] -- a stream whose peaks would have capped its gain keeps the target's gain and only the neighbourhood of the
+        peaks is turned down; every stream then holds back ``2 W`` samples (``stream_limiter()``), so a call may hand out
+        fewer samples than it generated, or none, and the last call of a stream hands out the rest. A refused call changes
+        nothing."""
         ramp = int(round(float(ramp_ms) * self.output_rate / 1000.0))
         prior = float("nan") if prior_lufs is None else float(prior_lufs)
-        self._check(self._lib.pe_set_stream_loudness(self._h, float(target_lufs), float(ceiling_db), prior, ramp))
+        was = self.stream_limiter()[:2]
+        self._check(self._lib.pe_set_stream_limiter(self._h, int(bool(limiter)), float(limiter_ms) if limiter else 0.0))
+        if self._lib.pe_set_stream_loudness(self._h, float(target_lufs), float(ceiling_db), prior, ramp):
+            err = EngineError(self._lib.pe_last_error().decode(errors="replace"))
+            self._lib.pe_set_stream_limiter(self._h, int(was[0]), float(was[1]))
+            raise err
+
+    def stream_limiter(self):
+        """(on, window_ms, W, D) of the look-ahead limiter on streams (pe_get_stream_limiter): the window and the delay
+        ``D = 2 W`` in samples of the delivered rate (0 where the rate is unknown)."""
+        on, ms, w, d = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32()
+        self._check(self._lib.pe_get_stream_limiter(self._h, C.byref(on), C.byref(ms), C.byref(w), C.byref(d)))
+        return bool(on.value), float(ms.value), w.value, d.value
+
+    def stream_last_limiter(self):
+        """(max_reduction, shaped_samples) of the last chunk call with the stream limiter, one entry per utterance / slot,
+        over the samples that call delivered (pe_stream_last_limiter); empty when it ran without the limiter."""
+        n = C.c_int32()
+        self._check(self._lib.pe_stream_last_limiter(self._h, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        r, c = np.zeros(m, np.float32), np.zeros(m, np.int32)
+        self._check(self._lib.pe_stream_last_limiter(self._h, r.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     c.ctypes.data_as(C.POINTER(C.c_int32)), m, C.byref(n)))
+        return r[:n.value], c[:n.value]
 
     @property
     def stream_loudness(self):
@@ -766,6 +808,32 @@ class Engine:
             float(ceiling_db), prior, int(ramp_samples), L.ctypes.data_as(fp), g0.ctypes.data_as(fp), g1.ctypes.data_as(fp),
             f.ctypes.data_as(ip), pcm.ctypes.data_as(C.POINTER(C.c_int16))))
         return L, g0, g1, f, [pcm[b, :len(r)].copy() for b, r in enumerate(rows)]
+
+    def debug_stream_limiter(self, rows, fs: int, chunks, target_lufs: float = -23.0, ceiling_db: float = -1.0,
+                             prior_lufs=None, ramp_samples: int = 0, window_ms: float = 5.0):
+        """Test hook (pe_debug_stream_limiter): ``debug_stream_loudness`` with the stream limiter on; a row ends with its
+        last chunk of length > 0. Returns (lufs, g0, g1, flags, delivered), each [n_chunks][rows], then per row e (float32
+        per stream sample) and the int16 in delivery order (lists; what no call delivered is NaN / zero)."""
+        B = len(rows)
+        ch = np.ascontiguousarray(np.asarray(chunks, np.int32).reshape(-1, B))
+        stride = max(1, max(len(r) for r in rows))
+        x = np.zeros((B, stride), np.float32)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.float32)
+        K = ch.shape[0]
+        L, g0, g1 = (np.zeros((K, B), np.float32) for _ in range(3))
+        f, dl = np.zeros((K, B), np.int32), np.zeros((K, B), np.int32)
+        env = np.full((B, stride), np.nan, np.float32)
+        pcm = np.zeros((B, stride), np.int16)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        prior = float("nan") if prior_lufs is None else float(prior_lufs)
+        self._check(self._lib.pe_debug_stream_limiter(
+            self._h, x.ctypes.data_as(fp), B, stride, int(fs), ch.ctypes.data_as(ip), K, float(target_lufs),
+            float(ceiling_db), prior, int(ramp_samples), float(window_ms), L.ctypes.data_as(fp), g0.ctypes.data_as(fp),
+            g1.ctypes.data_as(fp), f.ctypes.data_as(ip), dl.ctypes.data_as(ip), env.ctypes.data_as(fp),
+            pcm.ctypes.data_as(C.POINTER(C.c_int16))))
+        return (L, g0, g1, f, dl, [env[b, :len(r)].copy() for b, r in enumerate(rows)],
+                [pcm[b, :len(r)].copy() for b, r in enumerate(rows)])
 
     def _rates(self):
         nat, out, k = C.c_int32(), C.c_int32(), C.c_int32()
@@ -999,7 +1067,8 @@ class StreamPool:
 
     def next(self, chunk_frames: int = 45, per_slot=None, want_audio: bool = True) -> dict:
         """The next chunk of every listener, one batched vocoder pass: ``{slot: (float chunk or None, int16 chunk)}`` for the
-        slots that got samples -- empty when no slot has frames left. ``per_slot``: ``{slot: frames}`` (or an array of
+        slots that got samples -- empty when no slot has frames left (with the stream limiter also when every listener only
+        held samples back: ask ``frames_done`` / ``free_slots``). ``per_slot``: ``{slot: frames}`` (or an array of
         ``slots`` entries, 0 = default) overriding ``chunk_frames``, e.g. a short first chunk for a newcomer."""
         eng, S = self._eng, self.slots
         ps = None
