@@ -74,9 +74,14 @@ tests/cpp/test_seeds_emu: tests/cpp/test_seeds.cpp $(EMULIB) include/piper.hpp i
 # SynthesisConfig::speakerBlend / ::speakerVector through the piper:: API (tests/test_speaker_blend_emu.py)
 tests/cpp/test_speaker_blend_emu: tests/cpp/test_speaker_blend.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
 	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_speaker_blend.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
+# SynthesisConfig::sampleFormat through the piper:: API (tests/test_g711_cpp.py)
+tests/cpp/test_g711: tests/cpp/test_g711.cpp $(LIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_g711.cpp -o $@ -Lpiper_amd -lpiper_hip -Wl,-rpath,'$$ORIGIN/../../piper_amd'
+tests/cpp/test_g711_emu: tests/cpp/test_g711.cpp $(EMULIB) include/piper.hpp include/piper_hip.h
+	g++ -O1 -std=c++17 -Iinclude tests/cpp/test_g711.cpp -o $@ -Ltests/emu -lpiper_hip_emu -Wl,-rpath,'$$ORIGIN/../emu'
 
 clean:
 	rm -rf build $(LIB) $(EMULIB) tests/cpp/test_piper tests/cpp/test_piper_emu tests/cpp/test_loudness tests/cpp/test_loudness_emu \
 	       tests/cpp/test_true_peak tests/cpp/test_true_peak_emu tests/cpp/test_limiter tests/cpp/test_limiter_emu \
-	       tests/cpp/test_seeds_emu tests/cpp/test_speaker_blend_emu
+	       tests/cpp/test_seeds_emu tests/cpp/test_speaker_blend_emu tests/cpp/test_g711 tests/cpp/test_g711_emu
 .PHONY: all emu stamps clean

@@ -82,6 +82,10 @@ struct PhonemizeConfig {
   eSpeakConfig eSpeak;
 };
 
+// What synthesizeEncoded / textToEncodedAudio deliver and textToWavFile writes: 16-bit PCM, or G.711 -- 8-bit mu-law (PCMU)
+// or A-law (PCMA), companded on the GPU from the int16 (piper_hip.h: pe_set_sample_format). The values are PE_FORMAT_*.
+enum SampleFormat { S16 = 0, MuLaw = 1, ALaw = 2 };
+
 struct SynthesisConfig {
   // VITS inference settings
   float noiseScale = 0.667f;
@@ -109,6 +113,11 @@ struct SynthesisConfig {
   bool limiter = false;
   float limiterMs = 5.0f;
   int sampleWidth = 2;  // 16-bit
+  // S16, the default: nothing changes. MuLaw / ALaw: the engine also delivers one G.711 code per sample; synthesizeEncoded
+  // and textToEncodedAudio hand the codes out, textToWavFile writes a G.711 WAV (format tag 7 / 6, 8 bits, a fact chunk).
+  // synthesize / synthesizeBatch / textToAudio deliver their int16 as ever, and sampleWidth stays the int16's. (Beyond the
+  // reference.)
+  SampleFormat sampleFormat = S16;
   int channels = 1;     // mono
 
   // Speaker id from 0 to numSpeakers - 1
@@ -186,6 +195,10 @@ void loadVoice(PiperConfig &config, std::string modelPath, std::string modelConf
 void synthesize(std::vector<PhonemeId> &phonemeIds, SynthesisConfig &synthesisConfig, ModelSession &session,
                 std::vector<int16_t> &audioBuffer, SynthesisResult &result);
 
+// synthesize() for a G.711 sampleFormat: appends one code per sample to codeBuffer. Throws when the format is S16.
+void synthesizeEncoded(std::vector<PhonemeId> &phonemeIds, SynthesisConfig &synthesisConfig, ModelSession &session,
+                       std::vector<uint8_t> &codeBuffer, SynthesisResult &result);
+
 // Extension (not in the reference): several id sequences in ONE device call (pe_synthesize_batch). Every sequence
 // is computed, and peak-normalised to int16, exactly as its own synthesize() call would; audioBuffers[i] receives
 // sequence i. textToAudio uses it for the phrases of a sentence.
@@ -204,6 +217,11 @@ void phonemes_to_ids(const std::vector<Phoneme> &phonemes, const PhonemizeConfig
 // Phonemize text and synthesize audio
 void textToAudio(PiperConfig &config, Voice &voice, std::string text, std::vector<int16_t> &audioBuffer,
                  SynthesisResult &result, const std::function<void()> &audioCallback);
+
+// textToAudio() for a G.711 sampleFormat: the same phrases, groups and callbacks, one code per sample in codeBuffer; sentence
+// and phoneme silences are the law's zero code (0xFF mu-law, 0xD5 A-law). Throws when the format is S16.
+void textToEncodedAudio(PiperConfig &config, Voice &voice, std::string text, std::vector<uint8_t> &codeBuffer,
+                        SynthesisResult &result, const std::function<void()> &audioCallback);
 
 // Phonemize text and synthesize audio to WAV file
 void textToWavFile(PiperConfig &config, Voice &voice, std::string text, std::ostream &audioFile,

@@ -582,6 +582,41 @@ int pe_limiter_window(int32_t fs, float window_ms, int32_t* window_samples, doub
 int pe_debug_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride, const int32_t* valid, int32_t fs, const float* g,
                      float ceiling_db, int32_t kind, float window_ms, float* env_out, int16_t* pcm_out);
 
+/* Sample format of what the handle delivers. PE_FORMAT_S16, the default: int16 and floats, nothing changes.
+ * PE_FORMAT_ULAW / PE_FORMAT_ALAW: every whole-utterance call and every chunk of every kind of stream ALSO delivers one G.711
+ * code (8-bit mu-law, RTP payload type 0, or A-law, payload type 8) per delivered int16 sample, companded on the device and
+ * packed back to back under the same sample_offsets; pe_last_codes hands them out. The int16 and the floats are delivered
+ * exactly as without a format, bit for bit, and pe_result / pe_stream_chunk keep their layouts; a caller that wants the
+ * codes only passes want_pcm = 0 to pe_fetch. The law is that of the ITU-T G.191 software tools, with lin an int16,
+ * >> arithmetic and ~ one's complement:
+ *   mu-law:  a = (lin < 0 ? (~lin) >> 2 : lin >> 2) + 33;  if (a > 0x1FFF) a = 0x1FFF;
+ *            seg = 1; for (i = a >> 6; i; i >>= 1) seg++;
+ *            code = ((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF));  if (lin >= 0) code |= 0x80;
+ *   A-law:   ix = lin < 0 ? (~lin) >> 4 : lin >> 4;
+ *            if (ix > 15) { e = 1; while (ix > 31) { ix >>= 1; e++; }  ix = ix - 16 + (e << 4); }
+ *            if (lin >= 0) ix |= 0x80;   code = ix ^ 0x55;
+ * so code(0) is 0xFF / 0xD5, the byte a caller pads silence with (0x00 is full-scale negative in mu-law). Cost: one launch
+ * more per whole-utterance call and per chunk of a batch stream or pool (pe_run_launches); the one-utterance stream converts
+ * on the host, as it does its int16. A value outside the enum is refused, and so is any change while a stream is live or a
+ * pool is open on the handle, with a message that says which; nothing changes then. The format is part of the graph keys:
+ * switching drops nothing. pe_group_* and pe_coalescer_* keep working on handles with a format set, but do NOT hand out
+ * codes: their results carry int16 only. */
+enum { PE_FORMAT_S16 = 0, PE_FORMAT_ULAW = 1, PE_FORMAT_ALAW = 2 };
+int pe_set_sample_format(pe_engine* e, int32_t format);
+int pe_get_sample_format(pe_engine* e, int32_t* format);
+/* Codes of the last fetched whole-utterance call (which = 0) or of the last chunk of any kind of stream (which = 1):
+ * engine-owned views valid until the next call, row i at codes[sample_offsets[i] .. sample_offsets[i + 1]); *codes == NULL
+ * and *rows == 0 when the format was PE_FORMAT_S16. */
+int pe_last_codes(pe_engine* e, int32_t which, const uint8_t** codes, const int64_t** sample_offsets, int32_t* rows);
+/* Host twins, no engine needed: the law above and its expanders (format PE_FORMAT_ULAW or PE_FORMAT_ALAW). */
+int pe_g711_encode(int32_t format, const int16_t* pcm, uint8_t* codes, int64_t n);
+int pe_g711_decode(int32_t format, const uint8_t* codes, int16_t* pcm, int64_t n);
+/* Test hook: the rows form (flat = 0) or the flat form (flat = 1, batch = 1) of the encoder kernel alone on caller-given int16
+ * rows x[batch][stride], row b holding valid[b] samples; out receives the packed codes: out_capacity bytes are uploaded first
+ * and read back whole, so untouched bytes come back as given. */
+int pe_debug_g711(pe_engine* e, int32_t format, int32_t flat, const int16_t* x, int32_t batch, int64_t stride,
+                  const int32_t* valid, uint8_t* out, int64_t out_capacity);
+
 /* Test hook: the resampling kernel with the engine's current rate pair on caller-supplied rows. x[batch][stride] (host): row
  * b holds valid[b] native samples of an utterance, the first of which has native index origin[b]; everything outside them
  * counts as zero. out[b][0 .. count[b]) receives outputs n0[b] .. n0[b] + count[b] - 1 of that utterance (out_stride floats

@@ -31,6 +31,7 @@ SYMBOLS = [
     "pe_set_loudness", "pe_get_loudness", "pe_last_loudness", "pe_loudness_filter", "pe_debug_loudness",
     "pe_set_loudness_ceiling", "pe_get_loudness_ceiling", "pe_last_true_peak", "pe_true_peak_filter", "pe_debug_true_peak",
     "pe_set_loudness_limiter", "pe_get_loudness_limiter", "pe_last_limiter", "pe_limiter_window", "pe_debug_limiter",
+    "pe_set_sample_format", "pe_get_sample_format", "pe_last_codes", "pe_g711_encode", "pe_g711_decode", "pe_debug_g711",
     "pe_set_seed", "pe_profile_enable", "pe_profile_reset", "pe_profile_rows", "pe_profile_get", "pe_profile_bytes",
     "pe_stream", "pe_debug_tensor", "pe_debug_randn", "pe_rng_calls", "pe_run_launches", "pe_speculation_stats", "pe_warmup", "pe_graph_stats", "pe_xcc_pattern", "pe_device_pci_bus_id", "pe_policy_describe", "pe_last_error", "pe_destroy",
     "pe_group_create", "pe_group_broadcast_path", "pe_group_size", "pe_group_engine", "pe_group_synthesize_batch", "pe_group_synthesize_batch_scaled",
@@ -162,6 +163,13 @@ def bind(path: str) -> C.CDLL:
     lib.pe_limiter_window.argtypes = [C.c_int32, C.c_float, i32p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
     lib.pe_debug_limiter.argtypes = [vp, f32p, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, C.c_float, C.c_int32, C.c_float, f32p,
                                      C.POINTER(C.c_int16)]
+    u8p, i16p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
+    lib.pe_set_sample_format.argtypes = [vp, C.c_int32]
+    lib.pe_get_sample_format.argtypes = [vp, i32p]
+    lib.pe_last_codes.argtypes = [vp, C.c_int32, C.POINTER(u8p), C.POINTER(i64p), i32p]
+    lib.pe_g711_encode.argtypes = [C.c_int32, i16p, u8p, C.c_int64]
+    lib.pe_g711_decode.argtypes = [C.c_int32, u8p, i16p, C.c_int64]
+    lib.pe_debug_g711.argtypes = [vp, C.c_int32, C.c_int32, i16p, C.c_int32, C.c_int64, i32p, u8p, C.c_int64]
     lib.pe_set_seed.argtypes = [vp, C.c_uint64]
     lib.pe_set_seed.restype = None
     lib.pe_profile_enable.argtypes = [vp, C.c_int]

@@ -68,6 +68,7 @@ void Engine::free_all() {
   rs_coef_.reset(); raudio_.reset(); rpcm_.reset(); rs_dev_.reset(); rs_host_.reset();
   ld_coef_.reset(); ld_seg_.reset(); ld_dev_.reset(); ld_ctl_.reset(); tp_coef_.reset(); tp_words_.reset();
   lim_h_.reset(); lim_rep_.reset(); lim_host_.reset(); lim_v_.reset(); lim_z_.reset();
+  codes_.reset(); h_codes_.reset();
   rs_cap_ = ld_cap_ = lim_cap_ = 0;                    // (the row blocks the capacities spoke of are gone)
   if (ev0_) hipEventDestroy(ev0_);
   if (ev1_) hipEventDestroy(ev1_);
@@ -315,6 +316,7 @@ void Engine::ensure_stage_b(int Fmax, int batch) {
   }
   if (rs_on_) ensure_resample();
   if (ld_on_) ensure_loudness();
+  if (fmt_ != G711_S16) ensure_g711();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -664,7 +666,7 @@ void Engine::run() {
       frames_h_[b] = pol_.spec_expect ? std::min(Fg_, std::max(1, (int)std::ceil(last_ratio_ * (spec_rel(b) * (float)tlens_h_[b])))) : Fg_;
     lens_b_ = d_framesc_;
     // (the target-loudness setting swaps the launches behind the generator: its graphs live side by side with the others)
-    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key(), seed_key(), blend_key());
+    snprintf(key, sizeof(key), "C|%d|%d|%d|%d|%d|%d%s%s%s%s", B, Tg_, Ts_, (int)have_noise_w_, Fs_, Fg_, loud_key(), fmt_key(), seed_key(), blend_key());
     fold_dur_ = Tg_ <= REG_MAXT;              // (part of what graph 'C' is: a fixed function of its key)
     try {
       run_stage('C', key);
@@ -688,10 +690,11 @@ void Engine::run() {
   lens_b_ = d_frames_;
   if (have_noise_z_) {
     const long l0 = g_launches;
+    (void)fmt_key();                           // (no key here: the run's format is noted all the same)
     issue_stage_b();                           // host-injected noise (tests): not graph-captured
     run_launches_ += g_launches - l0;
   } else {
-    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s", B, Fg_, Fs_, Ts_, loud_key(), seed_key());
+    snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s%s", B, Fg_, Fs_, Ts_, loud_key(), fmt_key(), seed_key());
     run_stage('B', key);
   }
 }
@@ -751,7 +754,7 @@ bool Engine::finish_run() {
   Fg_ = std::min(frame_bucket(Fmax_), Fs_);
   lens_b_ = d_frames_;
   char key[160];
-  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s", B_, Fg_, Fs_, Ts_, loud_key(), seed_key());
+  snprintf(key, sizeof(key), "B|%d|%d|%d|%d%s%s%s", B_, Fg_, Fs_, Ts_, loud_key(), fmt_key(), seed_key());
   run_stage('B', key);
   return false;
 }
@@ -768,17 +771,28 @@ void Engine::download(bool want_audio, bool want_pcm) {
   // (read where a copy is enqueued, not here: a missed guess re-sizes the workspace, and the buffers move with it)
   auto asrc = [&]() -> const float* { return rs_on_ ? raudio_.get() : audio_; };
   auto psrc = [&]() -> const int16_t* { return rs_on_ ? rpcm_.get() : pcm_; };
+  // the G.711 codes of a run with a format: packed on the device by g711_kernel, one copy of the call's total
+  const int fmt = run_fmt_;
+  auto codes = [&](size_t n) {
+    if (fmt == G711_S16 || !codes_) return;
+    grow_pinned(h_codes_, std::max<size_t>(n, 1));
+    n = std::min(n, codes_.size());
+    if (n > 0) PE_HIP(hipMemcpyAsync(h_codes_.get(), codes_.get(), n, hipMemcpyDeviceToHost, stream_));
+  };
+  lc_rows_ = 0;
   pcm_zc_live_ = false;
-  if (spec_pending_ && B_ == 1 && (want_audio || want_pcm)) {
+  if (spec_pending_ && B_ == 1 && (want_audio || want_pcm || fmt != G711_S16)) {
     // one utterance, speculative run: the copies are enqueued for the guessed length (>= the real one when the guess
     // holds) behind stage B, so that one synchronisation ends the whole call; the host view is trimmed afterwards
     const size_t n = (size_t)out_samples((int64_t)spec_fg_ * hop_);
     grow(n);
     if (want_audio) PE_HIP(hipMemcpyAsync(h_audio_.get(), asrc(), n * sizeof(float), hipMemcpyDeviceToHost, stream_));
     if (want_pcm && !zc) PE_HIP(hipMemcpyAsync(h_pcm_.get(), psrc(), n * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
+    codes(n);
     lim_enqueue_report();
     if (finish_run()) {                        // synchronises; sample_off_ now holds the real length
       pcm_zc_live_ = zc;
+      lc_rows_ = fmt != G711_S16 ? B_ : 0;
       loud_collect();
       return;
     }
@@ -798,9 +812,11 @@ void Engine::download(bool want_audio, bool want_pcm) {
       PE_HIP(hipMemcpyAsync(h_pcm_.get() + sample_off_[b], psrc() + (size_t)b * So_,
                             (size_t)(sample_off_[b + 1] - sample_off_[b]) * sizeof(int16_t), hipMemcpyDeviceToHost,
                             stream_));
+  codes(total);
   lim_enqueue_report();
   PE_HIP(hipStreamSynchronize(stream_));
   pcm_zc_live_ = zc;
+  lc_rows_ = fmt != G711_S16 ? B_ : 0;
   loud_collect();
 }
 

@@ -228,6 +228,25 @@ class Engine {
   void debug_loudness(const float* x, int batch, int64_t stride, const int32_t* valid, int fs, float target, float ceiling_db,
                       float* lufs, float* scale, int32_t* flags);
 
+  // The sample format of what is delivered (kernels/g711.h). G711_S16, the default: int16 and floats, as ever.
+  // G711_ULAW / G711_ALAW: every whole-utterance call and every chunk of every kind of stream ALSO delivers one G.711 code
+  // per delivered int16 sample, packed under the same sample offsets (last_codes); the int16 and the floats stay bit for bit
+  // what they are without it. Whole utterances: g711_kernel is the last launch of the delivery stage on every route, one
+  // launch more per call, the codes fetched by one copy in download. Batch stream and pool: the chunk's int16 go to a device
+  // staging buffer and reach the host by one copy, g711_flat_kernel behind the stage writes the codes, one launch more per
+  // chunk. The one-utterance stream converts on the host, as it does its int16. Throws, and changes nothing, for an unknown
+  // value, or while a stream is live / a pool is open on the handle (set_output_rate's rule). The format is part of the
+  // 'B' and 'C' graph keys: nothing is dropped, the sets of graphs stay cached side by side.
+  void set_sample_format(int format);
+  int sample_format() const { return fmt_; }
+  // which = 0: the codes of the last fetched whole-utterance call; 1: of the last chunk of any kind of stream. Returns the
+  // rows (offsets[rows + 1]); 0, with null views, when that call ran with G711_S16. Views are valid until the next call.
+  int last_codes(int which, const uint8_t** codes, const int64_t** offsets);
+  // test hook: the rows form (x[batch][stride], row b holding valid[b] samples) or the flat form (batch 1) of the encoder
+  // alone; out[out_capacity] is uploaded, written by the kernel and read back whole
+  void debug_g711(int format, bool flat, const int16_t* x, int batch, int64_t stride, const int32_t* valid, uint8_t* out,
+                  int64_t out_capacity);
+
   // The int16 level of stream chunks (kernels/params.h: GAIN_*). GAIN_CHUNK, the default, is the
   // reference's rule: every chunk scaled by 32767 / max(0.01, its own peak). GAIN_FIXED: 32767 / max(0.01, peak) for every
   // sample. GAIN_RUNNING: every stream -- the one-utterance stream, a batch-stream row, a pool slot -- carries a running
@@ -739,6 +758,9 @@ class Engine {
     std::vector<int32_t> pos;                      // frames delivered per row; its size is the number of rows
     std::vector<int64_t> off;                      // sample offsets of the current chunk
     PinBuf<int16_t> pcm; PinBuf<float> audio;      // pinned host output of the current chunk
+    // with a G.711 format: the device staging of the chunk's packed int16 (the stage's output pointer), the codes on the
+    // device and their pinned host copy; grown with the chunks, never inside a graph (the pointers are data)
+    DevBuf<int16_t> pcm_dev; DevBuf<uint8_t> codes_dev; PinBuf<uint8_t> codes;
     int wg = 0;                                    // window bucket of the current chunk
     // what the stage reads the rows from: the latents [row][C][src_cs] and the decoder's conditioning rows (null: cond_)
     const float* src = nullptr; long src_bs = 0; int src_cs = 0;
@@ -918,6 +940,23 @@ class Engine {
   // `peaks`); max_n bounds every row's length (grid)
   void issue_loudness(int B, const float* x, long x_bs, const int* lens, int len_mul, const unsigned* peaks, long max_n,
                       int16_t* pcm, int16_t* zc, double samples);
+  // sample format. The codes of a whole-utterance call, packed, [capB_B_ * So_] on the device (an allocation of its own; its
+  // address is a kernel argument inside the graphs of its format, so growing it drops the graphs) and their pinned host copy;
+  // run_fmt_: the format of the run that is fetched next, noted where its graph key is formed.
+  int fmt_ = G711_S16;
+  mutable int run_fmt_ = G711_S16;
+  DevBuf<uint8_t> codes_; PinBuf<uint8_t> h_codes_;
+  int lc_rows_ = 0;                             // rows of the last fetched call's codes (0: s16)
+  std::vector<uint8_t> s_codes_;                // one-utterance stream: the chunk's codes (host conversion)
+  int64_t s_codes_off_[2] = {0, 0};
+  const uint8_t* lc_s_codes_ = nullptr; const int64_t* lc_s_off_ = nullptr; int lc_s_rows_ = 0;      // last chunk of any stream
+  const char* fmt_key() const {
+    run_fmt_ = fmt_;
+    return fmt_ == G711_ULAW ? "|u" : (fmt_ == G711_ALAW ? "|a" : "");
+  }
+  void ensure_g711();                           // after ensure_stage_b sized the workspace (and So_)
+  // the encoder on B delivered int16 rows (stride p_bs, lengths lens[b] * len_mul, max_n bounds them): the call's last launch
+  void issue_g711(int B, const int16_t* pcm, long p_bs, const int* lens, int len_mul, long max_n, double samples);
   float* audio_ = nullptr;
   int16_t* pcm_ = nullptr;
   unsigned* absmax_ = nullptr;

@@ -709,6 +709,53 @@ void Engine::issue_limiter_tail(const LimTail& t, int B, long max_n, double samp
 #undef PE_TAIL_LAUNCH
 
 // ------------------------------------------------------------------------------------------------
+// sample format: G.711 codes of the delivered int16
+// ------------------------------------------------------------------------------------------------
+
+void Engine::set_sample_format(int format) {
+  EntryLock entry_lock;
+  if (format != G711_S16 && format != G711_ULAW && format != G711_ALAW)
+    throw std::runtime_error("unknown sample format " + std::to_string(format) + " (0: s16, 1: ulaw, 2: alaw)");
+  bool live = s_active_ && s_pos_ < s_frames_;
+  if (sb_active_)
+    for (int b = 0; b < B_ && b < (int)batch_rows_.pos.size(); ++b) live = live || batch_rows_.pos[b] < frames_h_[b];
+  if (live || sp_slots_)
+    throw std::runtime_error(std::string("the sample format cannot change while a ") +
+                             (sp_slots_ ? "stream pool is open" : "stream is live") + " on this handle");
+  if (format == fmt_) return;
+  PE_HIP(hipSetDevice(device_));
+  finish_run();                                        // (a speculative run still in flight settles first)
+  // the format picks one launch and is part of the graph keys: nothing is dropped, streams that ended are not touched
+  fmt_ = format;
+}
+
+// The packed codes of a whole-utterance call: one byte per delivered sample of the batch capacity. Called at the end of
+// ensure_stage_b, which has set So_; a buffer that grows is inside the graphs of its format.
+void Engine::ensure_g711() {
+  const size_t need = std::max<size_t>(capB_B_ * (size_t)So_, 16);
+  if (codes_ && codes_.size() >= need) return;
+  side_alloc(codes_, need, true, FILL_POISON, "G.711 codes");
+}
+
+void Engine::issue_g711(int B, const int16_t* pcm, long p_bs, const int* lens, int len_mul, long max_n, double samples) {
+  if (!codes_ || codes_.size() < (size_t)B * (size_t)p_bs) throw std::runtime_error("G.711 code buffer is not sized for this call");
+  max_n = std::max<long>(1, std::min<long>(max_n, p_bs));
+  PE_LAUNCH_KB("g711_kernel", 3.0 * samples,
+               launch::g711_rows(stream_, B, max_n, lens, len_mul, pcm, p_bs, codes_.get(), (long)codes_.size(), fmt_));
+}
+
+int Engine::last_codes(int which, const uint8_t** codes, const int64_t** offsets) {
+  EntryLock entry_lock;
+  if (which != 0 && which != 1) throw std::runtime_error("pe_last_codes: which must be 0 (whole utterances) or 1 (stream chunk)");
+  const int rows = which == 0 ? lc_rows_ : lc_s_rows_;
+  static const uint8_t nothing[1] = {0};                 // (a chunk call that delivered nothing: rows of no bytes, not NULL)
+  const uint8_t* view = which == 0 ? h_codes_.get() : lc_s_codes_;
+  if (codes) *codes = rows ? (view ? view : nothing) : nullptr;
+  if (offsets) *offsets = rows ? (which == 0 ? sample_off_.data() : lc_s_off_) : nullptr;
+  return rows;
+}
+
+// ------------------------------------------------------------------------------------------------
 // test hooks: one kernel family alone on caller-given rows
 // ------------------------------------------------------------------------------------------------
 
@@ -811,6 +858,40 @@ void Engine::debug_limiter(const float* x, int batch, int64_t stride, const int3
     issue_limiter_tail(t, batch, std::max(maxn, 1), 0.0, false);
     rows_to_host(env, stride, denv.get(), xs, batch);
     rows_to_host(pcm, stride, dpcm.get(), xs, batch);
+    PE_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)
+    throw;
+  }
+}
+
+void Engine::debug_g711(int format, bool flat, const int16_t* x, int batch, int64_t stride, const int32_t* valid, uint8_t* out,
+                        int64_t out_capacity) {
+  EntryLock entry_lock;
+  if (format != G711_ULAW && format != G711_ALAW) throw std::runtime_error("G.711 hook: format must be 1 (ulaw) or 2 (alaw)");
+  if (batch < 1 || batch > 4096) throw std::runtime_error("batch size must be in [1, 4096]");
+  if (flat && batch != 1) throw std::runtime_error("G.711 hook: the flat form takes one row");
+  if (!x || !valid || !out) throw std::runtime_error("null argument");
+  if (stride < 1 || stride > ((int64_t)1 << 28)) throw std::runtime_error("row stride outside [1, 2^28]");
+  if (out_capacity < 1 || out_capacity > ((int64_t)1 << 32)) throw std::runtime_error("out_capacity outside [1, 2^32]");
+  const int maxn = check_row_lengths(valid, batch, stride);
+  PE_HIP(hipSetDevice(device_));
+  finish_run();
+  const long xs = (long)((stride + 3) & ~(int64_t)3);
+  DevBuf<int16_t> dx;
+  DevBuf<int> dval;
+  DevBuf<uint8_t> dout;
+  try {
+    dx.grow((size_t)batch * std::max<long>(xs, 8));
+    dval.grow((size_t)batch);
+    dout.grow((size_t)out_capacity);
+    rows_to_device(dx.get(), xs, x, batch, stride);
+    PE_HIP(hipMemcpyAsync(dval.get(), valid, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipMemcpyAsync(dout.get(), out, (size_t)out_capacity, hipMemcpyHostToDevice, stream_));
+    PE_HIP(hipStreamSynchronize(stream_));             // (the staging arrays are pageable)
+    if (flat) launch::g711_flat(stream_, dx.get(), std::min<long>(valid[0], (long)out_capacity), dout.get(), format);
+    else launch::g711_rows(stream_, batch, std::max(maxn, 1), dval.get(), 1, dx.get(), xs, dout.get(), (long)out_capacity, format);
+    PE_HIP(hipMemcpyAsync(out, dout.get(), (size_t)out_capacity, hipMemcpyDeviceToHost, stream_));
     PE_HIP(hipStreamSynchronize(stream_));
   } catch (...) {
     hipStreamSynchronize(stream_);                     // (nothing is freed under a running kernel)

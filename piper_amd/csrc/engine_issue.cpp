@@ -640,10 +640,13 @@ void Engine::issue_decoder(const float* zsrc, const int* lens, int Fmax, double 
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * ((double)rs_L_ / rs_M_) * (4.0 + 2.0 + (zc ? 2.0 : 0.0)),
                    launch::pcm16(dim3((unsigned)((max_out + 255) / 256), B), stream_, raudio_.get(), So_, rs_peaks(), rs_counts(), 1,
                                  rpcm_.get(), So_, zc));
+      if (fmt_ != G711_S16) issue_g711(B, rpcm_.get(), So_, rs_counts(), 1, max_out, fsum * hop_ * ((double)rs_L_ / rs_M_));
     } else if (with_pcm16 && ld_on_ && !zero_absmax)
       issue_loudness(B, audio_, Ss_, lens, hop_, absmax_, Lmax, pcm_, zc, fsum * hop_);
     else if (with_pcm16)
       PE_LAUNCH_KB("pcm16_kernel", fsum * hop_ * (4.0 + 2.0 + (zc ? 2.0 : 0.0)), launch::pcm16(dim3((Lmax + 255) / 256, B), stream_, audio_, Ss_, absmax_, lens, hop_, pcm_, Ss_, zc));
+    // the sample format's codes, from the int16 rows whichever kernel above wrote them: the call's last launch
+    if (with_pcm16 && !zero_absmax && !rs_on_ && fmt_ != G711_S16) issue_g711(B, pcm_, Ss_, lens, hop_, Lmax, fsum * hop_);
     prof_end(4, tail_done ? 0.0 : 2.0 * fsum * hop_ * post_cin_ * K);
   }
 }

@@ -3,6 +3,7 @@
 #include "engine_internal.h"
 #include "kernels/stream_loudness_rule.h"
 #include "kernels/stream_limiter_rule.h"
+#include "kernels/g711_law.h"
 
 namespace pe {
 
@@ -96,6 +97,7 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
       }
     }
     s_active_ = false;
+    lc_s_rows_ = 0; lc_s_codes_ = nullptr; lc_s_off_ = nullptr;
     if (nsamples) *nsamples = 0;
     return false;
   }
@@ -210,6 +212,14 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
       s_pcm_[i] = (int16_t)v;
     }
   }
+  // sample format: the host twin of the encoder on what this call hands out
+  lc_s_rows_ = 0; lc_s_codes_ = nullptr; lc_s_off_ = nullptr;
+  if (fmt_ != G711_S16) {
+    s_codes_.resize(std::max<size_t>(nout, 1));
+    for (size_t i = 0; i < nout; ++i) s_codes_[i] = (uint8_t)g711_code(fmt_, s_pcm_[i]);
+    s_codes_off_[0] = 0; s_codes_off_[1] = (int64_t)nout;
+    lc_s_rows_ = 1; lc_s_codes_ = s_codes_.data(); lc_s_off_ = s_codes_off_;
+  }
   lg_n_ = 1; lg_dev_peaks_ = nullptr; lg_lazy_ = false;
   lg_gain_.assign(1, sc);
   lg_peak_.assign(1, level);
@@ -226,6 +236,8 @@ bool Engine::stream_next(int chunk_frames, const float** audio, const int16_t** 
 
 void Engine::rows_free(ChunkRows& r) {
   r.host.reset(); r.dev.reset(); r.pcm.reset(); r.audio.reset(); r.gctl.reset(); r.gdev.reset();
+  r.pcm_dev.reset(); r.codes_dev.reset(); r.codes.reset();
+  lc_s_rows_ = 0; lc_s_codes_ = nullptr; lc_s_off_ = nullptr;      // (a chunk's codes not yet read pointed into r.codes)
   r.lctl.reset(); r.ldev.reset(); r.lseg.reset(); r.ltail.reset();
   r.lnseg = r.lW = 0;
   r.mctl.reset(); r.mreph.reset(); r.mrep.reset(); r.mstail.reset();
@@ -375,6 +387,11 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   out.pcm = r.pcm.get();
   out.audio = nullptr;
   lsm_n_ = 0;
+  // sample format: the chunk's codes follow what is delivered, under the same offsets (a call that runs nothing: none)
+  const bool law = fmt_ != G711_S16;
+  lc_s_rows_ = law ? n : 0;
+  lc_s_off_ = law ? r.off.data() : nullptr;
+  lc_s_codes_ = nullptr;
   if (!any) {                                          // no row has frames left (a call may deliver nothing while rows go on)
     gain_report_idle(r.gctl.get(), cap, n);
     if (gain_mode_ == GAIN_LOUDNESS) sl_collect(r, n, false);
@@ -383,7 +400,19 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
   }
   grow_pinned(r.pcm, (size_t)std::max<int64_t>(total, 1));
   if (want_audio) grow_pinned(r.audio, (size_t)std::max<int64_t>(total, 1));
-  void* ptrs[2] = {r.pcm.get(), want_audio ? r.audio.get() : nullptr};
+  if (law) {
+    // the stage's int16 go to a device staging buffer of the packed layout, which the encoder reads behind the stage; the
+    // buffers' addresses are data of the pinned block, not part of a graph, and the previous chunk has been waited for
+    const size_t want = ((size_t)std::max<int64_t>(total, 1) + 15) & ~(size_t)15;
+    if (!r.pcm_dev || !r.codes_dev || r.pcm_dev.size() < want || r.codes_dev.size() < want) {
+      r.pcm_dev.reset(); r.codes_dev.reset();
+      side_alloc(r.pcm_dev, want + want / 2, false, FILL_POISON, "stream chunk staging");
+      side_alloc(r.codes_dev, want + want / 2, false, FILL_POISON, "stream chunk codes");
+    }
+    grow_pinned(r.codes, want);
+    lc_s_codes_ = r.codes.get();
+  }
+  void* ptrs[2] = {law ? (void*)r.pcm_dev.get() : (void*)r.pcm.get(), want_audio ? r.audio.get() : nullptr};
   memcpy(st + sb_o_ptrs(cap), ptrs, sizeof(ptrs));
   // the window bucket: by the largest step among the rows that deliver
   r.wg = std::min(rup(cmax + 2 * hf, 32), Fs_);
@@ -404,6 +433,14 @@ bool Engine::rows_next(ChunkRows& r, const int32_t* frames, const int32_t* live,
     else snprintf(key, sizeof(key), "%c|%d|%d|%d|g%d", r.stage, n, r.wg, Fs_, gain_mode_);
   }
   run_stage(r.stage, key);
+  if (law) {
+    // the same int16 bytes as without a format, through the staging buffer; then the flat encoder on the `total` delivered
+    const long l0 = g_launches;
+    if (total > 0) PE_HIP(hipMemcpyAsync(r.pcm.get(), r.pcm_dev.get(), (size_t)total * sizeof(int16_t), hipMemcpyDeviceToHost, stream_));
+    PE_LAUNCH_KB("g711_kernel", 3.0 * (double)total, launch::g711_flat(stream_, r.pcm_dev.get(), (long)total, r.codes_dev.get(), fmt_));
+    run_launches_ += g_launches - l0;
+    if (total > 0) PE_HIP(hipMemcpyAsync(r.codes.get(), r.codes_dev.get(), (size_t)total, hipMemcpyDeviceToHost, stream_));
+  }
   if (lim) PE_HIP(hipMemcpyAsync(r.mreph.get(), r.mrep.get(), (size_t)slm_rep_words(cap) * sizeof(int), hipMemcpyDeviceToHost, stream_));
   PE_HIP(hipStreamSynchronize(stream_));
   // (which rows moved their state is decided by the chunks, not by what was handed out)

@@ -125,6 +125,12 @@ void limiter_true(dim3 grid, hipStream_t stream, const LimP& p);
 void pcm16_trim(dim3 grid, hipStream_t stream, const TrimP& p);
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
                 int len_mul, short* pcm, long p_bs, short* host);
+// G.711 codes of the delivered int16 (g711.h; law = G711_ULAW / G711_ALAW). Rows form: grid = (spans of G711_SPAN samples
+// of max_n, rows), row b = lens[b] * len_mul int16 at pcm + b * p_bs, codes packed back to back into out[0, out_cap).
+// Flat form: n contiguous int16 at a 16-byte aligned base -> n codes (n == 0: one idle workgroup, so that a chunk's launch count does not depend on what it delivers)
+void g711_rows(hipStream_t stream, int B, long max_n, const int* lens, int len_mul, const short* pcm, long p_bs,
+               unsigned char* out, long out_cap, int law);
+void g711_flat(hipStream_t stream, const short* pcm, long n, unsigned char* out, int law);
 
 }  // namespace launch
 }  // namespace pe

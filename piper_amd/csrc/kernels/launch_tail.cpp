@@ -9,6 +9,9 @@
 #include "limiter.h"
 #include "stream_loudness.h"
 #include "stream_limiter.h"
+#include "g711.h"
+
+#include <algorithm>
 
 namespace pe {
 namespace launch {
@@ -146,6 +149,17 @@ void pcm16_trim(dim3 grid, hipStream_t stream, const TrimP& p) {
 void pcm16_gain(dim3 grid, hipStream_t stream, const float* audio, long a_bs, const int* gq, int gcap, const int* lens,
                 int len_mul, short* pcm, long p_bs, short* host) {
   PE_LAUNCH(pcm16_gain_kernel, grid, dim3(PCM16_TPB), 0, stream, lens, len_mul, gq, gcap, audio, a_bs, pcm, p_bs, host);
+}
+
+void g711_rows(hipStream_t stream, int B, long max_n, const int* lens, int len_mul, const short* pcm, long p_bs,
+               unsigned char* out, long out_cap, int law) {
+  const unsigned spans = (unsigned)((std::max<long>(max_n, 1) + G711_SPAN - 1) / G711_SPAN);
+  PE_LAUNCH(g711_kernel, dim3(spans, B), dim3(G711_TPB), 0, stream, lens, len_mul, pcm, p_bs, out, out_cap, law);
+}
+
+void g711_flat(hipStream_t stream, const short* pcm, long n, unsigned char* out, int law) {
+  const unsigned spans = (unsigned)((std::max<long>(n, 1) + G711_SPAN - 1) / G711_SPAN);
+  PE_LAUNCH(g711_flat_kernel, dim3(spans), dim3(G711_TPB), 0, stream, pcm, n, out, law);
 }
 
 }  // namespace launch

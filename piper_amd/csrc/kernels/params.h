@@ -488,6 +488,11 @@ struct SlmP {
   float* env; long e_bs;                       // test hook: e[b][stream sample], or null
 };
 
+// ---- G.711 companding of the delivered int16 (g711.h: g711_kernel, g711_flat_kernel; pe_set_sample_format).
+// The format is part of the 'B' and 'C' graph keys; a stream chunk's encoder is launched outside the window stage's graph.
+enum { G711_S16 = 0, G711_ULAW = 1, G711_ALAW = 2 };
+static constexpr int G711_TPB = 256, G711_SPAN = 8 * G711_TPB;      // threads of 8 samples: samples per workgroup
+
 // ---- fused MRF stage (mrf.h)
 enum { MRF_RES = 1, MRF_KEEP = 2, MRF_FINAL = 4, MRF_INIT = 8, MRF_RESTAGE = 16 };
 struct MrfPhase {        // one conv of one resblock chain; 12 ints wide (the kernel copies the table to LDS as ints)

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "kernels/g711_law.h"
 
 struct pe_engine {
   pe::Engine* eng;
@@ -879,6 +880,55 @@ int pe_debug_limiter(pe_engine* e, const float* x, int32_t batch, int64_t stride
   return guard([&] {
     if (!e) throw std::runtime_error("null engine");
     e->eng->debug_limiter(x, batch, stride, valid, fs, g, ceiling_db, kind, window_ms, env_out, pcm_out);
+  });
+}
+
+int pe_set_sample_format(pe_engine* e, int32_t format) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->set_sample_format(format);
+  });
+}
+
+int pe_get_sample_format(pe_engine* e, int32_t* format) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    if (format) *format = e->eng->sample_format();
+  });
+}
+
+int pe_last_codes(pe_engine* e, int32_t which, const uint8_t** codes, const int64_t** sample_offsets, int32_t* rows) {
+  return guard([&] {
+    if (!e || !rows) throw std::runtime_error("null argument");
+    *rows = e->eng->last_codes(which, codes, sample_offsets);
+  });
+}
+
+static void g711_check(int32_t format, const void* a, const void* b, int64_t n) {
+  if (format != PE_FORMAT_ULAW && format != PE_FORMAT_ALAW) throw std::runtime_error("G.711 format must be 1 (ulaw) or 2 (alaw)");
+  if (n < 0 || (n > 0 && (!a || !b))) throw std::runtime_error("null argument");
+}
+
+int pe_g711_encode(int32_t format, const int16_t* pcm, uint8_t* codes, int64_t n) {
+  return guard([&] {
+    g711_check(format, pcm, codes, n);
+    for (int64_t i = 0; i < n; ++i) codes[i] = (uint8_t)pe::g711_code(format, pcm[i]);
+  });
+}
+
+int pe_g711_decode(int32_t format, const uint8_t* codes, int16_t* pcm, int64_t n) {
+  return guard([&] {
+    g711_check(format, codes, pcm, n);
+    for (int64_t i = 0; i < n; ++i)
+      pcm[i] = (int16_t)(format == PE_FORMAT_ALAW ? pe::g711_alaw_expand(codes[i]) : pe::g711_ulaw_expand(codes[i]));
+  });
+}
+
+int pe_debug_g711(pe_engine* e, int32_t format, int32_t flat, const int16_t* x, int32_t batch, int64_t stride,
+                  const int32_t* valid, uint8_t* out, int64_t out_capacity) {
+  return guard([&] {
+    if (!e) throw std::runtime_error("null engine");
+    e->eng->debug_g711(format, flat != 0, x, batch, stride, valid, out, out_capacity);
   });
 }
 

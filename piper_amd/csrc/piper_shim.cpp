@@ -347,6 +347,10 @@ static int delivered_rate(const SynthesisConfig& sc) {
   return sc.outputSampleRate > 0 ? sc.outputSampleRate : sc.sampleRate;
 }
 static void apply_output_rate(const SynthesisConfig& sc, ModelSession& session) {
+  // SynthesisConfig::sampleFormat: pe_set_sample_format only when the engine is not already there
+  int32_t fmt = PE_FORMAT_S16;
+  check(pe_get_sample_format(session.engine, &fmt));
+  if (fmt != (int32_t)sc.sampleFormat) check(pe_set_sample_format(session.engine, (int32_t)sc.sampleFormat));
   int32_t native = 0, out = 0, half = 0;
   check(pe_get_output_rate(session.engine, &native, &out, &half));
   const bool on = half > 0, want = sc.outputSampleRate > 0 && sc.outputSampleRate != sc.sampleRate;
@@ -437,6 +441,48 @@ void synthesize(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisCo
   audioBuffer.insert(audioBuffer.end(), r.pcm, r.pcm + n);
 }
 
+// the sample type of a delivery: int16 PCM, or G.711 codes (uint8_t) -- the value of a silent sample and where a fetched
+// call's rows are
+static void need_law(const SynthesisConfig& sc, const char* who) {
+  if (sc.sampleFormat != MuLaw && sc.sampleFormat != ALaw)
+    throw std::runtime_error(std::string(who) + ": SynthesisConfig::sampleFormat is not MuLaw or ALaw");
+}
+static int16_t silent_sample(const SynthesisConfig&, int16_t) { return 0; }
+static uint8_t silent_sample(const SynthesisConfig& sc, uint8_t) { return sc.sampleFormat == ALaw ? 0xD5 : 0xFF; }
+static void fetch_rows(pe_engine* engine, pe_result& r, const int16_t*& rows) {
+  check(pe_fetch(engine, 0, 1, &r));
+  rows = r.pcm;
+}
+static void fetch_rows(pe_engine* engine, pe_result& r, const uint8_t*& rows) {
+  check(pe_fetch(engine, 0, 0, &r));                    // (codes only: the int16 stay on the device)
+  const int64_t* offsets = nullptr;
+  int32_t n = 0;
+  check(pe_last_codes(engine, 0, &rows, &offsets, &n));
+  if (n != r.batch || !rows) throw std::runtime_error("the engine delivered no G.711 codes for this call");
+}
+
+void synthesizeEncoded(std::vector<PhonemeId>& phonemeIds, SynthesisConfig& synthesisConfig, ModelSession& session,
+                       std::vector<uint8_t>& codeBuffer, SynthesisResult& result) {
+  if (!session.engine) throw std::runtime_error("voice model is not loaded");
+  need_law(synthesisConfig, "synthesizeEncoded");
+  apply_output_rate(synthesisConfig, session);
+  const float scales[3] = {synthesisConfig.noiseScale, synthesisConfig.lengthScale, synthesisConfig.noiseW};
+  const int64_t offsets[2] = {0, (int64_t)phonemeIds.size()};
+  const int64_t sid = synthesisConfig.speakerId.value_or(0);
+  const int64_t* sids = synthesisConfig.speakerId ? &sid : nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  check(upload_utterances(session.engine, phonemeIds.data(), offsets, 1, scales, sids, synthesisConfig, 0));
+  check(pe_run(session.engine));
+  pe_result r;
+  const uint8_t* codes = nullptr;
+  fetch_rows(session.engine, r, codes);
+  result.inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const int64_t n = r.sample_offsets[1];
+  result.audioSeconds = (double)n / (double)delivered_rate(synthesisConfig);
+  result.realTimeFactor = result.audioSeconds > 0 ? result.inferSeconds / result.audioSeconds : 0.0;
+  codeBuffer.insert(codeBuffer.end(), codes, codes + n);
+}
+
 void synthesizeBatch(std::vector<std::vector<PhonemeId>>& phonemeIdLists, SynthesisConfig& synthesisConfig,
                      ModelSession& session, std::vector<std::vector<int16_t>>& audioBuffers,
                      SynthesisResult& result) {
@@ -487,9 +533,13 @@ void phonemes_to_ids(const std::vector<Phoneme>& phonemes, const PhonemizeConfig
   phonemeIds.push_back(config.idEos);
 }
 
-void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vector<int16_t>& audioBuffer,
-                 SynthesisResult& result, const std::function<void()>& audioCallback) {
+// The phrase loop of textToAudio and textToEncodedAudio, on the sample type T of what is delivered (int16_t: PCM; uint8_t:
+// G.711 codes): one loop, the two differ in where a fetched call's rows are and in the value of a silent sample.
+template <typename T>
+static void text_to_samples(PiperConfig& config, Voice& voice, std::string text, std::vector<T>& audioBuffer,
+                            SynthesisResult& result, const std::function<void()>& audioCallback) {
   const SynthesisConfig& sc = voice.synthesisConfig;
+  const T silent = silent_sample(sc, T());
   std::size_t sentenceSilenceSamples = 0;
   if (sc.sentenceSilenceSeconds > 0)
     sentenceSilenceSamples = (std::size_t)(sc.sentenceSilenceSeconds * delivered_rate(sc) * sc.channels);
@@ -599,15 +649,16 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   };
   // the finished group's PCM, copied out of the engine's (reused) host buffer: per phrase
-  auto collect = [&](const Group& g, std::vector<std::vector<int16_t>>& out) -> double {
+  auto collect = [&](const Group& g, std::vector<std::vector<T>>& out) -> double {
     out.clear();
     if (g.p1 == g.p0) return 0.0;
     const auto t0 = std::chrono::steady_clock::now();
     pe_result r;
-    check(pe_fetch(voice.session.engine, 0, 1, &r));
+    const T* rows = nullptr;
+    fetch_rows(voice.session.engine, r, rows);
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     out.resize(g.p1 - g.p0);
-    for (std::size_t k = 0; k < out.size(); ++k) out[k].assign(r.pcm + r.sample_offsets[k], r.pcm + r.sample_offsets[k + 1]);
+    for (std::size_t k = 0; k < out.size(); ++k) out[k].assign(rows + r.sample_offsets[k], rows + r.sample_offsets[k + 1]);
     result.audioSeconds += (double)r.sample_offsets[out.size()] / (double)delivered_rate(sc);
     return dt;
   };
@@ -616,7 +667,7 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
   std::size_t open_sentence = (std::size_t)-1;     // sentence whose audio is being assembled in audioBuffer
   auto close_sentence = [&]() {
     if (open_sentence == (std::size_t)-1) return;
-    if (sentenceSilenceSamples > 0) audioBuffer.insert(audioBuffer.end(), sentenceSilenceSamples, (int16_t)0);
+    if (sentenceSilenceSamples > 0) audioBuffer.insert(audioBuffer.end(), sentenceSilenceSamples, silent);
     if (audioCallback) {
       audioCallback();      // the callback must copy: the buffer is cleared afterwards (piper.cpp:591-595)
       audioBuffer.clear();
@@ -625,7 +676,7 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
   };
   // sentences without a single phrase (empty) still get their silence + callback, in order
   std::size_t next_sentence = 0;
-  auto emit = [&](const Group& g, const std::vector<std::vector<int16_t>>& pcm) {
+  auto emit = [&](const Group& g, const std::vector<std::vector<T>>& pcm) {
     for (std::size_t k = g.p0; k < g.p1; ++k) {
       const std::size_t si = phrases[k].sentence;
       if (si != open_sentence) {
@@ -635,10 +686,10 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
         next_sentence = si + 1;
       }
       audioBuffer.insert(audioBuffer.end(), pcm[k - g.p0].begin(), pcm[k - g.p0].end());
-      audioBuffer.insert(audioBuffer.end(), phrases[k].silenceAfter, (int16_t)0);
+      audioBuffer.insert(audioBuffer.end(), phrases[k].silenceAfter, silent);
     }
   };
-  std::vector<std::vector<int16_t>> cur, prev;
+  std::vector<std::vector<T>> cur, prev;
   if (!groups.empty()) result.inferSeconds += enqueue(groups[0]);
   for (std::size_t gi = 0; gi < groups.size(); ++gi) {
     result.inferSeconds += collect(groups[gi], cur);                        // waits for group gi
@@ -668,8 +719,47 @@ void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vecto
   if (result.audioSeconds > 0) result.realTimeFactor = result.inferSeconds / result.audioSeconds;
 }
 
+void textToAudio(PiperConfig& config, Voice& voice, std::string text, std::vector<int16_t>& audioBuffer,
+                 SynthesisResult& result, const std::function<void()>& audioCallback) {
+  text_to_samples<int16_t>(config, voice, text, audioBuffer, result, audioCallback);
+}
+
+void textToEncodedAudio(PiperConfig& config, Voice& voice, std::string text, std::vector<uint8_t>& codeBuffer,
+                        SynthesisResult& result, const std::function<void()>& audioCallback) {
+  need_law(voice.synthesisConfig, "textToEncodedAudio");
+  text_to_samples<uint8_t>(config, voice, text, codeBuffer, result, audioCallback);
+}
+
 void textToWavFile(PiperConfig& config, Voice& voice, std::string text, std::ostream& audioFile,
                    SynthesisResult& result) {
+  if (voice.synthesisConfig.sampleFormat != S16) {
+    // G.711: an 18-byte fmt chunk (tag 7 mu-law / 6 A-law, 8 bits, block align 1, cbSize 0), a fact chunk with the sample
+    // count, then the codes (padded to an even length, as RIFF asks)
+    std::vector<uint8_t> codes;
+    textToEncodedAudio(config, voice, text, codes, result, nullptr);
+    const SynthesisConfig& sc = voice.synthesisConfig;
+    const uint32_t n = (uint32_t)codes.size(), pad = n & 1u, rate = (uint32_t)delivered_rate(sc), ch = (uint32_t)sc.channels;
+    audioFile.write("RIFF", 4);
+    write_le(audioFile, 4 + (8 + 18) + (8 + 4) + (8 + n + pad), 4);
+    audioFile.write("WAVE", 4);
+    audioFile.write("fmt ", 4);
+    write_le(audioFile, 18, 4);
+    write_le(audioFile, sc.sampleFormat == ALaw ? 6 : 7, 2);
+    write_le(audioFile, ch, 2);
+    write_le(audioFile, rate, 4);
+    write_le(audioFile, rate * ch, 4);
+    write_le(audioFile, ch, 2);
+    write_le(audioFile, 8, 2);
+    write_le(audioFile, 0, 2);
+    audioFile.write("fact", 4);
+    write_le(audioFile, 4, 4);
+    write_le(audioFile, n / std::max<uint32_t>(ch, 1), 4);
+    audioFile.write("data", 4);
+    write_le(audioFile, n, 4);
+    audioFile.write((const char*)codes.data(), codes.size());
+    if (pad) audioFile.put('\0');
+    return;
+  }
   std::vector<int16_t> audio;
   textToAudio(config, voice, text, audio, result, nullptr);
   const SynthesisConfig& sc = voice.synthesisConfig;

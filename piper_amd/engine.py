@@ -22,11 +22,25 @@ class EngineError(RuntimeError):
 class Synthesis:
     """Result of one (batched) synthesis call. Arrays are copies (the C side reuses its buffers)."""
 
-    def __init__(self, audio: List[np.ndarray], pcm: List[np.ndarray], frames: np.ndarray, infer_seconds: float):
+    def __init__(self, audio: List[np.ndarray], pcm: List[np.ndarray], frames: np.ndarray, infer_seconds: float, codes=None):
         self.audio = audio
         self.pcm = pcm
         self.frames = frames
         self.infer_seconds = infer_seconds
+        self.codes = codes          # G.711 codes, one uint8 array per utterance; None with the sample format "s16"
+
+
+class Chunk(tuple):
+    """One row of a stream chunk: the ``(float chunk or None, int16 chunk)`` pair it always was, with ``codes`` -- the
+    chunk's G.711 codes as a uint8 array, None with the sample format "s16"."""
+
+    def __new__(cls, audio, pcm, codes=None):
+        t = super().__new__(cls, (audio, pcm))
+        t.codes = codes
+        return t
+
+    audio = property(lambda self: self[0])
+    pcm = property(lambda self: self[1])
 
 
 def per_utterance_scales(scales, batch: int):
@@ -303,7 +317,18 @@ class Engine:
         if want_pcm and total:
             p = np.frombuffer(bytearray(C.string_at(res.pcm, 2 * total)), np.int16)
             pcm = [p[offs[i]:offs[i + 1]] for i in range(B)]
-        return Synthesis(audio, pcm, frames, res.infer_seconds)
+        return Synthesis(audio, pcm, frames, res.infer_seconds, self._last_codes(0))
+
+    def _last_codes(self, which: int):
+        """pe_last_codes as a list of uint8 arrays, one per row; None when that call ran with the format "s16"."""
+        cp, op, rows = C.POINTER(C.c_uint8)(), C.POINTER(C.c_int64)(), C.c_int32()
+        self._check(self._lib.pe_last_codes(self._h, int(which), C.byref(cp), C.byref(op), C.byref(rows)))
+        if rows.value == 0:
+            return None
+        offs = np.frombuffer(C.string_at(op, 8 * (rows.value + 1)), np.int64)
+        total = int(offs[-1])
+        c = np.frombuffer(bytearray(C.string_at(cp, total)) if total else bytearray(), np.uint8)
+        return [c[offs[i]:offs[i + 1]] for i in range(rows.value)]
 
     # ---- API
     def synthesize_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, noise_w=None, noise_z=None,
@@ -422,12 +447,13 @@ class Engine:
         return res
 
     def stream(self, ids, scales=(0.667, 1.0, 0.8), sid=None, chunk_frames: int = 45, noise_w=None, noise_z=None, seed=None,
-               speaker=None):
+               speaker=None, codes: bool = False):
         """Generator over (float_audio, int16_pcm) chunks of one utterance: encoder/flow once, then the
         vocoder on exact-halo windows of `chunk_frames` frames (reference default 45). Concatenating
         the float chunks gives exactly the unchunked waveform; pcm is peak-normalised per chunk, or follows
         the level set by ``set_stream_gain``. ``seed``: the utterance's noise seed (pe_stream_begin_seeded). ``speaker``: the utterance's
-        entry of ``speakers`` as in ``synthesize_batch`` (pe_stream_begin_blended)."""
+        entry of ``speakers`` as in ``synthesize_batch`` (pe_stream_begin_blended). ``codes`` True: triples
+        (float_audio, int16_pcm, uint8 G.711 codes or None), the codes of ``set_sample_format``."""
         ids_np = np.ascontiguousarray(ids, np.int64)
         sc = (C.c_float * 3)(*[float(s) for s in scales])
         keep: list = []
@@ -455,10 +481,19 @@ class Engine:
                 if done >= frames.value:
                     return
                 done = min(frames.value, done + int(chunk_frames))
-                yield np.zeros(0, np.float32), np.zeros(0, np.int16)
+                if codes:
+                    yield (np.zeros(0, np.float32), np.zeros(0, np.int16),
+                           None if self.sample_format == "s16" else np.zeros(0, np.uint8))
+                else:
+                    yield np.zeros(0, np.float32), np.zeros(0, np.int16)
                 continue
             done = min(frames.value, done + int(chunk_frames))
-            yield (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
+            pair = (np.ctypeslib.as_array(a, (n.value,)).copy(), np.ctypeslib.as_array(p, (n.value,)).copy())
+            if codes:
+                c = self._last_codes(1)
+                yield pair + (None if c is None else c[0],)
+            else:
+                yield pair
 
     def stream_batch(self, id_lists, scales=(0.667, 1.0, 0.8), sids=None, chunk_frames=45, noise_w=None, noise_z=None,
                      want_audio: bool = True, timing: Optional[Timing] = None, seeds=None, speakers=None):
@@ -510,12 +545,15 @@ class Engine:
                 if not np.any(before < self.stream_frames):
                     return
                 empty = np.zeros(0, np.float32) if want_audio else None
-                yield [(empty, np.zeros(0, np.int16)) for _ in range(B)]
+                none = None if self.sample_format == "s16" else np.zeros(0, np.uint8)
+                yield [Chunk(empty, np.zeros(0, np.int16), none) for _ in range(B)]
                 k += 1
                 continue
             p = np.frombuffer(bytearray(C.string_at(ch.pcm, 2 * total)), np.int16)
             a = np.frombuffer(bytearray(C.string_at(ch.audio, 4 * total)), np.float32) if ch.audio else None
-            yield [(None if a is None else a[offs_k[b]:offs_k[b + 1]], p[offs_k[b]:offs_k[b + 1]]) for b in range(B)]
+            c = self._last_codes(1)
+            yield [Chunk(None if a is None else a[offs_k[b]:offs_k[b + 1]], p[offs_k[b]:offs_k[b + 1]],
+                         None if c is None else c[b]) for b in range(B)]
             k += 1
 
     def stream_pool(self, slots: int, max_frames: int) -> "StreamPool":
@@ -537,6 +575,40 @@ class Engine:
         voice's header carries none (an .onnx: pass ``audio.sample_rate`` of its .onnx.json). ``rate`` None, 0 or the
         native rate: off. Sample counts are then in output samples; ``frames`` stays in native frames."""
         self._check(self._lib.pe_set_output_rate(self._h, int(native or 0), int(rate or 0)))
+
+    SAMPLE_FORMATS = ("s16", "ulaw", "alaw")
+
+    def set_sample_format(self, fmt: Optional[str] = "s16"):
+        """Also deliver G.711 codes (include/piper_hip.h: pe_set_sample_format): ``"ulaw"`` or ``"alaw"``, one uint8 code per
+        delivered int16 sample, companded on the device -- ``codes`` of every result and chunk. ``"s16"`` or None: off.
+        The int16 and the floats are what they are without it."""
+        fmt = "s16" if fmt is None else fmt
+        if fmt not in self.SAMPLE_FORMATS:
+            raise EngineError(f"unknown sample format {fmt!r}: one of {self.SAMPLE_FORMATS}")
+        self._check(self._lib.pe_set_sample_format(self._h, self.SAMPLE_FORMATS.index(fmt)))
+
+    @property
+    def sample_format(self) -> str:
+        f = C.c_int32()
+        self._check(self._lib.pe_get_sample_format(self._h, C.byref(f)))
+        return self.SAMPLE_FORMATS[f.value]
+
+    def debug_g711(self, fmt: str, rows, flat: bool = False, pad: int = 0, canary: int = 0xA5, slack: int = 64):
+        """Test hook (pe_debug_g711): the encoder kernel alone on int16 ``rows`` -- the rows form, or with ``flat`` the flat
+        form on the one row. What lies behind a row's end in the staging matrix holds ``pad``. Returns (codes of the packed
+        rows, the ``slack`` bytes behind them), the output buffer pre-filled with ``canary``."""
+        B = len(rows)
+        valid = np.asarray([len(r) for r in rows], np.int32)
+        stride = max(1, int(valid.max()) if B else 1)
+        x = np.full((B, stride), pad, np.int16)
+        for b, r in enumerate(rows):
+            x[b, :len(r)] = np.asarray(r, np.int16)
+        total = int(valid.sum())
+        out = np.full(total + slack, canary, np.uint8)
+        self._check(self._lib.pe_debug_g711(self._h, self.SAMPLE_FORMATS.index(fmt), int(bool(flat)),
+                                            x.ctypes.data_as(C.POINTER(C.c_int16)), B, stride, valid.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out[:total].copy(), out[total:].copy()
 
     GAIN_MODES = ("chunk", "running", "fixed")
 
@@ -1067,7 +1139,7 @@ class StreamPool:
 
     def next(self, chunk_frames: int = 45, per_slot=None, want_audio: bool = True) -> dict:
         """The next chunk of every listener, one batched vocoder pass: ``{slot: (float chunk or None, int16 chunk)}`` for the
-        slots that got samples -- empty when no slot has frames left (with the stream limiter also when every listener only
+        slots that got samples (a ``Chunk``: the pair, with ``.codes`` under a G.711 sample format) -- empty when no slot has frames left (with the stream limiter also when every listener only
         held samples back: ask ``frames_done`` / ``free_slots``). ``per_slot``: ``{slot: frames}`` (or an array of
         ``slots`` entries, 0 = default) overriding ``chunk_frames``, e.g. a short first chunk for a newcomer."""
         eng, S = self._eng, self.slots
@@ -1088,7 +1160,8 @@ class StreamPool:
             return {}
         p = np.frombuffer(bytearray(C.string_at(ch.pcm, 2 * total)), np.int16)
         a = np.frombuffer(bytearray(C.string_at(ch.audio, 4 * total)), np.float32) if ch.audio else None
-        return {s: (None if a is None else a[offs[s]:offs[s + 1]], p[offs[s]:offs[s + 1]])
+        c = eng._last_codes(1)
+        return {s: Chunk(None if a is None else a[offs[s]:offs[s + 1]], p[offs[s]:offs[s + 1]], None if c is None else c[s])
                 for s in range(S) if offs[s + 1] > offs[s]}
 
     def leave(self, slot: int):
@@ -1129,3 +1202,24 @@ def limiter_window(fs: int, window_ms: float, lib=None):
     if lib.pe_limiter_window(int(fs), float(window_ms), C.byref(w), out.ctypes.data_as(C.POINTER(C.c_double)), out.size, C.byref(n)):
         raise EngineError(lib.pe_last_error().decode(errors="replace"))
     return w.value, out
+
+
+def _g711(entry, fmt: str, x: np.ndarray, out_dtype, in_ctype, out_ctype, lib=None) -> np.ndarray:
+    lib = lib if lib is not None else L.get_lib()
+    if fmt not in ("ulaw", "alaw"):
+        raise EngineError(f"G.711 format {fmt!r}: 'ulaw' or 'alaw'")
+    out = np.zeros(x.size, out_dtype)
+    if getattr(lib, entry)(1 if fmt == "ulaw" else 2, x.ctypes.data_as(C.POINTER(in_ctype)),
+                           out.ctypes.data_as(C.POINTER(out_ctype)), x.size):
+        raise EngineError(lib.pe_last_error().decode(errors="replace"))
+    return out
+
+
+def g711_encode(fmt: str, pcm, lib=None) -> np.ndarray:
+    """int16 samples -> G.711 codes (pe_g711_encode; host only): the law of the ITU-T G.191 tools, ``fmt`` "ulaw" / "alaw"."""
+    return _g711("pe_g711_encode", fmt, np.ascontiguousarray(pcm, np.int16).ravel(), np.uint8, C.c_int16, C.c_uint8, lib)
+
+
+def g711_decode(fmt: str, codes, lib=None) -> np.ndarray:
+    """G.711 codes -> int16 samples (pe_g711_decode; host only), the expanders of the same tools."""
+    return _g711("pe_g711_decode", fmt, np.ascontiguousarray(codes, np.uint8).ravel(), np.int16, C.c_uint8, C.c_int16, lib)

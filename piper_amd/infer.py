@@ -15,7 +15,8 @@ lines without a seed draw from the engine's own stream in the same call. ``--spe
 the ``speaker_id_map`` of the ``.json`` beside the model) speaks every line with that weighted mix of speaker embeddings, the
 weights used as given; a line's ``"speaker_blend": {"1": 0.7, "3": 0.3}`` or ``"speaker_vector": [...]`` (the embedding
 itself) or its ``speaker_id`` wins over the option, and ``speaker_id`` beside either key on one line is an error that names
-the line (new).
+the line (new). ``--sample-format ulaw|alaw`` (new) writes G.711 WAVs -- 8-bit mu-law or A-law, format tag 7 / 6, with a
+``fact`` chunk --, the codes companded on the GPU from the int16 the default format would have written.
 
     python -m piper_amd.infer --model voice.onnx --output-dir out/ < utterances.jsonl
 """
@@ -179,6 +180,8 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
     parser.add_argument("--limiter", action="store_true",
                         help="where the ceiling and --target-lufs conflict, turn down only the peaks (look-ahead limiter on the GPU)")
     parser.add_argument("--limiter-ms", type=float, default=5.0, help="window of --limiter in ms, 1 to 10")
+    parser.add_argument("--sample-format", choices=("s16", "ulaw", "alaw"), default="s16",
+                        help="ulaw / alaw: write G.711 WAVs (8-bit mu-law / A-law), companded on the GPU")
     parser.add_argument("--noise-scale", type=float, default=0.667)
     parser.add_argument("--noise-scale-w", type=float, default=0.8)
     parser.add_argument("--length-scale", type=float, default=1.0)
@@ -205,6 +208,7 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
             engine.set_output_rate(None, native=args.sample_rate)      # (an .onnx carries no rate of its own)
         engine.set_loudness(args.target_lufs, args.peak_ceiling_db, true_peak=args.true_peak, limiter=args.limiter,
                             limiter_ms=args.limiter_ms)
+    engine.set_sample_format(args.sample_format)
     scales = (args.noise_scale, args.length_scale, args.noise_scale_w)
     lines = list(stdin if stdin is not None else sys.stdin)
     utts = read_utterances(lines)
@@ -239,7 +243,12 @@ def main(argv=None, *, stdin=None, lib=None) -> int:
         audio_sec = sum(p.shape[-1] for p in res.pcm) / wav_rate
         _LOGGER.debug("Real-time factor for %s..%s: %0.4f (infer=%0.4f sec, audio=%0.2f sec)", group[0][0] + 1,
                       group[-1][0] + 1, infer_sec / audio_sec if audio_sec > 0 else 0.0, infer_sec, audio_sec)
-        for (idx, _, _), pcm in zip(group, res.pcm):
+        for b, ((idx, _, _), pcm) in enumerate(zip(group, res.pcm)):
+            if args.sample_format != "s16":
+                from .voice import write_g711_wav
+                with open(out_dir / f"{idx}.wav", "wb") as f:
+                    write_g711_wav(f, args.sample_format, wav_rate, res.codes[b].tobytes())
+                continue
             write_wav(out_dir / f"{idx}.wav", wav_rate, pcm)
     engine.close()
     return 0

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import json
 import logging
+import struct
 import unicodedata
 import wave
 from dataclasses import dataclass
@@ -49,25 +50,49 @@ def phonemes_to_ids_cpp(phonemes, id_map, intersperse_pad: bool = True) -> List[
 
 _LOGGER = logging.getLogger(__name__)
 
+# G.711 sample formats (Engine.set_sample_format): the WAVE format tag and the code of a zero sample, which is what silence
+# is padded with -- 0x00 is full-scale negative in mu-law
+G711_WAV_TAG = {"ulaw": 7, "alaw": 6}
+G711_ZERO = {"ulaw": b"\xff", "alaw": b"\xd5"}
+
+
+def write_g711_wav(f, sample_format: str, sample_rate: int, codes: bytes):
+    """A mono G.711 WAV into the binary file ``f``. The ``wave`` module writes PCM only, so the header is written by hand:
+    an 18-byte ``fmt `` chunk (tag 7 mu-law / 6 A-law, 1 channel, rate, byte rate = rate, block align 1, 8 bits, cbSize
+    0), a ``fact`` chunk with the sample count, then ``data`` (padded to an even length, as RIFF asks)."""
+    n = len(codes)
+    pad = n & 1
+    f.write(b"RIFF" + struct.pack("<I", 4 + (8 + 18) + (8 + 4) + (8 + n + pad)) + b"WAVE")
+    f.write(b"fmt " + struct.pack("<IHHIIHHH", 18, G711_WAV_TAG[sample_format], 1, int(sample_rate), int(sample_rate), 1, 8, 0))
+    f.write(b"fact" + struct.pack("<II", 4, n))
+    f.write(b"data" + struct.pack("<I", n))
+    f.write(codes)
+    if pad:
+        f.write(b"\0")
+
 
 @dataclass
 class PiperVoice:
     session: Engine
     config: PiperConfig
     output_sample_rate: Optional[int] = None      # None: the voice's own rate (config.sample_rate)
+    sample_format: str = "s16"                    # "ulaw" / "alaw": the *_raw methods return G.711 code bytes
 
     @staticmethod
     def load(model_path: Union[str, Path], config_path: Optional[Union[str, Path]] = None,
              use_cuda: bool = True, device: int = 0, output_sample_rate: Optional[int] = None,
              target_lufs: Optional[float] = None, peak_ceiling_db: float = -1.0, true_peak: bool = False,
-             limiter: bool = False, limiter_ms: float = 5.0) -> "PiperVoice":
+             limiter: bool = False, limiter_ms: float = 5.0, sample_format: Optional[str] = None) -> "PiperVoice":
         """Load an ONNX voice and its config. ``use_cuda`` is accepted for signature compatibility;
         the engine always runs on the GPU (``device``). ``output_sample_rate`` (new): deliver the audio at this rate,
         resampled on the GPU before the int16 conversion (Engine.set_output_rate; the config's rate is the native one).
         ``target_lufs`` (new): deliver every whole utterance at this integrated loudness (ITU-R BS.1770-4, mono) under a
         ceiling of ``peak_ceiling_db`` dB on the sample peak, or with ``true_peak`` on the true peak (dBTP, BS.1770-4
         Annex 2) as well (Engine.set_loudness); ``limiter``: where ceiling and target conflict, only the peaks are turned
-        down, by a zero-phase window of ``limiter_ms`` (1 to 10; either kind of ceiling). Streams keep their chunk rule."""
+        down, by a zero-phase window of ``limiter_ms`` (1 to 10; either kind of ceiling). Streams keep their chunk rule.
+        ``sample_format`` (new): ``"ulaw"`` or ``"alaw"`` -- the ``*_raw`` methods then return G.711 code bytes, one per
+        sample, companded on the GPU (Engine.set_sample_format), sentence silence is the law's zero code, and
+        ``synthesize`` writes a G.711 WAV; None or ``"s16"``: 16-bit PCM as ever."""
         if config_path is None:
             config_path = f"{model_path}.json"
         with open(config_path, "r", encoding="utf-8") as config_file:
@@ -83,7 +108,9 @@ class PiperVoice:
                                  limiter_ms=float(limiter_ms))
         elif true_peak or limiter:                           # (remembered for a later set_loudness)
             session.set_loudness(None, true_peak=bool(true_peak), limiter=bool(limiter), limiter_ms=float(limiter_ms))
-        return PiperVoice(config=config, session=session, output_sample_rate=output_sample_rate or None)
+        session.set_sample_format(sample_format)
+        return PiperVoice(config=config, session=session, output_sample_rate=output_sample_rate or None,
+                          sample_format=session.sample_format)
 
     @property
     def sample_rate(self) -> int:
@@ -124,7 +151,16 @@ class PiperVoice:
                    length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
                    noise_w: Optional[float] = None, sentence_silence: float = 0.0, seed: Optional[int] = None,
                    speaker_blend=None, speaker_vector=None):
-        """Synthesize WAV audio from text. ``seed``, ``speaker_blend`` and ``speaker_vector``: as in synthesize_stream_raw."""
+        """Synthesize WAV audio from text. ``seed``, ``speaker_blend`` and ``speaker_vector``: as in synthesize_stream_raw.
+        With a G.711 ``sample_format`` the ``wave`` module cannot write the file: ``wav_file`` is then a binary file
+        object, and gets a mu-law / A-law WAV (write_g711_wav)."""
+        if self.sample_format != "s16":
+            codes = b"".join(self.synthesize_stream_raw(text, speaker_id=speaker_id, length_scale=length_scale,
+                                                        noise_scale=noise_scale, noise_w=noise_w,
+                                                        sentence_silence=sentence_silence, seed=seed,
+                                                        speaker_blend=speaker_blend, speaker_vector=speaker_vector))
+            write_g711_wav(wav_file, self.sample_format, self.sample_rate, codes)
+            return
         wav_file.setframerate(self.sample_rate)
         wav_file.setsampwidth(2)
         wav_file.setnchannels(1)
@@ -143,7 +179,10 @@ class PiperVoice:
         ``speaker_blend`` / ``speaker_vector``: every sentence's speaker, as in synthesize_ids_to_raw."""
         sentence_phonemes = self.phonemize(text)
         num_silence_samples = int(sentence_silence * self.sample_rate)
-        silence_bytes = bytes(num_silence_samples * 2)
+        if self.sample_format != "s16":                      # one byte per sample, the law's zero code
+            silence_bytes = G711_ZERO[self.sample_format] * num_silence_samples
+        else:
+            silence_bytes = bytes(num_silence_samples * 2)
         for k, phonemes in enumerate(sentence_phonemes):
             phoneme_ids = self.phonemes_to_ids(phonemes)
             yield self.synthesize_ids_to_raw(phoneme_ids, speaker_id=speaker_id, length_scale=length_scale,
@@ -229,7 +268,15 @@ class PiperVoice:
             r = self.session.synthesize_batch([phoneme_ids], self._scales(length_scale, noise_scale, noise_w),
                                               sids=None if sid is None else [sid], timing=timing,
                                               seeds=None if seed is None else [seed])
-        return r.pcm[0].tobytes()
+        return self._raw(r)[0]
+
+    def _raw(self, r) -> List[bytes]:
+        """What the *_raw methods return per utterance: the int16 bytes, or the G.711 codes under a sample format."""
+        if self.sample_format != "s16":
+            if r.codes is None:
+                raise RuntimeError(f"the engine delivered no codes: its sample format is not {self.sample_format!r}")
+            return [c.tobytes() for c in r.codes]
+        return [p.tobytes() for p in r.pcm]
 
     def synthesize_ids_batch_to_raw(self, phoneme_id_lists: List[List[int]], speaker_ids=None,
                                     length_scale: Optional[float] = None, noise_scale: Optional[float] = None,
@@ -274,4 +321,4 @@ class PiperVoice:
             r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids)
         else:
             r = self.session.synthesize_batch(phoneme_id_lists, scales, sids=sids, timing=timing, seeds=seeds)
-        return [p.tobytes() for p in r.pcm]
+        return self._raw(r)
